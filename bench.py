@@ -8,12 +8,16 @@ costates -> aux system in LDS -> Riccati on MFMA tiles -> loss/gradient, written
 all-gather of those rows (the one exchange step of a data-parallel PDP iteration), issued on a side stream so that it overlaps
 the kernel of the next step.  Weak scaling: every rank owns its own B trajectories.
 
-    python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`, `cpu_baseline`, `cpu_baseline_1thread` and - on one
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run sets up, warms up, times the
+K steps and prints that line - nothing else.  --full adds everything measured beside the headline: `roofline` (isolated-launch kernel time,
+recorded traffic, register counts), the repeated timed regions of config.launch_diagnostics, `cpu_baseline`, `cpu_baseline_1thread` and - on one
 GPU - `other_configs` (the other BASELINE.json configurations and the complete IRL iterations incl. the OC solve, each timed here
-with HIP events and priced against SURVEY.md section 8d's per-trajectory figures) and, for N > 1, `per_rank` kernel / exchange times.
+with HIP events and priced against SURVEY.md section 8d's per-trajectory figures), `scaling_configs` and, for N > 1, `per_rank` kernel / exchange times.
+--dump-outputs DIR writes what the last timed step computed (rank 0's x, lam, loss, grad, status and, for N > 1, the gathered rows) as
+DIR/<name>.npy in float64; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -718,6 +722,23 @@ def scaling_configs(torch, dist, world, rank, steps, verify=False):
     return res if rank == 0 else None
 
 
+DUMP_LIMIT_BYTES = 60e6
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array (trajectories on axis 0) as dirname/<name>.npy in float64.  When together they exceed DUMP_LIMIT_BYTES, each keeps a fixed,
+    seeded sample of its rows (the same fraction of every array), and the row indices go to dirname/<name>_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {name: np.asarray(a, dtype=np.float64) for name, a in arrays.items()}
+    frac = min(1.0, DUMP_LIMIT_BYTES / sum(a.nbytes for a in arrays.values()))
+    for name, a in arrays.items():
+        if frac < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(len(a), max(1, int(len(a) * frac)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -734,7 +755,14 @@ def main():
     ap.add_argument("--verify-exchange", action="store_true",
                     help="after timing, check on every rank that the exchanged rows equal the single-process kernel on the whole batch and that the all-reduce form "
                          "gives their mean (adds a ragged total); results under `verified`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beside the headline: roofline / kernel-only timing, repeated timed regions, CPU baseline, other and scaling "
+                         "configurations (the --no-* options switch single parts off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # (the host driver only supports dmabuf IPC: without it RCCL's cross-process set-up fails; exported by the image, kept here)
     import torch
@@ -790,11 +818,13 @@ def main():
     else:
         prepared = [mdl.oc_pdp_grad_prepared(u, theta, dx, du, x0) for i in range(1 if one_stream else 2)]
     out = prepared[0][1]
-    ref_rows = mdl.oc_pdp_grad(u, theta, dx, du, x0=x0, buffers=bufs, packed=True)["packed"]
-    for call_, out_ in prepared:
-        call_()
-        if not torch.equal(out_["packed"], ref_rows):
-            raise SystemExit("the prepared call does not reproduce runtime.oc_pdp_grad bit for bit")
+    ref_rows = None                     # (--full: the general wrapper's rows, which every prepared call and the timed steps must reproduce bit for bit)
+    if args.full:
+        ref_rows = mdl.oc_pdp_grad(u, theta, dx, du, x0=x0, buffers=bufs, packed=True)["packed"]
+        for call_, out_ in prepared:
+            call_()
+            if not torch.equal(out_["packed"], ref_rows):
+                raise SystemExit("the prepared call does not reproduce runtime.oc_pdp_grad bit for bit")
     torch.cuda.synchronize()
     main_stream = torch.cuda.current_stream()
     pool = [] if one_stream else [torch.cuda.Stream() for _ in range(6)]
@@ -808,7 +838,7 @@ def main():
         for _c, out_ in prepared:
             if int(out_["status"].sum()) != 0 or not bool(torch.isfinite(out_["grad"]).all()):
                 raise SystemExit("benchmark inputs produced numerical trouble (status flags set)")
-            if not torch.equal(out_["packed"], ref_rows):
+            if ref_rows is not None and not torch.equal(out_["packed"], ref_rows):
                 raise SystemExit("steps issued on alternating streams do not reproduce the single call bit for bit")
     check_outputs()
 
@@ -853,7 +883,7 @@ def main():
                 _call()
 
     exch_us = None
-    if distributed:       # the exchange alone, blocking, on the compute stream: what a non-overlapped step would add
+    if distributed and args.full:       # the exchange alone, blocking, on the compute stream: what a non-overlapped step would add
         pk = og.buffers[0]
         exch_us = 1e3 * _event_ms(torch, lambda: parallel.gather_packed(pk, out=og.gathered[0]), reps=10, warm=2)
     # ---- kernel-only timing with HIP events on the launch stream (roofline.achieved): the median over KERNEL_SAMPLES isolated launches.  It comes BEFORE the warm-up
@@ -863,9 +893,15 @@ def main():
     import gc
     gc.collect()
     gc.disable()                        # (until the timed region is over: see there)
+    # (a plain run skips the sampling but keeps the load in front of the placement calibration below, so that it times its candidates at sustained clocks)
     KERNEL_SAMPLES = max(200, args.steps)
-    kern_ms = _event_ms(torch, prepared[0][0], reps=KERNEL_SAMPLES, warm=2)
-    headline_window = kern_ms.wins[0]
+    kern_ms, headline_window = None, None
+    if args.full:
+        kern_ms = _event_ms(torch, prepared[0][0], reps=KERNEL_SAMPLES, warm=2)
+        headline_window = kern_ms.wins[0]
+    elif PREHEAT is not None:
+        PREHEAT()
+        torch.cuda.synchronize()
 
     placement = None
     if pool:
@@ -884,12 +920,16 @@ def main():
             finish()
             torch.cuda.synchronize()
             tried.append((time.perf_counter() - t_) / CAL_STEPS * 1e3)
+        if distributed:                 # one placement for the whole job (the slowest rank's time per candidate decides): the --full diagnostics below issue
+            tried_ = torch.tensor(tried, dtype=torch.float64, device="cuda")      # collectives only when a stream pair was chosen, and every rank must issue the same ones
+            parallel.all_reduce_(tried_, op=dist.ReduceOp.MAX)
+            tried = tried_.tolist()
         best_ = int(np.argmin(tried))
         use(cands[best_][1])
         placement = {"candidates": [c_[0] for c_ in cands], "ms_per_step": tried, "chosen": cands[best_][0], "steps_per_candidate": CAL_STEPS,
                      "what": "HIP streams share a few hardware queues in creation order; which pair of step streams keeps the kernels, the side stream and RCCL's stream "
-                             "in different queues is found by timing the real step on each candidate before the warm-up steps (per rank; every rank issues the same "
-                             "number of collectives)"}
+                             "in different queues is found by timing the real step on each candidate before the warm-up steps (every rank issues the same "
+                             "number of collectives; for N > 1 the maximum over ranks per candidate, so that all ranks take the same placement)"}
 
     for _ in range(args.warmup):
         out = step()
@@ -943,7 +983,7 @@ def main():
             graph.replay()
     else:
         for _ in range(args.steps):
-            step()
+            out = step()
     t_enq = time.perf_counter() - t0    # (diagnostic: the host's share - how long it took to ENQUEUE the K steps)
     finish()                            # every kernel and every exchange of the K steps has completed inside the timed region
     if os.environ.get("PDP_BENCH_POLL_END", "0") == "1":
@@ -956,12 +996,19 @@ def main():
     dt = time.perf_counter() - t0
     gc.enable()
     WINDOWS.append({"window": len(WINDOWS), "reps": args.steps, "event_ms_median": dt / args.steps * 1e3, "t0": c0, "t1": _clocks(), "what": "the timed region (K steps)"})
-    check_outputs()                     # what the timed steps wrote: status flags clear, finite, the single call's rows bit for bit
+    check_outputs()                     # what the timed steps wrote: status flags clear, finite (--full: the single call's rows bit for bit)
     timed_window = len(WINDOWS) - 1
+    if args.dump_outputs and rank == 0:     # the last timed step's outputs, before anything below overwrites them
+        dump = {name: out[name] for name in ("x", "lam", "loss", "grad", "status")}
+        if distributed:
+            dump["gathered_rows"] = og.result((og.k - 1) % DEPTH)
+        dump_outputs(args.dump_outputs, {name: t.cpu().numpy() for name, t in dump.items()})
     # (after the fact, not part of `value`: the same K steps again - is the first timed region of a process slower than the ones behind it? - and, for the record, the K
     # steps on ONE stream, the launch scheme of rounds 1 - 5)
     launch_diag = None
     if graph is None:
+        launch_diag = {"stream_placement": placement, "timed_region_host_enqueue_ms_total": t_enq * 1e3}
+    if graph is None and args.full:
         def region(fn, fin):
             if distributed:
                 dist.barrier()
@@ -979,16 +1026,17 @@ def main():
             use(None)
             ones = [region(step, finish) for _ in range(3)]
             use(chosen_)
-        launch_diag = {"timed_region_repeated_ms_per_step": reps, "one_stream_ms_per_step": ones, "stream_placement": placement,
-                       "timed_region_host_enqueue_ms_total": t_enq * 1e3}
+        launch_diag.update(timed_region_repeated_ms_per_step=reps, one_stream_ms_per_step=ones)
     per_rank = None
     if distributed:
         tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
         parallel.all_reduce_(tmax, op=dist.ReduceOp.MAX)
-        mine = torch.tensor([kern_ms, exch_us, dt / args.steps * 1e3], dtype=torch.float64, device="cuda")
-        allr = torch.empty((world, 3), dtype=torch.float64, device="cuda")
+        mine = torch.tensor([dt / args.steps * 1e3] + ([kern_ms, exch_us] if args.full else []), dtype=torch.float64, device="cuda")
+        allr = torch.empty((world, mine.numel()), dtype=torch.float64, device="cuda")
         parallel.all_gather_into(allr, mine)
-        per_rank = {"kernel_ms": allr[:, 0].tolist(), "exchange_us": allr[:, 1].tolist(), "ms_per_step": allr[:, 2].tolist()}
+        per_rank = {"ms_per_step": allr[:, 0].tolist()}
+        if args.full:
+            per_rank.update(kernel_ms=allr[:, 1].tolist(), exchange_us=allr[:, 2].tolist())
         dt = float(tmax.item())
         if args.verify_exchange:
             # the headline exchange: block r of the gathered rows == the kernel run here on rank r's inputs (weak scaling: rank r owns synth_inputs(B, 1000 + r))
@@ -1008,7 +1056,7 @@ def main():
                                     "gathered_rows_max_rel_diff_per_rank": allc[:, 1].tolist(), "allreduce_mean_max_rel_err_per_rank": allc[:, 2].tolist()}
 
     scal = None
-    if not args.no_scaling_configs and B == BATCH:
+    if args.full and not args.no_scaling_configs and B == BATCH:
         try:
             scal = scaling_configs(torch, dist, world, rank, args.steps, verify=args.verify_exchange)
         except Exception as ex:              # the headline line must survive a failure of the side measurements (all ranks fail alike: no collective is left half-way)
@@ -1024,35 +1072,55 @@ def main():
         dist.barrier()
     if rank == 0:
         value = world * B * args.steps / dt
-        traffic, traffic_cal, traffic_at, traffic_current = None, None, None, None
-        tf = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tf) and B == BATCH:
-            tj = json.load(open(tf))
-            traffic, traffic_cal = tj.get("oc_pdp_fused_kernel_hbm_bytes_per_launch"), tj.get("calibration")
-            # the counters cannot be collected inside a timed run: the figure is a RECORD - and says of which kernel sources (round-5 verdict, item 9: a kernel change
-            # silently kept the old number)
-            traffic_at = tj.get("collected")
-            try:
-                from pdp_amd import codegen as _cg
-                now = _cg.kernel_sources_digest()
-                traffic_current = bool(traffic_at and traffic_at.get("kernel_sources_sha1") == now)
-                if not traffic_current:
-                    print("bench.py: profiles/traffic.json was collected on other kernel sources (%s) than this tree's (%s): roofline.traffic is STALE until "
-                          "probes/profile_r06.sh is re-run" % ((traffic_at or {}).get("kernel_sources_sha1", "unrecorded")[:12], now[:12]), file=sys.stderr)
-            except Exception:
-                pass
-        ach_tflops = FLOP_PER_TRAJ * B / (kern_ms * 1e-3) / 1e12
-        ach_gbps = BYTES_PER_TRAJ * B / (kern_ms * 1e-3) / 1e9
-        kres = None
-        try:        # registers / spills of the dominant kernel, read from the code object that ran (llvm-readelf --notes of the model library)
-            from pdp_amd import codegen
-            tpw = 1 if B <= 256 else (2 if B <= 512 else 4)
-            kname = "oc_pdp_fused3_kernel<%d,0>" % tpw if os.environ.get("PDP_FUSED_VARIANT", "3") == "3" else "oc_pdp_fused_kernel<0>"
-            r = codegen.kernel_resources(mdl.path).get(kname)
-            if r is not None:
-                kres = {"instantiation": kname, "vgpr_count": r["vgpr"], "agpr_count": r["agpr"], "vgpr_spill_count": r["spill"], "scratch_bytes": r["scratch"]}
-        except Exception as ex:
-            kres = {"error": repr(ex)}
+        roof = None
+        if args.full:
+            traffic, traffic_cal, traffic_at, traffic_current = None, None, None, None
+            tf = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tf) and B == BATCH:
+                tj = json.load(open(tf))
+                traffic, traffic_cal = tj.get("oc_pdp_fused_kernel_hbm_bytes_per_launch"), tj.get("calibration")
+                # the counters cannot be collected inside a timed run: the figure is a RECORD - and says of which kernel sources (round-5 verdict, item 9: a kernel change
+                # silently kept the old number)
+                traffic_at = tj.get("collected")
+                try:
+                    from pdp_amd import codegen as _cg
+                    now = _cg.kernel_sources_digest()
+                    traffic_current = bool(traffic_at and traffic_at.get("kernel_sources_sha1") == now)
+                    if not traffic_current:
+                        print("bench.py: profiles/traffic.json was collected on other kernel sources (%s) than this tree's (%s): roofline.traffic is STALE until "
+                              "probes/profile_r06.sh is re-run" % ((traffic_at or {}).get("kernel_sources_sha1", "unrecorded")[:12], now[:12]), file=sys.stderr)
+                except Exception:
+                    pass
+            ach_tflops = FLOP_PER_TRAJ * B / (kern_ms * 1e-3) / 1e12
+            ach_gbps = BYTES_PER_TRAJ * B / (kern_ms * 1e-3) / 1e9
+            kres = None
+            try:        # registers / spills of the dominant kernel, read from the code object that ran (llvm-readelf --notes of the model library)
+                from pdp_amd import codegen
+                tpw = 1 if B <= 256 else (2 if B <= 512 else 4)
+                kname = "oc_pdp_fused3_kernel<%d,0>" % tpw if os.environ.get("PDP_FUSED_VARIANT", "3") == "3" else "oc_pdp_fused_kernel<0>"
+                r = codegen.kernel_resources(mdl.path).get(kname)
+                if r is not None:
+                    kres = {"instantiation": kname, "vgpr_count": r["vgpr"], "agpr_count": r["agpr"], "vgpr_spill_count": r["spill"], "scratch_bytes": r["scratch"]}
+            except Exception as ex:
+                kres = {"error": repr(ex)}
+            roof = {"bound": "mfma", "kernel": "oc_pdp_fused3_kernel" if os.environ.get("PDP_FUSED_VARIANT", "3") == "3" else "oc_pdp_fused_kernel", "achieved": ach_tflops, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": ach_tflops / FP64_MFMA_PEAK_TFLOPS, "traffic": traffic, "traffic_calibration": traffic_cal, "kernel_resources": kres,
+                    "traffic_collected_at": traffic_at, "traffic_collected_on_these_kernel_sources": traffic_current,
+                    "traffic_source": "recorded: HBM bytes per launch from the rocprofv3 FETCH_SIZE / WRITE_SIZE passes kept in profiles/traffic.json "
+                                      "(probes/profile_r06.sh; counter values scaled by the factors measured on known byte counts in this repository's access "
+                                      "shapes, probes/pmc_calibrate.hip: `traffic_calibration`), not collected in this run", "kernel_ms": float(kern_ms), "kernel_ms_samples": KERNEL_SAMPLES,
+                    "kernel_ms_is": "the HIP-event-bracketed duration of ONE isolated launch (first workgroup in to last workgroup out, plus ~2 us of event overhead), median of "
+                                    "kernel_ms_samples; ms_per_step of the timed region is a THROUGHPUT figure over back-to-back launches - a CU takes the next launch's "
+                                    "workgroup the moment its own retires - and may therefore be smaller (config.launch, config.launch_diagnostics, DESIGN.md section 6)",
+                    "clocks": "sustained: every event-timed figure of this line is taken behind 20 ms of load (bench._event_ms)" if PREHEAT is not None else "cold (PDP_BENCH_NO_PREHEAT=1)",
+                    "algorithmic_flop_per_launch": FLOP_PER_TRAJ * B, "timing_windows": [headline_window], "timed_region_window": timed_window,
+                    "arithmetic_of_the_formulation_run": {"flop_per_launch": FLOP_PER_TRAJ_SCHUR * B,
+                                                          "frac": FLOP_PER_TRAJ_SCHUR * B / (kern_ms * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS,
+                                                          "note": "the kernel solves the Schur-complement form (one m x m system per step, not two n x n "
+                                                                  "inverses): 1.44 MFLOP of unpadded arithmetic per trajectory against the 3.5 MFLOP dense "
+                                                                  "count of the reference formulation that `achieved` prices"},
+                    "hbm": {"achieved": ach_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": ach_gbps / HBM_PEAK_GBPS,
+                            "algorithmic_bytes_per_launch": BYTES_PER_TRAJ * B}}
         res = {
             "metric": "trajectories/sec (fwd+Riccati+PDP grad), quadrotor n=13 T=50",
             "value": value, "unit": "trajectories/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1072,38 +1140,22 @@ def main():
                        "launch_modes": ({"eager_ms_per_step": eager_ms_per_step, "graph_replay_ms_per_step": dt / args.steps * 1e3} if graph is not None else None),
                        "dist_backend": backend if distributed else None, "ranks_share_one_device": bool(same_device and world > 1),
                        "collectives_forced_at_world_size_1": bool(distributed and world == 1)},
-            "roofline": {"bound": "mfma", "kernel": "oc_pdp_fused3_kernel" if os.environ.get("PDP_FUSED_VARIANT", "3") == "3" else "oc_pdp_fused_kernel", "achieved": ach_tflops, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": ach_tflops / FP64_MFMA_PEAK_TFLOPS, "traffic": traffic, "traffic_calibration": traffic_cal, "kernel_resources": kres,
-                         "traffic_collected_at": traffic_at, "traffic_collected_on_these_kernel_sources": traffic_current,
-                         "traffic_source": "recorded: HBM bytes per launch from the rocprofv3 FETCH_SIZE / WRITE_SIZE passes kept in profiles/traffic.json "
-                                           "(probes/profile_r06.sh; counter values scaled by the factors measured on known byte counts in this repository's access "
-                                           "shapes, probes/pmc_calibrate.hip: `traffic_calibration`), not collected in this run", "kernel_ms": float(kern_ms), "kernel_ms_samples": KERNEL_SAMPLES,
-                         "kernel_ms_is": "the HIP-event-bracketed duration of ONE isolated launch (first workgroup in to last workgroup out, plus ~2 us of event overhead), median of "
-                                         "kernel_ms_samples; ms_per_step of the timed region is a THROUGHPUT figure over back-to-back launches - a CU takes the next launch's "
-                                         "workgroup the moment its own retires - and may therefore be smaller (config.launch, config.launch_diagnostics, DESIGN.md section 6)",
-                         "clocks": "sustained: every event-timed figure of this line is taken behind 20 ms of load (bench._event_ms)" if PREHEAT is not None else "cold (PDP_BENCH_NO_PREHEAT=1)",
-                         "algorithmic_flop_per_launch": FLOP_PER_TRAJ * B, "timing_windows": [headline_window], "timed_region_window": timed_window,
-                         "arithmetic_of_the_formulation_run": {"flop_per_launch": FLOP_PER_TRAJ_SCHUR * B,
-                                                               "frac": FLOP_PER_TRAJ_SCHUR * B / (kern_ms * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS,
-                                                               "note": "the kernel solves the Schur-complement form (one m x m system per step, not two n x n "
-                                                                       "inverses): 1.44 MFLOP of unpadded arithmetic per trajectory against the 3.5 MFLOP dense "
-                                                                       "count of the reference formulation that `achieved` prices"},
-                         "hbm": {"achieved": ach_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": ach_gbps / HBM_PEAK_GBPS,
-                                 "algorithmic_bytes_per_launch": BYTES_PER_TRAJ * B}},
             "reference_recorded": {"value": 4.8, "unit": "trajectories/s", "note": "reference IRL iteration incl. IPOPT, author's Mac, BASELINE.md section 2 (context only)"},
         }
+        if roof is not None:
+            res["roofline"] = roof
         if per_rank is not None:
             res["per_rank"] = per_rank
         if scal is not None:
             res["scaling_configs"] = scal
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:                             # the headline line must survive a failure of the side measurements
                 res["cpu_baseline"] = cpu_baseline()
                 res["cpu_baseline_1thread"] = {"value": res["cpu_baseline"].get("one_thread", res["cpu_baseline"]["value"]), "unit": "trajectories/s", "cores": 1,
                                                "kind": "port", "sample": "the same restatement on one thread (like-for-like with the single-threaded reference)"}
             except Exception as ex:
                 res["cpu_baseline"] = {"value": None, "unit": "trajectories/s", "cores": 0, "kind": "port", "sample": "failed: %r" % (ex,)}
-        if world == 1 and not args.no_other_configs and B == BATCH:
+        if args.full and world == 1 and not args.no_other_configs and B == BATCH:
             try:
                 res["other_configs"] = other_configs(torch)
             except Exception as ex:          # the headline line must survive a failure of the side measurements

@@ -100,7 +100,7 @@ try:
     out["collected"] = {"kernel_sources_sha1": codegen.kernel_sources_digest(), "date": time.strftime("%Y-%m-%d"), "by": "probes/profile_r06.sh"}
 except Exception as ex:
     out["collected"] = {"error": repr(ex)}
-out["note"] = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `python bench.py --steps 20 --warmup 5 --no-cpu-baseline "
+out["note"] = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline "
                "--no-scaling-configs` (probes/profile_r06.sh); counters in bytes (rocprofv3 reports KB), mean over all dispatches of a (kernel, grid) pair")
 json.dump(out, open(os.path.join(O, "traffic.json"), "w"), indent=1)
 print(json.dumps(out, indent=1)[:6000])

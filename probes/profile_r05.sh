@@ -9,7 +9,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/prof5
 mkdir -p $O
-BENCH="python bench.py --steps 20 --warmup 5 --no-cpu-baseline"
+BENCH="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline"
 $BENCH > $O/plain.log 2>&1
 grep '^{' $O/plain.log | tail -1 > $O/bench_line_unprofiled.json
 PDP_BENCH_WINDOWS=$O/windows.json rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o p -- $BENCH > $O/stats.log 2>&1
@@ -18,7 +18,7 @@ python probes/rocprof_match.py $O/stats $O/windows.json $O/bench_line_unprofiled
 echo "rocprof_match exit $?" >> $O/rocprof_match.txt
 for f in $(find $O/stats -name 'p_kernel_stats.csv'); do cp $f $O/bench_full_kernel_stats.csv; done
 # ---- the headline alone (the command whose one kernel `roofline.achieved` prices: its average duration in this summary must agree with roofline.kernel_ms)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_headline -o p -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-scaling-configs > $O/stats_headline.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_headline -o p -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-scaling-configs > $O/stats_headline.log 2>&1
 for f in $(find $O/stats_headline -name 'p_kernel_stats.csv'); do cp $f $O/bench_kernel_stats.csv; done
 grep '^{' $O/stats_headline.log | tail -1 > $O/bench_line_headline_under_rocprof.json
 # ---- calibration
@@ -27,7 +27,7 @@ hipcc --offload-arch=gfx950 -O3 -o /tmp/pmc_calibrate probes/pmc_calibrate.hip >
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/calib_fetch -o p -- /tmp/pmc_calibrate 1024 4 > $O/calib_fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/calib_write -o p -- /tmp/pmc_calibrate 1024 4 > $O/calib_write.log 2>&1
 # ---- traffic of the bench kernels
-BENCH2="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-scaling-configs"
+BENCH2="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-scaling-configs"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/fetch -o p -- $BENCH2 > $O/fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/write -o p -- $BENCH2 > $O/write.log 2>&1
 python probes/pmc_traffic_r05.py $O > $O/traffic_summary.txt 2>&1

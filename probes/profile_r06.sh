@@ -10,7 +10,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/prof6
 mkdir -p $O
-BENCH="python bench.py --steps 20 --warmup 5 --no-cpu-baseline"
+BENCH="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline"
 if [ "$1" != "floors-only" ]; then
 $BENCH > $O/plain.log 2>&1
 grep '^{' $O/plain.log | tail -1 > $O/bench_line_unprofiled.json
@@ -19,19 +19,19 @@ grep '^{' $O/stats.log | tail -1 > $O/bench_line_under_rocprof.json
 python probes/rocprof_match.py $O/stats $O/windows.json $O/bench_line_unprofiled.json > $O/rocprof_match.txt 2>&1
 echo "rocprof_match exit $?" >> $O/rocprof_match.txt
 for f in $(find $O/stats -name 'p_kernel_stats.csv'); do cp $f $O/bench_full_kernel_stats.csv; done
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_headline -o p -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-scaling-configs > $O/stats_headline.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_headline -o p -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-scaling-configs > $O/stats_headline.log 2>&1
 for f in $(find $O/stats_headline -name 'p_kernel_stats.csv'); do cp $f $O/bench_kernel_stats_two_streams.csv; done
 grep '^{' $O/stats_headline.log | tail -1 > $O/bench_line_headline_under_rocprof.json
 # the same command with every step on ONE stream: every dispatch of the headline kernel isolated, so that the AVERAGE of the stats summary is the duration of a launch
 # (with the default two step streams a dispatch begins when it reaches the head of its queue, while the previous step still holds the CUs: begin to end it spans two steps)
-PDP_BENCH_ONE_STREAM=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_headline1 -o p -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-scaling-configs > $O/stats_headline1.log 2>&1
+PDP_BENCH_ONE_STREAM=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_headline1 -o p -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-scaling-configs > $O/stats_headline1.log 2>&1
 for f in $(find $O/stats_headline1 -name 'p_kernel_stats.csv'); do cp $f $O/bench_kernel_stats.csv; done
 grep '^{' $O/stats_headline1.log | tail -1 > $O/bench_line_headline_one_stream_under_rocprof.json
 hipcc --offload-arch=gfx950 -O3 -o /tmp/pmc_calibrate probes/pmc_calibrate.hip > $O/calib_build.log 2>&1
 /tmp/pmc_calibrate 1024 4 > $O/calib_truth.txt 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/calib_fetch -o p -- /tmp/pmc_calibrate 1024 4 > $O/calib_fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/calib_write -o p -- /tmp/pmc_calibrate 1024 4 > $O/calib_write.log 2>&1
-BENCH2="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-scaling-configs"
+BENCH2="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-scaling-configs"
 # (counter passes: bytes per launch do not depend on the clocks - without the 200 launches of load bench.py puts in front of every event-timed entry)
 PDP_BENCH_NO_PREHEAT=1 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/fetch -o p -- $BENCH2 > $O/fetch.log 2>&1
 PDP_BENCH_NO_PREHEAT=1 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/write -o p -- $BENCH2 > $O/write.log 2>&1

@@ -29,7 +29,7 @@ def _free_port():
 def _torchrun_bench(world, extra=()):
     env = dict(os.environ, PDP_DIST_BACKEND="gloo", PDP_DIST_SAME_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "5", "--warmup", "2", "--verify-exchange"] + list(extra)
+           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "5", "--warmup", "2", "--full", "--verify-exchange"] + list(extra)
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     try:                                     # (kept for the record and for debugging: pytest shortens long assertion messages)
         os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)

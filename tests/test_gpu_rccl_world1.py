@@ -126,7 +126,7 @@ def test_rccl_collectives_of_parallel_py_at_world_size_1():
 def test_bench_distributed_branch_over_rccl_at_world_size_1():
     """bench.py --gpus 1 with the collectives forced: the line says dist_backend nccl, carries per_rank statistics (gathered THROUGH RCCL) and --verify-exchange's
     bit-for-bit check of the exchanged rows, for the headline and for every scaling_configs entry (their exchanges incl. the ragged one)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2", "--verify-exchange", "--no-cpu-baseline", "--no-other-configs"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2", "--full", "--verify-exchange", "--no-cpu-baseline", "--no-other-configs"]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     try:
         os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
@@ -155,3 +155,20 @@ def test_bench_distributed_branch_over_rccl_at_world_size_1():
         ver = e["verified"]
         assert ver["gathered_rows"] == e["total_batch"] and all(ver["gathered_rows_bit_equal_to_single_process_per_rank"]), (name, ver)
         assert max(ver["allreduce_mean_max_rel_err_per_rank"]) <= 1e-12, (name, ver)
+
+
+def test_plain_bench_distributed_branch_dumps_the_gathered_rows(tmp_path):
+    """bench.py --gpus 1 without --full through the same one-rank RCCL group: the line carries the timed region alone (per_rank ms_per_step, nothing of --full),
+    and --dump-outputs writes the rows the last timed step's all-gather delivered - at one rank, that step's gradient | loss."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, "\n".join(r.stderr.splitlines()[-25:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["config"]["dist_backend"] == "nccl" and res["config"]["collectives_forced_at_world_size_1"] is True and res["steps"] == 10
+    assert list(res["per_rank"]) == ["ms_per_step"] and abs(res["per_rank"]["ms_per_step"][0] - res["ms_per_step"]) <= 1e-12 * res["ms_per_step"]
+    assert not {"roofline", "scaling_configs", "cpu_baseline", "other_configs"} & set(res), sorted(res)
+    rows, grad, loss = (np.load(os.path.join(str(tmp_path), k + ".npy")) for k in ("gathered_rows", "grad", "loss"))
+    assert rows.shape == (1024, 10) and np.array_equal(rows[:, :9], grad) and np.array_equal(rows[:, 9], loss)
