@@ -22,11 +22,11 @@
 // well beyond 16 x 1024 trajectories per GPU, which no BASELINE configuration has; see DESIGN.md section 4.3.
 #pragma once
 #include "pdp_model_kernels.h"
+#include "pdp_wave.h"
 
 namespace pdp {
 
 constexpr int MLP16_W = 16, MLP16_MAXL = 4;
-PDP_DEV int mlp_opaque(int v) { asm volatile("" : "+v"(v)); return v; }
 
 struct Mlp16Layout { int xs, us, zs, ds, misc, blk, total, actw; };
 template <class Mdl>
@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(64) cp_step_mlp16_kernel(int B, int T, pdp_pol
 
     // (computed HERE, from a lane id the optimiser cannot see through: hoisted above the rollout these 16 registers - and the 50 of the pool offsets below - stay live
     // across it and the kernel needs 266 VGPRs, one more than lets two wavefronts share a SIMD)
-    const int ln_ = mlp_opaque(lane);
+    const int ln_ = opaque(lane);
     // per-lane parameter slots q = 0..7 (parameter index lane + 64 q): LDS offsets of the two factors of d cost / d theta_j (delta_k[r] * z_k[c], or 1.0)
     int pr[8], pz[8];
 #pragma unroll
@@ -431,7 +431,7 @@ __global__ void __launch_bounds__(64) cp_step_mlp4t_kernel(int B, int T, pdp_pol
     wave_lds_sync();
 
     // ---------------- adjoint sweep, four trajectories at once
-    const int ln_ = mlp_opaque(lane);                     // (per-lane maps from an opaque lane id: not hoisted above the rollout)
+    const int ln_ = opaque(lane);                         // (per-lane maps from an opaque lane id: not hoisted above the rollout)
     const int j_ = ln_ & 3, rid_ = 4 * ((ln_ >> 2) & 3) + (ln_ >> 4);
     int fo[NX], go[NX], cxo, cuo;
     auto enc = [&](int code) { return code >= 0 ? code : (code == -1 ? NV : NV + 1 + (-2 - code)); };

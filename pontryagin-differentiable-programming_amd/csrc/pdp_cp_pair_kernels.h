@@ -12,7 +12,8 @@
 // MFMA - are the kind that interleave well on one SIMD.  TPW trajectories per workgroup as in pdp_fused3_kernels.h: 4 (waves w and w + 4
 // share a SIMD) once the batch fills the chip, 1 or 2 (the pair on two SIMDs) below.
 #pragma once
-#include "pdp_fused3_kernels.h"
+#include "pdp_model_kernels.h"
+#include "pdp_wave.h"
 
 namespace pdp {
 
@@ -113,7 +114,7 @@ __global__ void __launch_bounds__(128 * TPW) cp_step_poly2_kernel(int B, int T, 
 #pragma unroll
             for (int i = 0; i < NX; ++i) hx[i] = h[i];
         }
-        f3_signal(fl, T + 1);
+        wg_signal(fl, T + 1);
         if (mine && blockIdx.y == 0) {
             if (xo) for (int i = lane; i < (T + 1) * NX; i += 64) xo[(int64_t)b * (T + 1) * NX + i] = xs[i];
             if (uo) for (int i = lane; i < T * NU; i += 64) uo[(int64_t)b * T * NU + i] = us[i];
@@ -138,7 +139,7 @@ __global__ void __launch_bounds__(128 * TPW) cp_step_poly2_kernel(int B, int T, 
         for (int j = 0; j < NT; ++j) { const int cidx = 16 * (tile0 + j) + col; piv[j] = (cidx < p && row0 < M && (cidx % NU) == row0) ? cidx / NU : -1; }
         for (int c = 0; c < nchunk; ++c) {
             const int t0 = c * ch, cnt = min(ch, T - t0);
-            f3_wait_ge(fl, t0 + cnt);                        // acquire: x_t, u_t of the chunk are in the staging
+            wg_wait_ge(fl, t0 + cnt);                        // acquire: x_t, u_t of the chunk are in the staging
             wave_lds_sync();
             if (lane < cnt) {
                 const int t = t0 + lane;
@@ -177,7 +178,7 @@ __global__ void __launch_bounds__(128 * TPW) cp_step_poly2_kernel(int B, int T, 
                 for (int j = 0; j < NT; ++j) X[j] = Xb[j];
             }
         }
-        f3_wait_ge(fl, T + 1);                               // the terminal gradient h_x(x_T)
+        wg_wait_ge(fl, T + 1);                               // the terminal gradient h_x(x_T)
         wave_lds_sync();
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
@@ -262,7 +263,7 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
         const int ch = (T + nchunk - 1) / nchunk;
         for (int c = 0; c < nchunk; ++c) {
             const int t0 = c * ch, cnt = min(ch, T - t0);
-            f3_wait_ge(fl, t0 + cnt);                        // x_t of the chunk's stages are in the staging (x_{t0+cnt-1} was stored by step t0+cnt-2; the counter is past it)
+            wg_wait_ge(fl, t0 + cnt);                        // x_t of the chunk's stages are in the staging (x_{t0+cnt-1} was stored by step t0+cnt-2; the counter is past it)
             wave_lds_sync();
             if (lane < cnt) {
                 const int t = t0 + lane;
@@ -287,7 +288,7 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
                 }
             }
         }
-        f3_wait_ge(fl, T);                                   // x_T
+        wg_wait_ge(fl, T);                                   // x_T
         wave_lds_sync();
         if (lane < NX) { double d = xs[T * NX + lane] - ob[T * NX + lane]; dlT[lane] = d; lsum += d * d; }
         wave_lds_sync();

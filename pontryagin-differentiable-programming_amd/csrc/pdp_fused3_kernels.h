@@ -20,6 +20,7 @@
 // Each trajectory owns a 40 KB slice of the workgroup's 160 KB of LDS.
 #pragma once
 #include "pdp_model_kernels.h"
+#include "pdp_wave.h"
 
 #ifndef PDP_F3_GAIN_AHEAD
 #define PDP_F3_GAIN_AHEAD 3         // forward sweep: the feedback gains of step t + PDP_F3_GAIN_AHEAD are requested during step t (1, 2 or 3; profiles/r04_fused3_attempts.txt)
@@ -68,67 +69,16 @@ __host__ __device__ constexpr bool fused3_ok(int T) {
     return Mdl::NX > 4 && F3::ROWS >= 4 && F3::ROWSF >= 4 && (T + 1) * Mdl::NX + T * Mdl::NU <= 2 * F3::BUF;
 }
 
-typedef unsigned f3_u2 __attribute__((ext_vector_type(2)));
-typedef unsigned f3_u4 __attribute__((ext_vector_type(4)));
-
-// counters in LDS: release / acquire at workgroup scope (LDS and - for the trajectory the runner leaves in global memory - the CU's L1)
-PDP_DEV void f3_signal(int* f, int v) { __hip_atomic_store(f, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
-PDP_DEV void f3_wait_ge(int* f, int v) {
-    while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < v) __builtin_amdgcn_s_sleep(2);
-}
-
-// Gathers over uniform rows: off[r] = slot (in doubles, inside a row) of tile element (lane, r); absent elements read the row's 0.0
-struct Gather3 { int off[4]; };
-template <class CodeFn>
-PDP_DEV void make_gather3(Gather3& g, int lane, int c0, CodeFn code_of /* (row, col) -> code >= 0, -1 (zero) or <= -2 (constant) */) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int code = code_of(tile_row(lane, r), tile_col(lane));
-        g.off[r] = code >= 0 ? code : (code == -1 ? c0 : c0 + 1 + (-2 - code));
-    }
-}
-struct Run3 { unsigned cur[4]; };       // absolute LDS byte addresses of the four elements in the row the run is positioned at
-PDP_DEV Run3 run3_at(const Gather3& g, const double* row) {
-    Run3 r;
-    const unsigned base = lds_addr(row);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) r.cur[k] = base + 8u * (unsigned)g.off[k];
-    return r;
-}
-template <int NR = 4>
-PDP_DEV d4 read3(const Run3& r, unsigned imm) {      // imm: byte distance of the wanted row from the run's row - a literal after unrolling
-    d4 v = zero4();
-#pragma unroll
-    for (int k = 0; k < NR; ++k) v[k] = *(PDP_LDS const double*)(uintptr_t)(r.cur[k] + imm);
-    return v;
-}
-template <int NR = 4>
-PDP_DEV void move3(Run3& r, int bytes) {
-#pragma unroll
-    for (int k = 0; k < NR; ++k) r.cur[k] += (unsigned)bytes;
-}
-
-// tile -> array through range-checked buffer stores: voff[r] = byte offset of element (lane, r) inside one time step's block, or out of range (dropped by the
-// hardware, like every lane of a resource of size 0 = an output that was not asked for): no predicated store blocks in the step loops
-struct F3StoreMap { unsigned voff[4]; };
-PDP_DEV F3StoreMap f3_store_map(int R, int C, int ld, int coff, int lane) {
-    F3StoreMap m;
+// tile -> array through range-checked buffer stores (buf_store, pdp_wave.h): voff[r] = byte offset of element (lane, r) of the R x C block at column coff
+// inside one time step's block (leading dimension ld)
+PDP_DEV BufMap f3_store_map(int R, int C, int ld, int coff, int lane) {
+    BufMap m;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int row = tile_row(lane, r), col = tile_col(lane) - coff;
-        m.voff[r] = (row < R && col >= 0 && col < C) ? 8u * (unsigned)(row * ld + col) : 0x80000000u;
+        m.voff[r] = (row < R && col >= 0 && col < C) ? 8u * (unsigned)(row * ld + col) : BUF_OOB;
     }
     return m;
-}
-template <int NR = 4, class RS>
-PDP_DEV void f3_bstore(RS rs, unsigned soff, const F3StoreMap& m, const d4 v) {
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const double x = v[r];          // (through a scalar copy: see DESIGN.md section 8, finding 5)
-        f3_u2 w;
-        w.x = (unsigned)__double2loint(x); w.y = (unsigned)__double2hiint(x);
-        __builtin_amdgcn_raw_buffer_store_b64(w, rs, m.voff[r], soff, 0);
-    }
 }
 
 // TPW trajectories per workgroup of 2 TPW waves (runner = wave j, evaluator = wave j + TPW).  TPW = 4 (512 threads): the pair shares a SIMD - the layout for
@@ -217,7 +167,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
 #pragma unroll
                 for (int i = 0; i < Mdl::NPC; ++i) par[NP + i] = pc0[i];
             }
-            f3_signal(fl + 0, 1);
+            wg_signal(fl + 0, 1);
         }
         // ---- rollout x+ = f(x, u, theta): scalar recursion executed uniformly by the wave.  u is staged in the (still unused) pool and read one
         // step ahead; x_{t+1} goes straight to the API output from lane 0 - global stores are counted by vmcnt, which nothing in the loop
@@ -238,8 +188,8 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                 for (int i = 0; i < NX; ++i) xb[i] = xc[i];
             }
             wave_lds_sync();
-            const auto rsX = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (int)((T + 1) * NX * 8), 0x00020000);
-            const unsigned xvoff = lane == 0 ? 0u : 0x80000000u;
+            const auto rsX = PDP_BUF_RSRC(xb, (T + 1) * NX * 8);
+            const unsigned xvoff = lane == 0 ? 0u : BUF_OOB;
             double un[NU];
 #pragma unroll
             for (int i = 0; i < NU; ++i) un[i] = us[i];
@@ -260,20 +210,11 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
 #pragma unroll
                     for (int i = 0; i < NX; ++i) { xc[i] = xn[i]; xs[i] = mine ? xn[i] : xs[i]; }
                 }
-                const unsigned vo = lane < nb ? (unsigned)(lane * NX) * 8u : 0x80000000u;
+                const unsigned vo = lane < nb ? (unsigned)(lane * NX) * 8u : BUF_OOB;
                 const unsigned so = (unsigned)((tb_ + 1) * NX) * 8u;
 #pragma unroll
-                for (int i = 0; i + 1 < NX; i += 2) {
-                    f3_u4 w;
-                    w.x = (unsigned)__double2loint(xs[i]); w.y = (unsigned)__double2hiint(xs[i]);
-                    w.z = (unsigned)__double2loint(xs[i + 1]); w.w = (unsigned)__double2hiint(xs[i + 1]);
-                    __builtin_amdgcn_raw_buffer_store_b128(w, rsX, vo + 8u * i, so, 0);
-                }
-                if constexpr (NX & 1) {
-                    f3_u2 w;
-                    w.x = (unsigned)__double2loint(xs[NX - 1]); w.y = (unsigned)__double2hiint(xs[NX - 1]);
-                    __builtin_amdgcn_raw_buffer_store_b64(w, rsX, vo + 8u * (NX - 1), so, 0);
-                }
+                for (int i = 0; i + 1 < NX; i += 2) buf_store_f64x2(rsX, so, vo + 8u * i, xs[i], xs[i + 1]);
+                if constexpr (NX & 1) buf_store_f64(rsX, so, vo + 8u * (NX - 1), xs[NX - 1]);
             }
 #else
             for (int t = 0; t < T; ++t) {
@@ -287,24 +228,15 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                 {
                     const unsigned so = (unsigned)((t + 1) * NX) * 8u;
 #pragma unroll
-                    for (int i = 0; i + 1 < NX; i += 2) {
-                        f3_u4 w;
-                        w.x = (unsigned)__double2loint(xn[i]); w.y = (unsigned)__double2hiint(xn[i]);
-                        w.z = (unsigned)__double2loint(xn[i + 1]); w.w = (unsigned)__double2hiint(xn[i + 1]);
-                        __builtin_amdgcn_raw_buffer_store_b128(w, rsX, xvoff + 8u * i, so, 0);
-                    }
-                    if constexpr (NX & 1) {
-                        f3_u2 w;
-                        w.x = (unsigned)__double2loint(xn[NX - 1]); w.y = (unsigned)__double2hiint(xn[NX - 1]);
-                        __builtin_amdgcn_raw_buffer_store_b64(w, rsX, xvoff + 8u * (NX - 1), so, 0);
-                    }
+                    for (int i = 0; i + 1 < NX; i += 2) buf_store_f64x2(rsX, so, xvoff + 8u * i, xn[i], xn[i + 1]);
+                    if constexpr (NX & 1) buf_store_f64(rsX, so, xvoff + 8u * (NX - 1), xn[NX - 1]);
                 }
             }
 #endif
 #pragma unroll
             for (int i = 0; i < NX; ++i) xTr[i] = xc[i];
         }
-        f3_signal(fl + 0, 2);                                    // release: the trajectory is in memory, the staging area is free
+        wg_signal(fl + 0, 2);                                    // release: the trajectory is in memory, the staging area is free
         F3_STAMP();
 
         // ---- terminal condition: P = hxx(x_T), W = hxe(x_T) - evaluated here, while the evaluator fills the first chunk
@@ -332,60 +264,58 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
             constexpr int NA = F3::NA, NCA = Mdl::PATHA_NCONST;
             auto codeA = [](int mat, int i) { return Mdl::patha_code(mat, i); };
             auto codeB = [](int mat, int i) { int c = Mdl::pathb_code(mat, i); return c >= 0 ? c + NA : (c == -1 ? -1 : c - NCA); };
-            Gather3 gF, gY, gHxx, gHX, gHU, gGr, gHux;
-            make_gather3(gF, lane, F3::CB0, [&](int r, int c) { return (r < NX && c < NX) ? codeA(0, r * NX + c) : -1; });
-            make_gather3(gY, lane, F3::CB0, [&](int r, int c) {
+            RowGather gF, gY, gHxx, gHX, gHU, gGr, gHux;
+            make_row_gather(gF, lane, F3::CB0, [&](int r, int c) { return (r < NX && c < NX) ? codeA(0, r * NX + c) : -1; });
+            make_row_gather(gY, lane, F3::CB0, [&](int r, int c) {
                 return r >= NX ? -1 : (c < M ? codeA(1, r * NU + c) : (c < M + NP ? codeA(2, r * NP + (c - M)) : -1)); });
-            make_gather3(gGr, lane, F3::CB0, [&](int r, int c) { return (r < NX && (c & 3) < NU) ? codeA(1, r * NU + (c & 3)) : -1; });
-            make_gather3(gHux, lane, F3::CB0, [&](int r, int c) { return (r < M && c < NX) ? codeB(1, c * NU + r) : -1; });
-            make_gather3(gHxx, lane, F3::CB0, [&](int r, int c) { return (r < NX && c < NX) ? codeB(0, r * NX + c) : -1; });
-            make_gather3(gHX, lane, F3::CB0, [&](int r, int c) {
+            make_row_gather(gGr, lane, F3::CB0, [&](int r, int c) { return (r < NX && (c & 3) < NU) ? codeA(1, r * NU + (c & 3)) : -1; });
+            make_row_gather(gHux, lane, F3::CB0, [&](int r, int c) { return (r < M && c < NX) ? codeB(1, c * NU + r) : -1; });
+            make_row_gather(gHxx, lane, F3::CB0, [&](int r, int c) { return (r < NX && c < NX) ? codeB(0, r * NX + c) : -1; });
+            make_row_gather(gHX, lane, F3::CB0, [&](int r, int c) {
                 return r >= NX ? -1 : (c < M ? codeB(1, r * NU + c) : (c < M + NP ? codeB(2, r * NP + (c - M)) : -1)); });
-            make_gather3(gHU, lane, F3::CB0, [&](int r, int c) {
+            make_row_gather(gHU, lane, F3::CB0, [&](int r, int c) {
                 return r >= M ? -1 : (c < M ? codeB(3, r * NU + c) : (c < M + NP ? codeB(4, r * NP + (c - M)) : -1)); });
             // gains of a step in the workspace: K [NU x NX] (rows 0..3 of its tile: one register), k [NU x NP], zero sink
             const TileMapBytes mK = make_tile_map_sink(NU, NX, NX, 0, 0, lane, GSZ0 - 1), mIK = make_tile_map_sink(NU, NP, NP, 0, M, lane, NU * NP);
             // Riccati record of a stage (RIC): P_{t+1} [NX x NX] | W_{t+1} [NX x NP] | zero sink
             constexpr int RSZ = oc_riccati_doubles<Mdl>();
-            [[maybe_unused]] const F3StoreMap mRP = f3_store_map(NX, NX, NX, 0, lane), mRW = f3_store_map(NX, NP, NP, M, lane);
-            [[maybe_unused]] const auto rsR = __builtin_amdgcn_make_buffer_rsrc((void*)(RIC && riccati ? riccati + (int64_t)b * T * RSZ : ws_gain), 0,
-                                                                                 RIC && riccati ? (int)((int64_t)T * RSZ * 8) : 0, 0x00020000);
+            [[maybe_unused]] const BufMap mRP = f3_store_map(NX, NX, NX, 0, lane), mRW = f3_store_map(NX, NP, NP, M, lane);
+            [[maybe_unused]] const auto rsR = PDP_BUF_RSRC(RIC && riccati ? riccati + (int64_t)b * T * RSZ : ws_gain, RIC && riccati ? (int64_t)T * RSZ * 8 : 0);
             // packed fp32 prediction record (PredRec, pdp_model_kernels.h)
             [[maybe_unused]] const PredMaps<Mdl> pm(lane);
             [[maybe_unused]] const bool precPW = RIC && prec && !(flags & PDP_OC_RECORD_PRIMAL);      // the P | W part of the record is wanted
-            [[maybe_unused]] const auto rsPR = __builtin_amdgcn_make_buffer_rsrc((void*)(precPW ? (void*)(prec + (int64_t)b * T * PredRec<Mdl>::SIZE) : (void*)ws_gain), 0,
-                                                                                  precPW ? (int)((int64_t)T * PredRec<Mdl>::SIZE * 4) : 0, 0x00020000);
+            [[maybe_unused]] const auto rsPR = PDP_BUF_RSRC(precPW ? (void*)(prec + (int64_t)b * T * PredRec<Mdl>::SIZE) : (void*)ws_gain, precPW ? (int64_t)T * PredRec<Mdl>::SIZE * 4 : 0);
             constexpr int RB = 8 * BS;                           // bytes per row
             for (int g = 0; g < nchunk; ++g) {
                 int t0, cnt;
                 bchunk(g, t0, cnt);
                 const double* pb = pool + (g & 1) * F3::BUF;
                 F3_W0();
-                f3_wait_ge(fl + 2, g + 1);
+                wg_wait_ge(fl + 2, g + 1);
                 F3_W1();
                 int tl = cnt - 1;
                 // the runs sit one row BELOW the step's row: the step reads at +RB, its one-step-ahead requests at +0
                 const double* r0 = pb + (tl - 1) * BS;
-                Run3 rF = run3_at(gF, r0), rY = run3_at(gY, r0), rHxx = run3_at(gHxx, r0), rHX = run3_at(gHX, r0), rHU = run3_at(gHU, r0),
-                     rGr = run3_at(gGr, r0), rHux = run3_at(gHux, r0);
+                RowRun rF = row_run_at(gF, r0), rY = row_run_at(gY, r0), rHxx = row_run_at(gHxx, r0), rHX = row_run_at(gHX, r0), rHU = row_run_at(gHU, r0),
+                     rGr = row_run_at(gGr, r0), rHux = row_run_at(gHux, r0);
                 auto move_all = [&](int bytes) {
-                    move3(rF, bytes); move3(rY, bytes); move3(rHxx, bytes); move3(rHX, bytes); move3<1>(rHU, bytes); move3(rGr, bytes); move3<1>(rHux, bytes);
+                    row_move(rF, bytes); row_move(rY, bytes); row_move(rHxx, bytes); row_move(rHX, bytes); row_move<1>(rHU, bytes); row_move(rGr, bytes); row_move<1>(rHux, bytes);
                 };
                 // F and [G|E] feed the first MFMAs of a step and are requested one step ahead (two register sets in rotation); the Hessian
                 // tiles are accumulator inputs of later MFMAs and are requested at the top of their own step.  Step 0 of a chunk requests
                 // nothing ahead (no LDS read outside the buffer).
-                d4 Fa = read3(rF, RB), Ya = read3(rY, RB), Fb = z, Yb = z;
+                d4 Fa = row_read(rF, RB), Ya = row_read(rY, RB), Fb = z, Yb = z;
                 auto bstep = [&](int tl, unsigned imm, const d4 Fc, const d4 Yc, d4& Fn, d4& Yn) {      // imm: distance of row tl from the runs
                     const int t = t0 + tl;
 #ifdef PDP_PHASE_TIMING_FINE
                     if (blockIdx.x == 0 && threadIdx.x == 0) g_rb_stamp[9] = __builtin_readcyclecounter();
 #endif
-                    d4 Hxx = read3(rHxx, imm), HX2 = read3(rHX, imm), HU2 = read3<1>(rHU, imm), Grep = read3(rGr, imm), Hux = read3<1>(rHux, imm);
-                    if (tl > 0) { Fn = read3(rF, imm - RB); Yn = read3(rY, imm - RB); }
+                    d4 Hxx = row_read(rHxx, imm), HX2 = row_read(rHX, imm), HU2 = row_read<1>(rHU, imm), Grep = row_read(rGr, imm), Hux = row_read<1>(rHux, imm);
+                    if (tl > 0) { Fn = row_read(rF, imm - RB); Yn = row_read(rY, imm - RB); }
                     RiccatiGains gn;
                     d4 P_old;
                     if constexpr (RIC) {          // (uniform branches: a store to an absent output would be dropped by its size-0 resource, but still issued - 8 to 13 per step)
-                        if (riccati) { f3_bstore(rsR, (unsigned)(t * RSZ) * 8u, mRP, P); f3_bstore(rsR, (unsigned)(t * RSZ + NX * NX) * 8u, mRW, W2); }
+                        if (riccati) { buf_store(rsR, (unsigned)(t * RSZ) * 8u, mRP, P); buf_store(rsR, (unsigned)(t * RSZ + NX * NX) * 8u, mRW, W2); }
                         if (precPW) { pred_store(rsPR, (unsigned)(t * PredRec<Mdl>::SIZE) * 4u, pm.P, P); pred_store(rsPR, (unsigned)(t * PredRec<Mdl>::SIZE) * 4u, pm.W, W2); }
                     }
                     ok = riccati_backward<M, false>(P, W2, Fc, Yc, Grep, Hxx, HX2, HU2, Hux[0], scratch, lane, NP, gn, P_old) && ok;
@@ -407,7 +337,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                     bstep(tl - 3, (unsigned)(1 * RB), Fb, Yb, Fa, Ya);
                     move_all(-U * RB);
                 }
-                f3_signal(fl + 3, g + 1);
+                wg_signal(fl + 3, g + 1);
             }
         }
         bool finite = tile_finite(P) && tile_finite(W2);
@@ -419,12 +349,12 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         d4 X2 = z;
         {
             constexpr int DLX = Mdl::FWD_NVAR, DLU = Mdl::FWD_NVAR + NX;      // pool slots of x - x_demo, u - u_demo
-            Gather3 gFT, gGT, gE, gDX, gDU;
-            make_gather3(gFT, lane, F3::CF0, [](int r, int c) { return (r < NX && c < NX) ? Mdl::fwd_code(0, c * NX + r) : -1; });
-            make_gather3(gGT, lane, F3::CF0, [](int r, int c) { return (r < M && c < NX) ? Mdl::fwd_code(1, c * NU + r) : -1; });
-            make_gather3(gE, lane, F3::CF0, [](int r, int c) { return (r < NX && c >= M && c < M + NP) ? Mdl::fwd_code(2, r * NP + (c - M)) : -1; });
-            make_gather3(gDX, lane, F3::CF0, [](int r, int c) { return (r < NX) ? DLX + r : -1; });
-            make_gather3(gDU, lane, F3::CF0, [](int r, int c) { return (r < M) ? DLU + r : -1; });
+            RowGather gFT, gGT, gE, gDX, gDU;
+            make_row_gather(gFT, lane, F3::CF0, [](int r, int c) { return (r < NX && c < NX) ? Mdl::fwd_code(0, c * NX + r) : -1; });
+            make_row_gather(gGT, lane, F3::CF0, [](int r, int c) { return (r < M && c < NX) ? Mdl::fwd_code(1, c * NU + r) : -1; });
+            make_row_gather(gE, lane, F3::CF0, [](int r, int c) { return (r < NX && c >= M && c < M + NP) ? Mdl::fwd_code(2, r * NP + (c - M)) : -1; });
+            make_row_gather(gDX, lane, F3::CF0, [](int r, int c) { return (r < NX) ? DLX + r : -1; });
+            make_row_gather(gDU, lane, F3::CF0, [](int r, int c) { return (r < M) ? DLU + r : -1; });
             // feedback gains of step t are fetched one step ahead (each lane re-reads exactly what it stored); K is read back transposed and
             // replicated in the four column blocks (operand form of the 4-row product U = -K X - k)
             const TileMapBytes mKT = to_bytes_sink(make_rep4_map_transposed(NX, NU, NX, lane), GSZ0 - 1), mIK = make_tile_map_sink(NU, NP, NP, 0, M, lane, NU * NP);
@@ -444,40 +374,37 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
             d4 kn = -load_all<1>(gw + NX * NU, mIK);
 #endif
             // sensitivity outputs of the RIC instantiation: buffer stores, an absent output is a resource of size 0
-            [[maybe_unused]] const F3StoreMap mSX = f3_store_map(NX, NP, NP, M, lane), mSU = f3_store_map(NU, NP, NP, M, lane);
-            [[maybe_unused]] const auto rsSX = __builtin_amdgcn_make_buffer_rsrc((void*)(dxdp ? dxdp + (int64_t)b * (T + 1) * NX * NP : ws_gain), 0,
-                                                                                  dxdp ? (int)((int64_t)(T + 1) * NX * NP * 8) : 0, 0x00020000);
-            [[maybe_unused]] const auto rsSU = __builtin_amdgcn_make_buffer_rsrc((void*)(dudp ? dudp + (int64_t)b * T * NU * NP : ws_gain), 0,
-                                                                                  dudp ? (int)((int64_t)T * NU * NP * 8) : 0, 0x00020000);
+            [[maybe_unused]] const BufMap mSX = f3_store_map(NX, NP, NP, M, lane), mSU = f3_store_map(NU, NP, NP, M, lane);
+            [[maybe_unused]] const auto rsSX = PDP_BUF_RSRC(dxdp ? dxdp + (int64_t)b * (T + 1) * NX * NP : ws_gain, dxdp ? (int64_t)(T + 1) * NX * NP * 8 : 0);
+            [[maybe_unused]] const auto rsSU = PDP_BUF_RSRC(dudp ? dudp + (int64_t)b * T * NU * NP : ws_gain, dudp ? (int64_t)T * NU * NP * 8 : 0);
             [[maybe_unused]] const PredMaps<Mdl> pmf(lane);
-            [[maybe_unused]] const auto rsPRf = __builtin_amdgcn_make_buffer_rsrc((void*)(RIC && prec ? (void*)(prec + (int64_t)b * T * PredRec<Mdl>::SIZE) : (void*)ws_gain), 0,
-                                                                                   RIC && prec ? (int)((int64_t)T * PredRec<Mdl>::SIZE * 4) : 0, 0x00020000);
+            [[maybe_unused]] const auto rsPRf = PDP_BUF_RSRC(RIC && prec ? (void*)(prec + (int64_t)b * T * PredRec<Mdl>::SIZE) : (void*)ws_gain, RIC && prec ? (int64_t)T * PredRec<Mdl>::SIZE * 4 : 0);
             constexpr int RF = 8 * FS;
             static_assert((U & 1) == 0, "the register sets of the unrolled loops alternate: U must be even");
             for (int c = 0; c < nchunkF; ++c) {
                 const int g = nchunk + c, t0 = c * chF, cnt = min(chF, T - t0);
                 const double* pb = pool + (g & 1) * F3::BUF;
                 F3_W0();
-                f3_wait_ge(fl + 2, g + 1);
+                wg_wait_ge(fl + 2, g + 1);
                 F3_W1();
-                Run3 rFT = run3_at(gFT, pb), rGT = run3_at(gGT, pb), rE = run3_at(gE, pb), rDX = run3_at(gDX, pb), rDU = run3_at(gDU, pb);
-                auto move_all = [&](int bytes) { move3(rFT, bytes); move3<1>(rGT, bytes); move3(rE, bytes); move3(rDX, bytes); move3<1>(rDU, bytes); };
+                RowRun rFT = row_run_at(gFT, pb), rGT = row_run_at(gGT, pb), rE = row_run_at(gE, pb), rDX = row_run_at(gDX, pb), rDU = row_run_at(gDU, pb);
+                auto move_all = [&](int bytes) { row_move(rFT, bytes); row_move<1>(rGT, bytes); row_move(rE, bytes); row_move(rDX, bytes); row_move<1>(rDU, bytes); };
                 auto fstep = [&](int tl, unsigned imm, const d4 Xc, d4& Xn, const d4 KTc, const d4 kc, d4& KTnx, d4& knx) {
                     const int t = t0 + tl, tnx = (t + PDP_F3_GAIN_AHEAD < T) ? t + PDP_F3_GAIN_AHEAD : T - 1;
                     KTnx = -load_all<4>(gw + tnx * GSZ, mKT);
                     knx = -load_all<1>(gw + tnx * GSZ + NX * NU, mIK);
-                    d4 FT = read3(rFT, imm);
-                    d4 GT = read3<1>(rGT, imm);
-                    d4 E2 = read3(rE, imm);
-                    d4 DX = read3(rDX, imm);                    // (x_t - xd_t)[row] broadcast over columns
-                    d4 DU = read3<1>(rDU, imm);
+                    d4 FT = row_read(rFT, imm);
+                    d4 GT = row_read<1>(rGT, imm);
+                    d4 E2 = row_read(rE, imm);
+                    d4 DX = row_read(rDX, imm);                    // (x_t - xd_t)[row] broadcast over columns
+                    d4 DU = row_read<1>(rDU, imm);
                     d4 U2;
                     riccati_forward(KTc, kc, FT, GT, E2, Xc, U2, Xn);
                     acc += DX[0] * Xc[0] + DX[1] * Xc[1] + DX[2] * Xc[2] + DX[3] * Xc[3] + DU[0] * U2[0];
                     if constexpr (RIC) {
                         if (dxdp || dudp) {
-                            f3_bstore(rsSX, (unsigned)(t * NX * NP) * 8u, mSX, Xc);
-                            f3_bstore<1>(rsSU, (unsigned)(t * NU * NP) * 8u, mSU, U2);
+                            buf_store(rsSX, (unsigned)(t * NX * NP) * 8u, mSX, Xc);
+                            buf_store<1>(rsSU, (unsigned)(t * NU * NP) * 8u, mSU, U2);
                         }
                         if (prec) {
                             pred_store(rsPRf, (unsigned)(t * PredRec<Mdl>::SIZE) * 4u, pmf.X, Xn);       // X_{t+1}
@@ -520,7 +447,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                 }
                 for (; tl < cnt; ++tl) { fstep(tl, 0u, X2, Xb, KTn, kn, KTb, kb); X2 = Xb; KTn = KTb; kn = kb; move_all(RF); }
 #endif
-                f3_signal(fl + 3, g + 1);
+                wg_signal(fl + 3, g + 1);
             }
         }
         F3_STAMP();
@@ -535,7 +462,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         acc = sum_over_rowgroups(acc);
         lsum = wave_sum(lsum);
         F3_W0();
-        f3_wait_ge(fl + 4, 1);
+        wg_wait_ge(fl + 4, 1);
         F3_W1();
         lsum += misc[4];                                        // the evaluator's share: sum over t < T of |x - xd|^2 + |u - ud|^2
         // PDP_OC_PACKED: grad is [B][NP + 1] with the loss in the last column - the row the data-parallel iteration all-gathers
@@ -559,7 +486,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
 #endif
         __builtin_amdgcn_s_setprio(PDP_F3_EVAL_PRIO);
         F3_W0();
-        f3_wait_ge(fl + 0, 2);                                   // parameters in LDS, trajectory in memory
+        wg_wait_ge(fl + 0, 2);                                   // parameters in LDS, trajectory in memory
         F3_W1();
         F3_STAMP();
         // ---- terminal condition and the constants of both groups
@@ -584,9 +511,9 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         {
             constexpr int NA = F3::NA;
             auto codeA = [](int mat, int i) { return Mdl::patha_code(mat, i); };
-            Gather3 gF, gCX;
-            make_gather3(gF, lane, F3::CB0, [&](int r, int c) { return (r < NX && c < NX) ? codeA(0, r * NX + c) : -1; });
-            make_gather3(gCX, lane, F3::CB0, [&](int r, int c) { return (r < NX && c == 0) ? codeA(3, r) : -1; });
+            RowGather gF, gCX;
+            make_row_gather(gF, lane, F3::CB0, [&](int r, int c) { return (r < NX && c < NX) ? codeA(0, r * NX + c) : -1; });
+            make_row_gather(gCX, lane, F3::CB0, [&](int r, int c) { return (r < NX && c == 0) ? codeA(3, r) : -1; });
             constexpr int RB = 8 * BS;
             for (int g = 0; g < nchunk; ++g) {
                 int t0, cnt;
@@ -594,7 +521,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                 const int bo = (g & 1) * F3::BUF;
                 double* pb = pool + bo;
                 F3_W0();
-                f3_wait_ge(fl + 3, g - 1);                       // the buffer's previous chunk has been consumed
+                wg_wait_ge(fl + 3, g - 1);                       // the buffer's previous chunk has been consumed
                 F3_W1();
                 if (lane < cnt) {
                     PDP_F3_PAR();
@@ -620,13 +547,13 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                     // last instruction).  Same addressing as the runner's loops: runs one row below the step's row, literal row offsets.
                     int tl = cnt - 1;
                     const double* r0 = pb + (tl - 1) * BS;
-                    Run3 cF = run3_at(gF, r0), cC = run3_at(gCX, r0), wL;
+                    RowRun cF = row_run_at(gF, r0), cC = row_run_at(gCX, r0), wL;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) wL.cur[r] = lds_addr(r0) + 8u * (unsigned)(NA + tile_row(lane, r));      // lambda_{t+1} -> row tl (column-0 lanes)
-                    auto move_all = [&](int bytes) { move3(cF, bytes); move3(cC, bytes); move3(wL, bytes); };
-                    d4 Fa = read3(cF, RB), CXa = read3(cC, RB), Fb = z, CXb = z, Lam2 = z;
+                    auto move_all = [&](int bytes) { row_move(cF, bytes); row_move(cC, bytes); row_move(wL, bytes); };
+                    d4 Fa = row_read(cF, RB), CXa = row_read(cC, RB), Fb = z, CXb = z, Lam2 = z;
                     auto cstep = [&](int tl, unsigned imm, const d4 Fc, const d4 CXc, d4& Fn, d4& CXn, const d4 Lin, d4& Lout) {
-                        if (tl > 0) { Fn = read3(cF, imm - RB); CXn = read3(cC, imm - RB); }
+                        if (tl > 0) { Fn = row_read(cF, imm - RB); CXn = row_read(cC, imm - RB); }
                         if (tile_col(lane) == 0) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r) *(PDP_LDS double*)(uintptr_t)(wL.cur[r] + imm) = Lin[r];
@@ -664,7 +591,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                     PackedSink s{row + NA};
                     Mdl::eval_pathb(xc, uc, lc, th, pc, s);
                 }
-                f3_signal(fl + 2, g + 1);
+                wg_signal(fl + 2, g + 1);
             }
         }
         F3_STAMP();
@@ -675,7 +602,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
             for (int c = 0; c < nchunkF; ++c) {
                 const int g = nchunk + c, t0 = c * chF, cnt = min(chF, T - t0), bo = (g & 1) * F3::BUF;
                 F3_W0();
-                f3_wait_ge(fl + 3, g - 1);
+                wg_wait_ge(fl + 3, g - 1);
                 F3_W1();
                 if (lane < cnt) {
                     PDP_F3_PAR();
@@ -692,12 +619,12 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
 #pragma unroll
                     for (int i = 0; i < Mdl::FWD_NCONST; ++i) row[F3::CF0 + 1 + i] = Mdl::fwd_const(i);
                 }
-                f3_signal(fl + 2, g + 1);
+                wg_signal(fl + 2, g + 1);
             }
         }
         lsum = wave_sum(lsum);
         if (lane == 0) misc[4] = lsum;
-        f3_signal(fl + 4, 1);
+        wg_signal(fl + 4, 1);
 #ifdef PDP_PHASE_TIMING
         F3_STAMP();
         if (lane == 0 && b == 0) { long long* o = (long long*)(loss + B) + 16; for (int i = 0; i < 12; ++i) o[i] = ts[i]; o[12] = twait; }

@@ -11,6 +11,7 @@
 // Applies when one parameter tile suffices (p <= 16 - m), n > 4 and a step's matrices fit a slot; everything else takes lqr_solve_kernel.
 #pragma once
 #include "pdp_lqr_kernels.h"
+#include "pdp_wave.h"
 #include <type_traits>
 
 namespace pdp {
@@ -48,12 +49,11 @@ __host__ __device__ inline bool lqs_ok(int n, int m, int p, bool costate) {
 
 // Two kinds of signal.  lqs_signal_lds orders only the wave's LDS traffic in front of the counter (s_waitcnt lgkmcnt(0)): a RELEASE store would also
 // wait for vmcnt(0) - for the streamer that is every load it has in flight for the NEXT steps (the pipeline would collapse to one step in flight),
-// for the runner the HBM round trip of the gains it has just stored.  lqs_signal (release) is used once, where global memory really is handed over.
+// for the runner the HBM round trip of the gains it has just stored.  wg_signal (release, pdp_wave.h) is used once, where global memory really is handed over.
 PDP_DEV void lqs_signal_lds(int* f, int v) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __hip_atomic_store(f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-PDP_DEV void lqs_signal(int* f, int v) { __hip_atomic_store(f, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
 #ifdef PDP_LQS_TIMING      // probe builds (probes/lqr_stream_timing.py): cycles spent waiting at the counters
 #define LQS_TW0() const long long tw0_ = __builtin_readcyclecounter()
 #define LQS_TW1() lqs_waited += __builtin_readcyclecounter() - tw0_
@@ -78,7 +78,6 @@ PDP_DEV void lqs_wait_cached(int* f, int v, int& seen) {
 PDP_DEV void lqs_wait_ge_acquire(int* f, int v) {      // global memory handed over as well
     while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < v) __builtin_amdgcn_s_sleep(1);
 }
-PDP_DEV unsigned lqs_lds_addr(const double* p) { return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const double*)p; }
 
 // offsets (doubles, inside a slot) of the four elements of a tile: from block A (at segA) where its map has the element, else from block B, else the zero
 struct LqsGather { unsigned off[4]; };      // BYTE offsets
@@ -92,11 +91,9 @@ template <int NR = 4>
 PDP_DEV d4 lqs_read(const LqsGather& g, unsigned slot_addr) {
     d4 v = zero4();
 #pragma unroll
-    for (int r = 0; r < NR; ++r) v[r] = *(__attribute__((address_space(3))) const double*)(uintptr_t)(slot_addr + g.off[r]);
+    for (int r = 0; r < NR; ++r) v[r] = *(PDP_LDS const double*)(uintptr_t)(slot_addr + g.off[r]);
     return v;
 }
-
-// (range-checked buffer stores lqs_store / StoreMap / LQS_RSRC: pdp_lqr_kernels.h)
 
 template <int M, int NL>
 __global__ void __launch_bounds__(512) lqr_solve_stream_kernel(pdp_lqr_problem pr, double* __restrict__ Xo, double* __restrict__ Uo,
@@ -118,7 +115,7 @@ __global__ void __launch_bounds__(512) lqr_solve_stream_kernel(pdp_lqr_problem p
     const LqsLayout L = lqs_layout(n, M, p, costate);
     constexpr int LQS_SP = 64 * NL;                          // doubles per ring slot
     const int gsz = n * M + M * p, pwsz = lqs_pw_doubles(n, p), ntri = n * (n + 1) / 2;
-    const unsigned ring_addr = lqs_lds_addr(ring);
+    const unsigned ring_addr = lds_addr(ring);
     const d4 z = zero4();
 #ifdef PDP_LQS_TIMING
     long long lqs_waited = 0;
@@ -218,9 +215,9 @@ __global__ void __launch_bounds__(512) lqr_solve_stream_kernel(pdp_lqr_problem p
                         gHxx = lqs_gather(L.Hxx, mNN, 0, mNone, L.Z), gHX = lqs_gather(L.Hxu, mNM, L.Hxe, mNP, L.Z),
                         gHU = lqs_gather(L.Huu, mMM, L.Hue, mMP, L.Z), gHux = lqs_gather(L.Hxu, mGT, 0, mNone, L.Z);
         constexpr unsigned SB = 8u * LQS_SP;                 // bytes per slot: the slot of a step is a literal offset in the 4-step trips below
-        const StoreMap sNN = lqs_store_map(mPst), sNP = lqs_store_map(mNP), sNM = lqs_store_map(mNM), sMP = lqs_store_map(mMP);
-        const auto rPW = LQS_RSRC(ws_pw ? ws_pw + (int64_t)b * T * pwsz : ws_gain, ws_pw ? (int64_t)T * pwsz * 8 : 0);
-        const auto rG = LQS_RSRC(ws_gain + (int64_t)b * T * gsz, (int64_t)T * gsz * 8);
+        const BufMap sNN = lqs_store_map(mPst), sNP = lqs_store_map(mNP), sNM = lqs_store_map(mNM), sMP = lqs_store_map(mMP);
+        const auto rPW = PDP_BUF_RSRC(ws_pw ? ws_pw + (int64_t)b * T * pwsz : ws_gain, ws_pw ? (int64_t)T * pwsz * 8 : 0);
+        const auto rG = PDP_BUF_RSRC(ws_gain + (int64_t)b * T * gsz, (int64_t)T * gsz * 8);
         lqs_wait_cached(fl + 0, T > 1 ? 2 : 1, seen);
         d4 Fa = lqs_read(gF, ring_addr), Ya = lqs_read(gY, ring_addr), Fb = z, Yb = z;
         auto bstep = [&](int k, unsigned so, unsigned sn, const d4 Fc, const d4 Yc, d4& Fn, d4& Yn) {      // so / sn: byte offsets of this / the next step's slot
@@ -229,15 +226,15 @@ __global__ void __launch_bounds__(512) lqr_solve_stream_kernel(pdp_lqr_problem p
             d4 Hxx = lqs_read(gHxx, sa), HX2 = lqs_read(gHX, sa), HU2 = lqs_read<1>(gHU, sa), Grep = lqs_read(gGr, sa), Hux = lqs_read<1>(gHux, sa);
             if (k + 1 < T) { Fn = lqs_read(gF, ring_addr + sn); Yn = lqs_read(gY, ring_addr + sn); }
             const int t = T - 1 - k;
-            lqs_store(rPW, sNN, (unsigned)(t * pwsz) * 8u, P);               // P_{t+1}, W_{t+1} for the costate output (lambda_{t+1} = P x_{t+1} + W, PDP.py:604)
-            lqs_store(rPW, sNP, (unsigned)(t * pwsz + ntri) * 8u, W0);
+            buf_store(rPW, (unsigned)(t * pwsz) * 8u, sNN, P);               // P_{t+1}, W_{t+1} for the costate output (lambda_{t+1} = P x_{t+1} + W, PDP.py:604)
+            buf_store(rPW, (unsigned)(t * pwsz + ntri) * 8u, sNP, W0);
             RiccatiGains g;
             d4 P_old;
             ok = riccati_backward<M, true, false>(P, W0, Fc, Yc, Grep, Hxx, HX2, HU2, Hux[0], scratch, lane, p0, g, P_old) && ok;
-            lqs_store(rG, sNM, (unsigned)(t * gsz) * 8u, g.KT);
-            lqs_store<1>(rG, sMP, (unsigned)(t * gsz + n * M) * 8u, g.IK);
+            buf_store(rG, (unsigned)(t * gsz) * 8u, sNM, g.KT);
+            buf_store<1>(rG, (unsigned)(t * gsz + n * M) * 8u, sMP, g.IK);
             if (k + 1 < T) lqs_signal_lds(fl + 1, k + 1);   // the slot is free (its tiles are in registers)
-            else lqs_signal(fl + 1, T);                       // last step: RELEASE - the gains / P, W of all steps are handed to the streamer
+            else wg_signal(fl + 1, T);                        // last step: RELEASE - the gains / P, W of all steps are handed to the streamer
         };
         static_assert(LQS_D == 4, "the trips below are written for a ring of four slots");
         int k = 0;
@@ -262,9 +259,9 @@ __global__ void __launch_bounds__(512) lqr_solve_stream_kernel(pdp_lqr_problem p
                         gk = lqs_gather(L.fK + n * M, mMP, 0, mNone, L.fZ), gE = lqs_gather(L.fE, mNP, 0, mNone, L.fZ),
                         gP = lqs_gather(L.fPW, costate ? mPld : mNone, 0, mNone, L.fZ), gW = lqs_gather(L.fPW + ntri, costate ? mNP : mNone, 0, mNone, L.fZ);
         constexpr unsigned SB = 8u * LQS_SP;
-        const StoreMap sNP = lqs_store_map(mNP), sMP = lqs_store_map(mMP);
-        const auto rU = LQS_RSRC(Uo + (int64_t)b * T * M * p, (int64_t)T * M * p * 8), rX = LQS_RSRC(Xo + (int64_t)b * (T + 1) * n * p, (int64_t)(T + 1) * n * p * 8),
-                   rL = LQS_RSRC(Lo ? Lo + (int64_t)b * T * n * p : Uo, Lo ? (int64_t)T * n * p * 8 : 0);
+        const BufMap sNP = lqs_store_map(mNP), sMP = lqs_store_map(mMP);
+        const auto rU = PDP_BUF_RSRC(Uo + (int64_t)b * T * M * p, (int64_t)T * M * p * 8), rX = PDP_BUF_RSRC(Xo + (int64_t)b * (T + 1) * n * p, (int64_t)(T + 1) * n * p * 8),
+                   rL = PDP_BUF_RSRC(Lo ? Lo + (int64_t)b * T * n * p : Uo, Lo ? (int64_t)T * n * p * 8 : 0);
         struct FwdTiles { d4 FT, GT, KT, Pt, k, Et, Wt; };
         auto load_fwd = [&](FwdTiles& w, unsigned so) {
             const unsigned sa = ring_addr + so;
@@ -277,11 +274,11 @@ __global__ void __launch_bounds__(512) lqr_solve_stream_kernel(pdp_lqr_problem p
             d4 U, Xn;
             riccati_forward(KTn, kn, c.FT, c.GT, c.Et, X, U, Xn);
             X = Xn;
-            lqs_store<1>(rU, sMP, (unsigned)(j * M * p) * 8u, U);
-            lqs_store(rX, sNP, (unsigned)((j + 1) * n * p) * 8u, Xn);
+            buf_store<1>(rU, (unsigned)(j * M * p) * 8u, sMP, U);
+            buf_store(rX, (unsigned)((j + 1) * n * p) * 8u, sNP, Xn);
             if (Lo) {
                 d4 Lm = mma_tn(c.Pt, Xn, c.Wt);              // P x+ + W  (P symmetric)
-                lqs_store(rL, sNP, (unsigned)(j * n * p) * 8u, Lm);
+                buf_store(rL, (unsigned)(j * n * p) * 8u, sNP, Lm);
             }
             lqs_signal_lds(fl + 1, T + j + 1);
         };

@@ -17,6 +17,7 @@
 #include "pdp_riccati.h"
 #include "pdp_riccati_small.h"
 #include "pdp_policy.h"
+#include "pdp_wave.h"
 
 namespace pdp {
 
@@ -441,14 +442,8 @@ __global__ void __launch_bounds__(64) oc_ls_select_kernel(int B, int T, int K, c
 // ------------------------------------------------------------------------------------------------------
 // OC: fused forward + costates + aux system (LDS) + Riccati + PDP gradient, one wavefront per trajectory
 // ------------------------------------------------------------------------------------------------------
-typedef unsigned pdp_u2x __attribute__((ext_vector_type(2)));
-typedef unsigned pdp_u4 __attribute__((ext_vector_type(4)));
 struct Gather { int off[4]; int tmul[4]; };
-// running form: cur[r] is the ABSOLUTE LDS byte address of the element for the current step (the base of the dynamic LDS block is a
-// link-time constant the compiler cannot fold: added once here, not as a VALU add in front of every ds_read); the ds_read / ds_write
-// address is the register itself
-#define PDP_LDS __attribute__((address_space(3)))
-PDP_DEV unsigned lds_addr(const double* p) { return (unsigned)(uintptr_t)(PDP_LDS const double*)p; }
+// running form: cur[r] is the ABSOLUTE LDS byte address of the element for the current step (lds_addr, pdp_wave.h)
 struct GatherRun { unsigned cur[4]; int tmul[4]; };
 PDP_DEV GatherRun gather_at(const Gather& g, int tl, const double* lds) {
     GatherRun r;
@@ -504,16 +499,16 @@ struct PredRec {
     static constexpr int X = 0, U = NX * NP, P = U + NU * NP, W = P + NX * (NX + 1) / 2, SIZE = W + NX * NP;
     __host__ __device__ static constexpr int tri(int i, int j) { return i <= j ? i * NX - i * (i - 1) / 2 + (j - i) : j * NX - j * (j - 1) / 2 + (i - j); }
 };
-struct PredMap { unsigned voff[4]; };        // BYTE offsets of a tile's elements inside one stage's record (fp32), or out of range
+// BYTE offsets of a tile's elements inside one stage's record (fp32), or out of range
 template <class Fn>
-PDP_DEV PredMap pred_map(int lane, Fn idx /* (row, col) -> float index inside the record, or -1 */) {
-    PredMap m;
+PDP_DEV BufMap pred_map(int lane, Fn idx /* (row, col) -> float index inside the record, or -1 */) {
+    BufMap m;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { const int k = idx(tile_row(lane, r), tile_col(lane)); m.voff[r] = k >= 0 ? 4u * (unsigned)k : 0x80000000u; }
+    for (int r = 0; r < 4; ++r) { const int k = idx(tile_row(lane, r), tile_col(lane)); m.voff[r] = k >= 0 ? 4u * (unsigned)k : BUF_OOB; }
     return m;
 }
 template <int NR = 4, class RS>
-PDP_DEV void pred_store(RS rs, unsigned soff, const PredMap& m, const d4 v) {
+PDP_DEV void pred_store(RS rs, unsigned soff, const BufMap& m, const d4 v) {
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
         const float x = (float)v[r];
@@ -522,7 +517,7 @@ PDP_DEV void pred_store(RS rs, unsigned soff, const PredMap& m, const d4 v) {
 }
 template <class Mdl>
 struct PredMaps {
-    PredMap X, U, P, W;
+    BufMap X, U, P, W;
     PDP_DEV explicit PredMaps(int lane) {
         using R = PredRec<Mdl>;
         constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP;
@@ -653,8 +648,8 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
             for (int i = 0; i < NX; ++i) xb[i] = xc[i];
         }
         wave_lds_sync();
-        const auto rsX = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (int)((T + 1) * NX * 8), 0x00020000);
-        const unsigned xvoff = lane == 0 ? 0u : 0x80000000u;
+        const auto rsX = PDP_BUF_RSRC(xb, (T + 1) * NX * 8);
+        const unsigned xvoff = lane == 0 ? 0u : BUF_OOB;
         PDP_ACC0();
         double un[NU];                                       // u_{t+1} is read from LDS while step t computes
 #pragma unroll
@@ -673,17 +668,8 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
             {
                 const unsigned so = (unsigned)((t + 1) * NX) * 8u;
 #pragma unroll
-                for (int i = 0; i + 1 < NX; i += 2) {
-                    pdp_u4 w;
-                    w.x = (unsigned)__double2loint(xn[i]); w.y = (unsigned)__double2hiint(xn[i]);
-                    w.z = (unsigned)__double2loint(xn[i + 1]); w.w = (unsigned)__double2hiint(xn[i + 1]);
-                    __builtin_amdgcn_raw_buffer_store_b128(w, rsX, xvoff + 8u * i, so, 0);
-                }
-                if constexpr (NX & 1) {
-                    pdp_u2x w;
-                    w.x = (unsigned)__double2loint(xn[NX - 1]); w.y = (unsigned)__double2hiint(xn[NX - 1]);
-                    __builtin_amdgcn_raw_buffer_store_b64(w, rsX, xvoff + 8u * (NX - 1), so, 0);
-                }
+                for (int i = 0; i + 1 < NX; i += 2) buf_store_f64x2(rsX, so, xvoff + 8u * i, xn[i], xn[i + 1]);
+                if constexpr (NX & 1) buf_store_f64(rsX, so, xvoff + 8u * (NX - 1), xn[NX - 1]);
             }
         }
         PDP_ACC(6);
@@ -751,8 +737,7 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
         // prediction record (RIC, fp32, see PredRec): range-checked buffer stores, a NULL record is a resource of size 0
         [[maybe_unused]] const PredMaps<Mdl> pm(lane);
         [[maybe_unused]] const bool precPW = RIC && prec && !(flags & PDP_OC_RECORD_PRIMAL);      // (PDP_OC_RECORD_PRIMAL: the P | W stores go to a resource of size 0)
-        [[maybe_unused]] const auto rsPR = __builtin_amdgcn_make_buffer_rsrc((void*)(precPW ? (void*)(prec + (int64_t)b * T * PredRec<Mdl>::SIZE) : (void*)ws_gain), 0,
-                                                                              precPW ? (int)((int64_t)T * PredRec<Mdl>::SIZE * 4) : 0, 0x00020000);
+        [[maybe_unused]] const auto rsPR = PDP_BUF_RSRC(precPW ? (void*)(prec + (int64_t)b * T * PredRec<Mdl>::SIZE) : (void*)ws_gain, precPW ? (int64_t)T * PredRec<Mdl>::SIZE * 4 : 0);
         const bool given = (flags & PDP_OC_GIVEN_TRAJ) != 0;
         // costate tile: column 0 holds lambda_{t+1}; terminal value lambda_T = h_x(x_T)
         d4 Lam = z;
@@ -928,8 +913,7 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
         d4 KTn = -load_all<NRT>(gw, mKT);
         d4 kn = -load_all<1>(gw + NX * NU, mIK);
         [[maybe_unused]] const PredMaps<Mdl> pmf(lane);
-        [[maybe_unused]] const auto rsPRf = __builtin_amdgcn_make_buffer_rsrc((void*)(RIC && prec ? (void*)(prec + (int64_t)b * T * PredRec<Mdl>::SIZE) : (void*)ws_gain), 0,
-                                                                               RIC && prec ? (int)((int64_t)T * PredRec<Mdl>::SIZE * 4) : 0, 0x00020000);
+        [[maybe_unused]] const auto rsPRf = PDP_BUF_RSRC(RIC && prec ? (void*)(prec + (int64_t)b * T * PredRec<Mdl>::SIZE) : (void*)ws_gain, RIC && prec ? (int64_t)T * PredRec<Mdl>::SIZE * 4 : 0);
         const int nchunk = (T + CH - 1) / CH;
         const int ch = (T + nchunk - 1) / nchunk;      // chunks of equal length
         for (int c = 0; c < nchunk; ++c) {

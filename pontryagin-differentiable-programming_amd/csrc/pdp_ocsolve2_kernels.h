@@ -41,8 +41,8 @@
 // predicated blocks).
 #pragma once
 #include <type_traits>
-#include "pdp_ocsolve_kernels.h"
-#include "pdp_fused3_kernels.h"
+#include "pdp_model_kernels.h"
+#include "pdp_wave.h"
 
 #ifndef PDP_MS2_DLAM_STAGED
 #define PDP_MS2_DLAM_STAGED 1      // the multiplier step reads its (P, W) records through an LDS copy (dlam_staged) when four trajectories share a CU; 0: straight from the workspace
@@ -64,7 +64,7 @@ struct Ms2Layout {
     static constexpr bool AUG = !SMALL && NX < 16;
     static constexpr int NA = AUG ? NX + 1 : NX;
     static constexpr int NS = Mdl::SOL_NVAR, NF = Mdl::SOLF_NVAR;
-    // backward pool row: [sol entries | defect c_t (NX) | grad_x L (NX) | grad_u L (NU) | 0.0 | constants]  (uniform rows, see Fused3Layout)
+    // backward pool row: [sol entries | defect c_t (NX) | grad_x L (NX) | grad_u L (NU) | 0.0 | constants]  (uniform rows, see Fused3Layout in pdp_fused3_kernels.h)
     static constexpr int C0 = NS, RX = NS + NX, RU = NS + 2 * NX, CB0 = NS + 2 * NX + NU;
     static constexpr int ONEB = CB0 + 1 + Mdl::SOL_NCONST;                 // a 1.0 behind the constants (the homogeneous coordinate of F~)
     static constexpr int BSTRIDE = (ONEB + 1) | 1;
@@ -138,55 +138,15 @@ enum { MS2_ALPHA = 0, MS2_F = 1, MS2_TH = 2, MS2_PR = 3, MS2_DU = 4, MS2_Z = 5, 
        MS2_S_GD = 9, MS2_S_AMIN = 10, MS2_S_THOLD = 11,        // the line search's state while the sweep of a correction runs (slots 12 .. 19: timing builds)
        MS2_G0 = 24 };          // slots 24 .. 31: the guard pass's copy of MS2_F .. MS2_FIN
 
-// Mailbox values come out of LDS in vector registers although every lane reads the same word: said explicitly (v_readfirstlane), or every pointer and
-// branch derived from them would be treated as divergent - 64-bit per-lane addresses for each of the trial pass's ~100 loads, masked branches in the
-// runner's control flow
-PDP_DEV int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-PDP_DEV double uni(double v) { return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v))); }
-// A value the optimiser cannot see through: per-lane maps derived from opaque(lane) INSIDE a sweep are recomputed at every sweep (a few hundred cycles against
-// the sweep's 50 - 100 k) instead of being hoisted out of the iteration loop, where the maps of BOTH sweeps stayed live across each other and pushed the
-// four-trajectories-per-workgroup instantiation (256 registers per wave) into scratch memory (round 3: 21 spilled VGPRs)
-PDP_DEV int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
-// the same for values that live in SCALAR registers (launch constants: T, the workspace pointers).  Row offsets and row pointers derived from the plain T + 1 or from `stp`
-// are invariants of the whole launch: the compiler forms all of them at kernel entry - two scalar registers per row pointer, 2 NX + NU rows per array - and keeps them, i.e.
-// parks them in lanes of vector registers (round 6: FOUR vector registers of the four-trajectory instantiation held ~200 such words, read back ~1000 times).  Derived from an
-// opaque copy inside a pass they are formed there (a few scalar instructions beside thousands of vector ones) and die with it.
-PDP_DEV int sopaque(int v) { asm volatile("" : "+s"(v)); return v; }
-template <class P> PDP_DEV P* sopaque(P* p) { asm volatile("" : "+s"(p)); return p; }
 PDP_DEV int ms2_load(int* f) { return uni(__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)); }
 // wait until *f >= v; false when the partner never gets there (watchdog) or the trajectory has been declared dead
 PDP_DEV bool ms2_wait_ge(int* f, int v, int* ctl) {
     int n = 0;
     while (ms2_load(f) < v) {
         __builtin_amdgcn_s_sleep(PDP_MS2_SLEEP);
-        if (++n > (1 << 22) || ms2_load(ctl + MS2_DEAD) != 0) { f3_signal(ctl + MS2_DEAD, 1); return false; }
+        if (++n > (1 << 22) || ms2_load(ctl + MS2_DEAD) != 0) { wg_signal(ctl + MS2_DEAD, 1); return false; }
     }
     return true;
-}
-
-// tile <-> workspace through buffer instructions: voff[r] = byte offset of element (lane, r) inside a stage's record, or out of range (the
-// hardware drops such lanes of a store and returns 0 for them in a load); the stage offset travels in the scalar offset
-struct BufMap { unsigned voff[4]; };
-constexpr unsigned MS2_OOB = 0x80000000u;
-template <int NR = 4, class RS>
-PDP_DEV void buf_store(RS rs, unsigned soff, const BufMap& m, const d4 v) {
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const double x = v[r];
-        pdp_u2 w;
-        w.x = (unsigned)__double2loint(x); w.y = (unsigned)__double2hiint(x);
-        __builtin_amdgcn_raw_buffer_store_b64(w, rs, m.voff[r], soff, 0);
-    }
-}
-template <int NR = 4, class RS>
-PDP_DEV d4 buf_load(RS rs, unsigned soff, const BufMap& m) {
-    d4 v = zero4();
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const pdp_u2 w = __builtin_amdgcn_raw_buffer_load_b64(rs, m.voff[r], soff, 0);
-        v[r] = __hiloint2double((int)w.y, (int)w.x);
-    }
-    return v;
 }
 
 // Cross-lane traffic of this kernel through DPP modifiers instead of ds_bpermute (round 6): the shuffle form keeps one address register per distance - (lane ^ o) << 2, the
@@ -311,13 +271,8 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
         const double* stpl = sopaque((const double*)stp);
         const bool stepped = a != 0.0, put = dst != cur;
         const double* __restrict__ ps = Pt(cur);
-        const auto rsPd = __builtin_amdgcn_make_buffer_rsrc((void*)Pt(dst), 0, (int)(GRP * 8), 0x00020000);
-        const auto rsRd = __builtin_amdgcn_make_buffer_rsrc((void*)Rs(dst), 0, (int)(GRP * 8), 0x00020000);      // grad_x L (T + 1 nodes; node 0: x_0 is fixed) | grad_u L | c
-        auto bst = [](auto rs, unsigned soff, unsigned voff, double v_) {
-            pdp_u2 w;
-            w.x = (unsigned)__double2loint(v_); w.y = (unsigned)__double2hiint(v_);
-            __builtin_amdgcn_raw_buffer_store_b64(w, rs, voff, soff, 0);
-        };
+        const auto rsPd = PDP_BUF_RSRC(Pt(dst), GRP * 8);
+        const auto rsRd = PDP_BUF_RSRC(Rs(dst), GRP * 8);      // grad_x L (T + 1 nodes; node 0: x_0 is fixed) | grad_u L | c
         a_f = 0.0; a_th = 0.0; a_pr = 0.0; a_du = 0.0; a_z = 0.0; a_l = 0.0; a_lc = 0.0;
         bool fin = true;
         // Groups of 64 lanes OVERLAP by one node (round 6): lane 0 of a later group evaluates node `base` once more - it was lane 63 of the group before - only to hand its f and
@@ -328,7 +283,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
             const bool mine = !(base > 0 && lane == 0);
             const bool node = t <= T && mine, stage = t < T && mine, last = t == T && mine;
             const unsigned o8 = 8u * (unsigned)(t <= T ? t : T);      // (lanes behind the horizon read node T's slots and store nothing)
-            const unsigned on = node ? o8 : MS2_OOB, os = stage ? o8 : MS2_OOB, oc = (node && t > 0) ? o8 - 8u : MS2_OOB;
+            const unsigned on = node ? o8 : BUF_OOB, os = stage ? o8 : BUF_OOB, oc = (node && t > 0) ? o8 - 8u : BUF_OOB;
             double xc[NX], uc[NU], lc[NX], v[NX];
 #pragma unroll
             for (int i = 0; i < NX; ++i) {
@@ -340,12 +295,12 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
             for (int i = 0; i < NU; ++i) { const double ua = sm_ld(ps + OUl + i * TSl, o8), ud = sm_ld(stpl + OUl + i * TSl, o8); uc[i] = stepped ? fma(a, ud, ua) : ua; }
 #pragma unroll
             for (int i = 0; i < NX; ++i) {
-                if constexpr (PRIMAL) { a_z = fmax(a_z, node ? fabs(xc[i]) : 0.0); if (put) bst(rsPd, (unsigned)(i * TSl) * 8u, on, xc[i]); }
-                if constexpr (DUAL) { a_l = fmax(a_l, stage ? fabs(lc[i]) : 0.0); if (put) bst(rsPd, (unsigned)(OLl + i * TSl) * 8u, os, lc[i]); }
+                if constexpr (PRIMAL) { a_z = fmax(a_z, node ? fabs(xc[i]) : 0.0); if (put) buf_store_f64(rsPd, (unsigned)(i * TSl) * 8u, on, xc[i]); }
+                if constexpr (DUAL) { a_l = fmax(a_l, stage ? fabs(lc[i]) : 0.0); if (put) buf_store_f64(rsPd, (unsigned)(OLl + i * TSl) * 8u, os, lc[i]); }
             }
             if constexpr (PRIMAL) {
 #pragma unroll
-                for (int i = 0; i < NU; ++i) { a_z = fmax(a_z, stage ? fabs(uc[i]) : 0.0); if (put) bst(rsPd, (unsigned)(OUl + i * TSl) * 8u, os, uc[i]); }
+                for (int i = 0; i < NU; ++i) { a_z = fmax(a_z, stage ? fabs(uc[i]) : 0.0); if (put) buf_store_f64(rsPd, (unsigned)(OUl + i * TSl) * 8u, os, uc[i]); }
             }
             double nl[NX];
 #pragma unroll
@@ -358,7 +313,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
                 for (int i = 0; i < NX; ++i) {
                     const double nv = ms2_up1(v[i]);                     // the previous node's f(x, u)
                     const double ci = nv - xc[i];                        // defect of stage t - 1
-                    bst(rsRd, (unsigned)(OLl + i * TSl) * 8u, oc, ci);
+                    buf_store_f64(rsRd, (unsigned)(OLl + i * TSl) * 8u, oc, ci);
                     const bool has = node && t > 0;
                     a_th += has ? fabs(ci) : 0.0; a_pr = fmax(a_pr, has ? fabs(ci) : 0.0); a_lc += has ? nl[i] * ci : 0.0;
                     fin = fin && (!has || fabs(ci) <= 1.7e308);
@@ -377,14 +332,14 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
 #pragma unroll
                 for (int i = 0; i < NX; ++i) {
                     const double g = last ? hT[i] - nl[i] : ((stage && t > 0) ? v[i] - nl[i] : 0.0);      // grad_x L of node t (x_0 is fixed: no row)
-                    bst(rsRd, (unsigned)(i * TSl) * 8u, on, g);
+                    buf_store_f64(rsRd, (unsigned)(i * TSl) * 8u, on, g);
                     a_du = fmax(a_du, node ? fabs(g) : 0.0);
                     fin = fin && (!node || fabs(g) <= 1.7e308);
                 }
                 double hu[NU];
                 Mdl::dHu(xc, uc, lc, th, pc, hu);
 #pragma unroll
-                for (int i = 0; i < NU; ++i) { bst(rsRd, (unsigned)(OUl + i * TSl) * 8u, os, hu[i]); a_du = fmax(a_du, stage ? fabs(hu[i]) : 0.0); fin = fin && (!stage || fabs(hu[i]) <= 1.7e308); }
+                for (int i = 0; i < NU; ++i) { buf_store_f64(rsRd, (unsigned)(OUl + i * TSl) * 8u, os, hu[i]); a_du = fmax(a_du, stage ? fabs(hu[i]) : 0.0); fin = fin && (!stage || fabs(hu[i]) <= 1.7e308); }
             }
         }
         if constexpr (PRIMAL) { a_f = ms2_sum(a_f); a_th = ms2_sum(a_th); a_lc = ms2_sum(a_lc); a_pr = ms2_max(a_pr); a_z = ms2_max(a_z); }
@@ -498,7 +453,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
 #pragma unroll
                 for (int i = 0; i < Mdl::NPC; ++i) par[NP + i] = pc0[i];
             }
-            f3_signal(ctl + MS2_PARS, 1);
+            wg_signal(ctl + MS2_PARS, 1);
         }
         // ---- starting point: the caller's (x, u, lambda) [PDP_MS_WARM], or IPOPT's: w0 = 0 (PDP.py:155,166), x_0 = ini_state
         const bool warm = (op.flags & PDP_MS_WARM) != 0;
@@ -752,7 +707,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
         auto issue = [&](int type, double alpha, int cur, int dst) {
             if (lane == 0) { ctl[MS2_TYPE] = type; ctl[MS2_CUR] = cur; ctl[MS2_DST] = dst; ctl[MS2_CSRC] = issue_csrc; res[MS2_ALPHA] = alpha; ctl[MS2_PROD] = 0; ctl[MS2_CONS] = 0; }
             ++seq;
-            f3_signal(ctl + MS2_SEQ, seq);
+            wg_signal(ctl + MS2_SEQ, seq);
         };
         auto wait_slot = [&](int slot_) {        // (the evaluator has the SIMD's issue slots while the runner has nothing to do)
             __builtin_amdgcn_s_setprio(0);
@@ -760,11 +715,11 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
             __builtin_amdgcn_s_setprio(3);
         };
         auto wait_done = [&]() { wait_slot(MS2_DONE); };
-        auto abort_sweep = [&]() { f3_signal(ctl + MS2_ABORT, seq); wait_done(); };
+        auto abort_sweep = [&]() { wg_signal(ctl + MS2_ABORT, seq); wait_done(); };
 
         const int col = tile_col(lane);
-        const auto rsG = __builtin_amdgcn_make_buffer_rsrc((void*)gw, 0, (int)((int64_t)T * GSZ * 8), 0x00020000);
-        const auto rsP = __builtin_amdgcn_make_buffer_rsrc((void*)pw, 0, (int)((int64_t)T * PWSZ * 8), 0x00020000);
+        const auto rsG = PDP_BUF_RSRC(gw, (int64_t)T * GSZ * 8);
+        const auto rsP = PDP_BUF_RSRC(pw, (int64_t)T * PWSZ * 8);
         // residuals of the current iterate, as the evaluator's last accepted pass left them
         double f_cur = 0.0, th_cur = 0.0, inf_pr = 0.0, inf_du = 0.0, zmax = 0.0, lmax = 0.0, lamc = 0.0;
         bool finite = true;
@@ -782,36 +737,36 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
             // gather / store maps of this sweep (from an opaque lane id: see opaque())
             const int ln = opaque(lane);
             auto codeS = [](int mat, int i) { return Mdl::sol_code(mat, i); };       // 0 F, 1 G, 2 Hxx, 3 Hxu, 4 Huu
-            Gather3 gF, gY, gHxx, gHX, gHU, gGr, gHux;
+            RowGather gF, gY, gHxx, gHX, gHU, gGr, gHux;
             if constexpr (AUG) {
                 // homogeneous form: F~ = [F c; 0 1], G~ = [G; 0], Hxx~ = [Hxx rx; rx' 0], Hux~ = [Hxu' | ru], Huu
-                make_gather3(gF, ln, L::CB0, [&](int r, int c) { return (r < NX && c < NX) ? codeS(0, r * NX + c) : ((r < NX && c == NX) ? L::C0 + r : ((r == NX && c == NX) ? L::ONEB : -1)); });
+                make_row_gather(gF, ln, L::CB0, [&](int r, int c) { return (r < NX && c < NX) ? codeS(0, r * NX + c) : ((r < NX && c == NX) ? L::C0 + r : ((r == NX && c == NX) ? L::ONEB : -1)); });
                 // (G~ "by row blocks", one register: lane 16 k + 4 b + i <- G[4 b + k][i]; riccati_backward_aug's second operand form of G)
-                make_gather3(gY, ln, L::CB0, [&](int r, int c) { return (r < 4 && (c & 3) < M && 4 * (c >> 2) + r < NX) ? codeS(1, (4 * (c >> 2) + r) * NU + (c & 3)) : -1; });
-                make_gather3(gHxx, ln, L::CB0, [&](int r, int c) { return (r < NX && c < NX) ? codeS(2, r * NX + c) : ((r < NX && c == NX) ? L::RX + r : ((r == NX && c < NX) ? L::RX + c : -1)); });
-                make_gather3(gHux, ln, L::CB0, [&](int r, int c) { return (r < M && c < NX) ? codeS(3, c * NU + r) : ((r < M && c == NX) ? L::RU + r : -1); });
-                make_gather3(gHU, ln, L::CB0, [&](int r, int c) { return (r < M && c < M) ? codeS(4, r * NU + c) : -1; });
-                make_gather3(gHX, ln, L::CB0, [&](int r, int c) { return -1; });
+                make_row_gather(gY, ln, L::CB0, [&](int r, int c) { return (r < 4 && (c & 3) < M && 4 * (c >> 2) + r < NX) ? codeS(1, (4 * (c >> 2) + r) * NU + (c & 3)) : -1; });
+                make_row_gather(gHxx, ln, L::CB0, [&](int r, int c) { return (r < NX && c < NX) ? codeS(2, r * NX + c) : ((r < NX && c == NX) ? L::RX + r : ((r == NX && c < NX) ? L::RX + c : -1)); });
+                make_row_gather(gHux, ln, L::CB0, [&](int r, int c) { return (r < M && c < NX) ? codeS(3, c * NU + r) : ((r < M && c == NX) ? L::RU + r : -1); });
+                make_row_gather(gHU, ln, L::CB0, [&](int r, int c) { return (r < M && c < M) ? codeS(4, r * NU + c) : -1; });
+                make_row_gather(gHX, ln, L::CB0, [&](int r, int c) { return -1; });
             } else {
-            make_gather3(gF, ln, L::CB0, [&](int r, int c) { return SMALL ? ((r < NX && (c & 3) < NX) ? codeS(0, r * NX + (c & 3)) : -1)
+            make_row_gather(gF, ln, L::CB0, [&](int r, int c) { return SMALL ? ((r < NX && (c & 3) < NX) ? codeS(0, r * NX + (c & 3)) : -1)
                                                                             : ((r < NX && c < NX) ? codeS(0, r * NX + c) : -1); });
-            make_gather3(gY, ln, L::CB0, [&](int r, int c) { return r >= NX ? -1 : (c < M ? codeS(1, r * NU + c) : (c == M ? L::C0 + r : -1)); });
-            make_gather3(gHux, ln, L::CB0, [&](int r, int c) { return SMALL ? ((r < M && (c & 3) < NX) ? codeS(3, (c & 3) * NU + r) : -1)
+            make_row_gather(gY, ln, L::CB0, [&](int r, int c) { return r >= NX ? -1 : (c < M ? codeS(1, r * NU + c) : (c == M ? L::C0 + r : -1)); });
+            make_row_gather(gHux, ln, L::CB0, [&](int r, int c) { return SMALL ? ((r < M && (c & 3) < NX) ? codeS(3, (c & 3) * NU + r) : -1)
                                                                               : ((r < M && c < NX) ? codeS(3, c * NU + r) : -1); });
-            make_gather3(gHxx, ln, L::CB0, [&](int r, int c) { return SMALL ? ((r < NX && (c & 3) < NX) ? codeS(2, r * NX + (c & 3)) : -1)
+            make_row_gather(gHxx, ln, L::CB0, [&](int r, int c) { return SMALL ? ((r < NX && (c & 3) < NX) ? codeS(2, r * NX + (c & 3)) : -1)
                                                                               : ((r < NX && c < NX) ? codeS(2, r * NX + c) : -1); });
-            make_gather3(gHX, ln, L::CB0, [&](int r, int c) { return r >= NX ? -1 : (c < M ? codeS(3, r * NU + c) : (c == M ? L::RX + r : -1)); });
-            make_gather3(gHU, ln, L::CB0, [&](int r, int c) { return r >= M ? -1 : (c < M ? codeS(4, r * NU + c) : (c == M ? L::RU + r : -1)); });
+            make_row_gather(gHX, ln, L::CB0, [&](int r, int c) { return r >= NX ? -1 : (c < M ? codeS(3, r * NU + c) : (c == M ? L::RX + r : -1)); });
+            make_row_gather(gHU, ln, L::CB0, [&](int r, int c) { return r >= M ? -1 : (c < M ? codeS(4, r * NU + c) : (c == M ? L::RU + r : -1)); });
             }
-            make_gather3(gGr, ln, L::CB0, [&](int r, int c) { return (r < NX && (c & 3) < NU) ? codeS(1, r * NU + (c & 3)) : -1; });
+            make_row_gather(gGr, ln, L::CB0, [&](int r, int c) { return (r < NX && (c & 3) < NU) ? codeS(1, r * NU + (c & 3)) : -1; });
             BufMap mK, mIK, mP, mW;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = tile_row(ln, r), colb = tile_col(ln);
-                mK.voff[r] = (row < NU && colb < NA) ? 8u * (unsigned)L::gK(row, colb) : MS2_OOB;                           // K [NU x NX] (rep form: first column block) / K~ [NU x NA]
-                mIK.voff[r] = (row < NU && colb == M) ? 8u * (unsigned)(NX * NU + row) : MS2_OOB;                          // k behind K (not in the homogeneous form)
-                mP.voff[r] = (row < NA && colb < NA && (SMALL || row <= colb)) ? 8u * (unsigned)L::pk(row, colb) : MS2_OOB;   // P_{t+1}: full / upper triangle (of P~)
-                mW.voff[r] = (row < NX && colb == M) ? 8u * (unsigned)(PSZ + row) : MS2_OOB;
+                mK.voff[r] = (row < NU && colb < NA) ? 8u * (unsigned)L::gK(row, colb) : BUF_OOB;                           // K [NU x NX] (rep form: first column block) / K~ [NU x NA]
+                mIK.voff[r] = (row < NU && colb == M) ? 8u * (unsigned)(NX * NU + row) : BUF_OOB;                          // k behind K (not in the homogeneous form)
+                mP.voff[r] = (row < NA && colb < NA && (SMALL || row <= colb)) ? 8u * (unsigned)L::pk(row, colb) : BUF_OOB;   // P_{t+1}: full / upper triangle (of P~)
+                mW.voff[r] = (row < NX && colb == M) ? 8u * (unsigned)(PSZ + row) : BUF_OOB;
             }
             // per-lane tile masks: diagonal of the n x n / m x m blocks
             d4 dgN, dgM0 = z;
@@ -851,18 +806,18 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
                 }
                 int tl = cnt - 1;
                 const double* r0 = pb + (tl - 1) * BS;      // the runs sit one row BELOW the step's row: the step reads at +RB, its one-step-ahead requests at +0
-                Run3 rF = run3_at(gF, r0), rY = run3_at(gY, r0), rHxx = run3_at(gHxx, r0), rHX = run3_at(gHX, r0), rHU = run3_at(gHU, r0),
-                     rGr = run3_at(gGr, r0), rHux = run3_at(gHux, r0);
+                RowRun rF = row_run_at(gF, r0), rY = row_run_at(gY, r0), rHxx = row_run_at(gHxx, r0), rHX = row_run_at(gHX, r0), rHU = row_run_at(gHU, r0),
+                     rGr = row_run_at(gGr, r0), rHux = row_run_at(gHux, r0);
                 constexpr int NRY = AUG ? 1 : NRT;              // (homogeneous form: G by row blocks, one register)
                 auto move_all = [&](int bytes) {
-                    move3<NRT>(rF, bytes); move3<NRY>(rY, bytes); move3<NRT>(rHxx, bytes); move3<NRT>(rHX, bytes); move3<1>(rHU, bytes); move3<NRT>(rGr, bytes); move3<1>(rHux, bytes);
+                    row_move<NRT>(rF, bytes); row_move<NRY>(rY, bytes); row_move<NRT>(rHxx, bytes); row_move<NRT>(rHX, bytes); row_move<1>(rHU, bytes); row_move<NRT>(rGr, bytes); row_move<1>(rHux, bytes);
                 };
-                d4 Fa = read3<NRT>(rF, RB), Ya = read3<NRY>(rY, RB), Fb = z, Yb = z;
+                d4 Fa = row_read<NRT>(rF, RB), Ya = row_read<NRY>(rY, RB), Fb = z, Yb = z;
                 auto bstep = [&](int tl, unsigned imm, const d4 Fc, const d4 Yc, d4& Fn, d4& Yn) {
                     const int t = t0 + tl;
-                    d4 Hxx = read3<NRT>(rHxx, imm), HX2 = z, HU2 = read3<1>(rHU, imm), Grep = read3<NRT>(rGr, imm), Hux = read3<1>(rHux, imm);
-                    if constexpr (!AUG) HX2 = read3<NRT>(rHX, imm);
-                    if (tl > 0) { Fn = read3<NRT>(rF, imm - RB); Yn = read3<NRY>(rY, imm - RB); }
+                    d4 Hxx = row_read<NRT>(rHxx, imm), HX2 = z, HU2 = row_read<1>(rHU, imm), Grep = row_read<NRT>(rGr, imm), Hux = row_read<1>(rHux, imm);
+                    if constexpr (!AUG) HX2 = row_read<NRT>(rHX, imm);
+                    if (tl > 0) { Fn = row_read<NRT>(rF, imm - RB); Yn = row_read<NRY>(rY, imm - RB); }
                     d4 Ys = Yc, Fs = Fc;
                     double Hux0 = Hux[0];
                     if (scaled) {
@@ -921,7 +876,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
                     if (pdall) bstep(tl - 3, (unsigned)((U - 3) * RB), Fb, Yb, Fa, Ya);
                     move_all(-U * RB);
                 }
-                if (pdall) f3_signal(ctl + MS2_CONS, g + 1);
+                if (pdall) wg_signal(ctl + MS2_CONS, g + 1);
                 MS2_T1(1);
             }
             pdall = pdall && ok && !dead;
@@ -937,27 +892,27 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = tile_row(ln, r), colf = tile_col(ln);
-                mIK.voff[r] = (row < NU && colf == M) ? 8u * (unsigned)(NX * NU + row) : MS2_OOB;                           // k behind K (not in the homogeneous form)
-                mKT.voff[r] = (row < NA && (colf & 3) < NU) ? 8u * (unsigned)L::gK(colf & 3, row) : MS2_OOB;                // K (K~) read back transposed, replicated in the column blocks
-                mPld.voff[r] = (AUG && row < NA && colf < NA) ? 8u * (unsigned)L::pk(row, colf) : MS2_OOB;                   // P~ read back as a full tile from its upper triangle
+                mIK.voff[r] = (row < NU && colf == M) ? 8u * (unsigned)(NX * NU + row) : BUF_OOB;                           // k behind K (not in the homogeneous form)
+                mKT.voff[r] = (row < NA && (colf & 3) < NU) ? 8u * (unsigned)L::gK(colf & 3, row) : BUF_OOB;                // K (K~) read back transposed, replicated in the column blocks
+                mPld.voff[r] = (AUG && row < NA && colf < NA) ? 8u * (unsigned)L::pk(row, colf) : BUF_OOB;                   // P~ read back as a full tile from its upper triangle
             }
-            Gather3 gFT, gGT, gE, gRX, gRU;
-            make_gather3(gFT, ln, L::CF0, [](int r, int c) { return SMALL ? ((r < NX && (c & 3) < NX) ? Mdl::solf_code(0, (c & 3) * NX + r) : -1)
+            RowGather gFT, gGT, gE, gRX, gRU;
+            make_row_gather(gFT, ln, L::CF0, [](int r, int c) { return SMALL ? ((r < NX && (c & 3) < NX) ? Mdl::solf_code(0, (c & 3) * NX + r) : -1)
                                                                           : ((r < NX && c < NX) ? Mdl::solf_code(0, c * NX + r)
                                                                              : (AUG && r == NX && c < NX ? L::FC0 + c : (AUG && r == NX && c == NX ? L::ONEF : -1))); });      // F~' = [F' 0; c' 1]
-            make_gather3(gGT, ln, L::CF0, [](int r, int c) { return SMALL ? ((r < M && (c & 3) < NX) ? Mdl::solf_code(1, (c & 3) * NU + r) : -1)
+            make_row_gather(gGT, ln, L::CF0, [](int r, int c) { return SMALL ? ((r < M && (c & 3) < NX) ? Mdl::solf_code(1, (c & 3) * NU + r) : -1)
                                                                           : ((r < M && c < NX) ? Mdl::solf_code(1, c * NU + r) : -1); });
-            make_gather3(gE, ln, L::CF0, [](int r, int c) { return (r < NX && c == M) ? L::FC0 + r : -1; });
-            make_gather3(gRX, ln, L::CF0, [](int r, int c) { return (r < NX && c == M) ? L::FRX + r : -1; });
-            make_gather3(gRU, ln, L::CF0, [](int r, int c) { return (r < M && c == M) ? L::FRU + r : -1; });
+            make_row_gather(gE, ln, L::CF0, [](int r, int c) { return (r < NX && c == M) ? L::FC0 + r : -1; });
+            make_row_gather(gRX, ln, L::CF0, [](int r, int c) { return (r < NX && c == M) ? L::FRX + r : -1; });
+            make_row_gather(gRU, ln, L::CF0, [](int r, int c) { return (r < M && c == M) ? L::FRU + r : -1; });
             BufMap mDX, mDU;                                 // dx_{t+1} / du_t: column M of the tile, row i to [i TS + stage]
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = tile_row(lane, r);
-                mDX.voff[r] = (col == M && row < NX) ? 8u * (unsigned)(row * TS) : MS2_OOB;
-                mDU.voff[r] = (col == M && row < NU) ? 8u * (unsigned)(OU + row * TS) : MS2_OOB;
+                mDX.voff[r] = (col == M && row < NX) ? 8u * (unsigned)(row * TS) : BUF_OOB;
+                mDU.voff[r] = (col == M && row < NU) ? 8u * (unsigned)(OU + row * TS) : BUF_OOB;
             }
-            const auto rsD = __builtin_amdgcn_make_buffer_rsrc((void*)stp, 0, (int)(GRP * 8), 0x00020000);
+            const auto rsD = PDP_BUF_RSRC(stp, GRP * 8);
             // feedback gains of stage t are requested two steps ahead (three register sets in rotation)
             struct Gn { d4 KT, k, Pt; };                     // Pt (homogeneous form): P~_{t+1} as a full tile, for the multiplier step below
             // (loaded as stored, +K and +k: a negation right behind the load would make the step wait for the loads it has just issued; the sign is
@@ -992,7 +947,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
             }
             BufMap mDL;                                      // dlam_t: row 0 of the four-row product, entry c to [OL + c TS + t]
 #pragma unroll
-            for (int r = 0; r < 4; ++r) mDL.voff[r] = (r == 0 && lane < NX) ? 8u * (unsigned)(OL + lane * TS) : MS2_OOB;
+            for (int r = 0; r < 4; ++r) mDL.voff[r] = (r == 0 && lane < NX) ? 8u * (unsigned)(OL + lane * TS) : BUF_OOB;
             double acc = 0.0;
             const bool scaledE = hs != 1.0;
             constexpr int RF = 8 * FS;
@@ -1005,17 +960,17 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
                 MS2_T0();
                 if (!ms2_wait_ge(ctl + MS2_PROD, g + 1, ctl)) { dead = true; break; }
                 MS2_T1(2);
-                Run3 rFT = run3_at(gFT, pb), rGT = run3_at(gGT, pb), rE = run3_at(gE, pb), rRX = run3_at(gRX, pb), rRU = run3_at(gRU, pb);
-                auto move_all = [&](int bytes) { move3<NRT>(rFT, bytes); move3<1>(rGT, bytes); move3<NRT>(rE, bytes); move3<NRT>(rRX, bytes); move3<1>(rRU, bytes); };
+                RowRun rFT = row_run_at(gFT, pb), rGT = row_run_at(gGT, pb), rE = row_run_at(gE, pb), rRX = row_run_at(gRX, pb), rRU = row_run_at(gRU, pb);
+                auto move_all = [&](int bytes) { row_move<NRT>(rFT, bytes); row_move<1>(rGT, bytes); row_move<NRT>(rE, bytes); row_move<NRT>(rRX, bytes); row_move<1>(rRU, bytes); };
                 auto fstep = [&](int tl, unsigned imm, const d4 Xc, d4& Xn, Gn& cur, Gn& fill) {
                     const int t = t0 + tl;
                     if constexpr (!AHEAD3) fill = ldg(t + 2);
-                    d4 FT = read3<NRT>(rFT, imm);
-                    d4 GT = read3<1>(rGT, imm);
+                    d4 FT = row_read<NRT>(rFT, imm);
+                    d4 GT = row_read<1>(rGT, imm);
                     d4 E2 = z;
-                    if constexpr (!AUG) E2 = read3<NRT>(rE, imm);
-                    d4 RXn = read3<NRT>(rRX, imm);
-                    d4 RUc = read3<1>(rRU, imm);
+                    if constexpr (!AUG) E2 = row_read<NRT>(rE, imm);
+                    d4 RXn = row_read<NRT>(rRX, imm);
+                    d4 RUc = row_read<1>(rRU, imm);
                     if (scaledE) {
                         if constexpr (AUG) {                // the defect sits in row NX of F~'
 #pragma unroll
@@ -1056,7 +1011,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
                     move_all(3 * RF);
                 }
                 for (; tl < cnt; ++tl) { fstep(tl, 0u, X2, Xb, A, Cn); X2 = Xb; const Gn nx = A; A = Bn; Bn = Cn; Cn = nx; move_all(RF); }
-                f3_signal(ctl + MS2_CONS, g + 1);       // release: dx, du of the chunk are in memory
+                wg_signal(ctl + MS2_CONS, g + 1);       // release: dx, du of the chunk are in memory
                 MS2_T1(3);
             }
             return ms2_sum(acc) + lamc;
@@ -1290,7 +1245,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
                 if constexpr (SPLIT) {
                     trial_pass(PartPrimal{}, a_try, cur, cur ^ 1); // this wave's half: (theta, phi) of the trial point - all the filter asks for
                     fin_p = fin_all;
-                    f3_signal(ctl + MS2_PDONE, seq);               // release: trial (x, u) and defects are in memory
+                    wg_signal(ctl + MS2_PDONE, seq);               // release: trial (x, u) and defects are in memory
                     ft = a_f; tht = a_th;
                 } else {
                     wait_slot(MS2_TDONE);
@@ -1494,7 +1449,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
             wave_lds_sync();
             if (lane == 0) { for (int k_ = 0; k_ < 8; ++k_) res[MS2_G0 + k_] = res[MS2_F + k_]; }
             __threadfence_block();
-            f3_signal(ctl + MS2_GDONE, 1);
+            wg_signal(ctl + MS2_GDONE, 1);
         }
 #ifdef PDP_MS_TIMING      // cumulative cycles of the evaluator: trial passes | updates | backward chunk evaluations | forward chunk evaluations | dlam | terminal | waits inside a sweep | number of trial passes
         long long et[8] = {0, 0, 0, 0, 0, 0, 0, 0}, et0 = 0;
@@ -1646,7 +1601,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
                 et[7] += 1;
                 if (lane == 0) for (int k_ = 0; k_ < 8; ++k_) res[12 + k_] = (double)et[k_];
 #endif
-                f3_signal(ctl + MS2_TDONE, last);
+                wg_signal(ctl + MS2_TDONE, last);
                 // the sweep below reads the trial (x, u) and the defects the runner's half of the pass writes
                 if (shared && !ms2_wait_ge(ctl + MS2_PDONE, last, ctl)) break;
             }
@@ -1676,7 +1631,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
                     if (g >= 2) {
                         bool freed = false;
                         int n = 0;
-                        while (!(freed = ms2_load(ctl + MS2_CONS) >= g - 1) && !stop()) { __builtin_amdgcn_s_sleep(PDP_MS2_SLEEP); if (++n > (1 << 22)) { f3_signal(ctl + MS2_DEAD, 1); dead = true; } }
+                        while (!(freed = ms2_load(ctl + MS2_CONS) >= g - 1) && !stop()) { __builtin_amdgcn_s_sleep(PDP_MS2_SLEEP); if (++n > (1 << 22)) { wg_signal(ctl + MS2_DEAD, 1); dead = true; } }
                         if (!freed) break;
                     }
                     MS2_E1(6);
@@ -1704,7 +1659,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
 #pragma unroll
                         for (int i = 0; i < Mdl::SOL_NCONST; ++i) row[L::CB0 + 1 + i] = Mdl::sol_const(i);
                     }
-                    f3_signal(ctl + MS2_PROD, g + 1);
+                    wg_signal(ctl + MS2_PROD, g + 1);
                     MS2_E1(2);
                 }
                 // forward chunks: F', G', the defect and the gradients the directional derivative needs; behind each consumed chunk the multiplier step
@@ -1715,7 +1670,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
                     if (g >= 2) {
                         bool freed = false;
                         int n = 0;
-                        while (!(freed = ms2_load(ctl + MS2_CONS) >= g - 1) && !stop()) { __builtin_amdgcn_s_sleep(PDP_MS2_SLEEP); if (++n > (1 << 22)) { f3_signal(ctl + MS2_DEAD, 1); dead = true; } }
+                        while (!(freed = ms2_load(ctl + MS2_CONS) >= g - 1) && !stop()) { __builtin_amdgcn_s_sleep(PDP_MS2_SLEEP); if (++n > (1 << 22)) { wg_signal(ctl + MS2_DEAD, 1); dead = true; } }
                         if (!freed) break;
                     }
                     MS2_E1(6);
@@ -1742,12 +1697,12 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
 #pragma unroll
                         for (int i = 0; i < Mdl::SOLF_NCONST; ++i) row[L::CF0 + 1 + i] = Mdl::solf_const(i);
                     }
-                    f3_signal(ctl + MS2_PROD, g + 1);
+                    wg_signal(ctl + MS2_PROD, g + 1);
                     MS2_E1(3);
                     if (c >= 1) {       // the runner has left chunk c - 1 (it could not start chunk c before the signal above): its dx are in memory
                         bool got = false;
                         int n = 0;
-                        while (!(got = ms2_load(ctl + MS2_CONS) >= g) && !stop()) { __builtin_amdgcn_s_sleep(PDP_MS2_SLEEP); if (++n > (1 << 22)) { f3_signal(ctl + MS2_DEAD, 1); dead = true; } }
+                        while (!(got = ms2_load(ctl + MS2_CONS) >= g) && !stop()) { __builtin_amdgcn_s_sleep(PDP_MS2_SLEEP); if (++n > (1 << 22)) { wg_signal(ctl + MS2_DEAD, 1); dead = true; } }
                         if (!got) break;
                         MS2_E1(6);
                         // (the consumed chunk's buffer is free until chunk c + 1 is evaluated)
@@ -1762,7 +1717,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
                 if (!stop()) {
                     bool got = false;
                     int n = 0;
-                    while (!(got = ms2_load(ctl + MS2_CONS) >= nchunk + nchunkF) && !stop()) { __builtin_amdgcn_s_sleep(PDP_MS2_SLEEP); if (++n > (1 << 22)) { f3_signal(ctl + MS2_DEAD, 1); dead = true; } }
+                    while (!(got = ms2_load(ctl + MS2_CONS) >= nchunk + nchunkF) && !stop()) { __builtin_amdgcn_s_sleep(PDP_MS2_SLEEP); if (++n > (1 << 22)) { wg_signal(ctl + MS2_DEAD, 1); dead = true; } }
                     MS2_E1(6);
                     if (got) {          // the last chunk: both pool buffers are free - its records in ONE block, one trip to memory
                         int tp, cp_;
@@ -1779,7 +1734,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_solve_ms2_kernel(int B, int T, p
 #ifdef PDP_MS_TIMING
             if (lane == 0) for (int k_ = 0; k_ < 8; ++k_) res[12 + k_] = (double)et[k_];
 #endif
-            f3_signal(ctl + MS2_DONE, last);
+            wg_signal(ctl + MS2_DONE, last);
         }
     }
 #undef PDP_MS2_PAR

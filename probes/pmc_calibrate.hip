@@ -4,7 +4,7 @@
 //
 //   read16      16 B / lane global_load_dwordx4, streaming                    (the guide's calibrated case: the control)
 //   read8        8 B / lane global_load_dwordx2, streaming                    (how every kernel of csrc/ reads its inputs and matrices)
-//   write8       8 B / lane range-checked raw buffer store, streaming          (how the fused kernels write x, lambda, gains, records: LQS_RSRC / rsX)
+//   write8       8 B / lane range-checked raw buffer store, streaming          (how the fused kernels write x, lambda, gains, records: buf_store, csrc/pdp_wave.h)
 //   copy8_lds    8 B / lane load -> LDS -> 8 B / lane buffer store             (the streamer wave of lqr_solve_stream_kernel, the chunk hand-over of the solver)
 //   rows712      one wave per "trajectory": 50 rows of 712 B written, then read back 3 rows ahead by the same wave (the gain scratch of oc_pdp_fused3_kernel:
 //                712 B per stage, written by the backward sweep, re-read by the forward sweep)  - total bytes as given on the command line
