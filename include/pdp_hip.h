@@ -291,6 +291,15 @@ int pdp_oc_solve_ms_batched(int B, int T, const double* x0, const double* theta,
 #define PDP_OC_PACKED 2 /* grad is [B][p + 1]: gradient and, in the last column, the loss (the row the multi-GPU iteration all-gathers) */
 #define PDP_OC_RECORD_PRIMAL 4 /* pdp_oc_pdp_grad_sens_batched: only the X | U part of sens->predict_record is written (same stride; the P | W part is left untouched) -
                                   the record of a prediction of states and controls only (PDP_MS_PREDICT_PRIMAL), 5 instead of 13 stores per stage */
+#define PDP_OC_COTANGENT 8 /* the unit as a vector-Jacobian product of the OC solution: demo_x / demo_u do not hold a demonstration but the COTANGENTS of a caller's scalar loss L(x, u),
+                              gx [B][T+1][n] = dL/dx in demo_x and gu [B][T][m] = dL/du in demo_u, and
+                                  grad[b][j] = sum_{t<=T} gx[b][t] . X_t[:,j] + sum_{t<T} gu[b][t] . U_t[:,j]
+                              - the plain contraction, no factor - is dL/dtheta through the solution (X_t = dx_t/dtheta, U_t = du_t/dtheta, the same sweeps, the same order of
+                              summation).  The default mode IS this mode with g = x - x_demo, u - u_demo: half the gradient of its own loss |x - x_demo|^2 + |u - u_demo|^2, as in the
+                              reference (Examples/IRL/cartpole/cartpole_PDP.py:63-74).  No loss is formed: `loss` is not written and may be NULL.  gx[b][0] is read nowhere (X_0 = 0:
+                              the initial state does not depend on theta) - it may hold anything.  x, lam, status, PDP_OC_GIVEN_TRAJ and theta_bstride as in the default mode.
+                              Plain gradient only: with any of dxdp, dudp, sens->riccati, sens->predict_record (a caller who stores the sensitivities can contract them) or with
+                              PDP_OC_PACKED (there is no loss to pack) the call returns PDP_E_ARG */
 int64_t pdp_oc_pdp_workspace_bytes(int B, int T);
 int pdp_oc_pdp_grad_batched(int B, int T, int flags, const double* x0, const double* u, const double* theta,
                             int theta_bstride, const double* demo_x, const double* demo_u, double* x, double* lam,

@@ -193,6 +193,17 @@ class OCSys(_CasadiFrontEnd):
         return self.model().oc_pdp_grad(u, self._theta(auxvar_value, u.shape[0]), demo_state, demo_control, x0=ini_state, x=state_traj,
                                         lam=costate_traj, want_sens=want_sens, buffers=buffers, want_riccati=want_riccati, want_predict_record=want_predict_record)
 
+    def pdp_vjp_batch(self, control_traj, auxvar_value, grad_state, grad_control, ini_state=None, state_traj=None, costate_traj=None, buffers=None):
+        """The gradient of ANY scalar loss L(state, control) through the OC solution, for a batch: grad_state [B,T+1,n] = dL/dstate and grad_control [B,T,m] = dL/dcontrol
+        (cotangents, e.g. from torch.autograd.grad) -> dict(grad [B,p] = sum_t dL/dx_t' X_t + dL/du_t' U_t, x, lam, status), the sensitivities X_t, U_t of the auxiliary
+        control system (PDP.py:582-608) contracted inside the fused kernel instead of being written out (PDP_OC_COTANGENT, include/pdp_hip.h).  pdp_grad_batch is the special
+        case grad_state = x - demo_state, grad_control = u - demo_control (half the gradient of its own loss, Examples/IRL/cartpole/cartpole_PDP.py:63-74).
+        grad_state[:, 0] is not read: the initial state does not depend on the parameter.  Trajectory arguments as in pdp_grad_batch; auxvar_value may be a tensor.
+        pdp_amd.autograd.oc_trajectory wraps solve + this call as a torch.autograd layer."""
+        u = runtime.dev(control_traj)
+        th = auxvar_value if hasattr(auxvar_value, "data_ptr") else self._theta(auxvar_value, u.shape[0])
+        return self.model().oc_pdp_vjp(u, th, grad_state, grad_control, x0=ini_state, x=state_traj, lam=costate_traj, buffers=buffers)
+
     # ---- PDP.py:272-314 ----------------------------------------------------------------------------------------
     def getAuxSys(self, state_traj_opt, control_traj_opt, costate_traj_opt, auxvar_value=1):
         if self._model is None:

@@ -1,0 +1,71 @@
+"""torch.autograd layer over the optimal-control solution: `oc_trajectory` maps the parameter theta of a PDP.OCSys to the optimal
+(state, control) trajectory and is differentiable in theta, so that any scalar loss written in torch on the trajectory can be minimised with
+`loss.backward()` and torch.optim:
+
+    state, control = oc_trajectory(oc, ini_state, horizon, theta)        # theta: CUDA fp64, requires_grad
+    loss = ((state[:, ::10, :2] - keyframes) ** 2).sum()
+    loss.backward()                                                      # theta.grad = dL/dtheta through the OC solution
+
+Forward: OCSys.ocSolver_batch (the reference's OCSys.ocSolver, PDP.py:121-220, for a batch).  Backward: the gradient of a scalar L(x, u) through the solution is
+sum_t (dL/dx_t)' X_t + (dL/du_t)' U_t with X_t = dx_t/dtheta, U_t = du_t/dtheta the solution of the auxiliary control system (PDP.py:582-608) at the optimal
+trajectory - one launch of the fused unit in its cotangent mode (OCSys.pdp_vjp_batch, PDP_OC_COTANGENT in include/pdp_hip.h): the sensitivities are contracted with
+the incoming gradients on the chip and never written out.
+
+Limits: first order only (backward is once_differentiable); no gradient with respect to ini_state; no finite state / control bounds (the bounded solve goes through a
+log-barrier model whose KKT system is not the one the unit differentiates)."""
+import warnings
+
+import torch
+from torch.autograd.function import once_differentiable
+
+
+class _OCTrajectory(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, theta, oc, ini_state, horizon, info_out, solver_kwargs):
+        with torch.no_grad():
+            sol = oc.ocSolver_batch(ini_state, horizon, theta.detach().cpu().numpy(), **solver_kwargs)
+        bad = int((~sol["converged"]).sum())
+        if bad:
+            warnings.warn("oc_trajectory: %d of %d OC solves did not converge (largest |grad| = %.3e); they are differentiated at their last iterate"
+                          % (bad, sol["converged"].numel(), float(sol["grad_norm"][~sol["converged"]].max())), RuntimeWarning)
+        info_out.update(sol)
+        x, u, lam = sol["state"], sol["control"], sol["costate"]
+        ctx.oc, ctx.shared = oc, theta.dim() == 1
+        ctx.save_for_backward(x, u, lam, theta.detach())
+        return x.clone(), u.clone()          # (the saved tensors stay as the solver left them whatever the caller does to the outputs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_state, grad_control):
+        x, u, lam, theta = ctx.saved_tensors
+        gx = torch.zeros_like(x) if grad_state is None else grad_state.to(torch.float64).contiguous()
+        gu = torch.zeros_like(u) if grad_control is None else grad_control.to(torch.float64).contiguous()
+        out = ctx.oc.pdp_vjp_batch(u, theta, gx, gu, state_traj=x, costate_traj=lam)
+        bad = int((out["status"] != 0).sum())
+        if bad:
+            warnings.warn("oc_trajectory: the Riccati sweep of the backward pass reported numerical trouble on %d trajectories (status bits of "
+                          "pdp_oc_pdp_grad_batched, include/pdp_hip.h)" % bad, RuntimeWarning)
+        g = out["grad"]
+        return (g.sum(dim=0) if ctx.shared else g.clone()), None, None, None, None, None
+
+
+def oc_trajectory(oc, ini_state, horizon, theta, return_info=False, **solver_kwargs):
+    """Optimal trajectory of the PDP.OCSys `oc` from ini_state [B, n] over `horizon` steps at the parameter `theta`, differentiable in theta.
+    theta: CUDA fp64 tensor, [p] (one parameter shared by the batch: theta.grad is the sum over the batch) or [B, p] (one per sample).
+    Returns (state [B, T+1, n], control [B, T, m]) - with return_info=True also the solver's dict (cost, converged, iterations, ...).
+    solver_kwargs go to OCSys.ocSolver_batch (tol, max_iter, u_init, warm_start, ...).  Samples that did not converge give one RuntimeWarning per call and are
+    differentiated at their last iterate."""
+    if not (torch.is_tensor(theta) and theta.is_cuda and theta.dtype == torch.float64):
+        raise TypeError("oc_trajectory: theta must be a CUDA fp64 tensor ([p] shared, or [B, p] per sample)")
+    if torch.is_tensor(ini_state) and ini_state.requires_grad:
+        raise NotImplementedError("oc_trajectory: the gradient with respect to ini_state is not implemented (the auxiliary control system is solved with X_0 = 0); "
+                                  "pass ini_state.detach()")
+    if oc.has_bounds():
+        raise NotImplementedError("oc_trajectory: finite state / control bounds are not supported - the bounded solve runs on a log-barrier model whose KKT system is "
+                                  "not the one the gradient unit differentiates")
+    if theta.dim() not in (1, 2) or theta.shape[-1] != oc.n_auxvar:
+        raise ValueError("oc_trajectory: theta must be [p] or [B, p] with p = %d, got %s" % (oc.n_auxvar, tuple(theta.shape)))
+    x0 = ini_state.detach() if torch.is_tensor(ini_state) else ini_state
+    info = {}
+    state, control = _OCTrajectory.apply(theta, oc, x0, int(horizon), info, solver_kwargs)
+    return (state, control, info) if return_info else (state, control)

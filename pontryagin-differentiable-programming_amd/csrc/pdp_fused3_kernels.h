@@ -89,7 +89,11 @@ PDP_DEV BufMap f3_store_map(int R, int C, int ld, int coff, int lane) {
 // leaves the Riccati matrices P_{t+1}, W_{t+1} of every stage (PP[t], WW[t] of the reference's lqrSolver, PDP.py:561-580) in `riccati` [B][T][n n + n p + 1] - with
 // dxdp / dudp they give the first-order change of the optimal (x, u, lambda) with theta (pdp_oc_predict_batched) - and all three are written with range-checked
 // buffer stores (an output that is NULL is a resource of size 0).  A template parameter, not a run-time branch: the default kernel keeps its instruction stream.
-template <class Mdl, int TPW = 4, bool RIC = false>
+// MODE = PDP_FUSED_COT (PDP_OC_COTANGENT; plain gradient only, no sensitivity outputs): demo_x / demo_u carry the cotangents gx = dL/dx [B][T+1][n], gu = dL/du [B][T][m] of
+// a caller's scalar loss L(x, u) and go into the DLX / DLU pool slots as they are - where the default forms x - x_demo, u - u_demo - so that
+// grad = sum_t gx_t' X_t + gu_t' U_t is the vector-Jacobian product of L through the OC solution, contracted in the same order into the same accumulators.
+// No loss is formed (no lsum, no misc[4] share, no hand-over of it: `loss` is not written and may be NULL) and gx[b][0] is never loaded (X_0 = 0).
+template <class Mdl, int TPW = 4, int MODE = PDP_FUSED_PLAIN>
 __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, int flags, const double* __restrict__ x0, const double* __restrict__ u,
                                                             const double* __restrict__ theta, int tb, const double* __restrict__ demo_x,
                                                             const double* __restrict__ demo_u, double* __restrict__ x, double* __restrict__ lam,
@@ -105,6 +109,8 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
     // the wave index is uniform over the wave - said explicitly, or every pointer derived from it (trajectory, workspace, LDS slice) would be
     // carried per lane and every global access would pay 64-bit VALU address arithmetic
     static_assert(TPW == 1 || TPW == 2 || TPW == 4, "trajectories per workgroup");
+    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT, "instantiation");
+    constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, slot = wid & (TPW - 1);
     const bool runner = wid < TPW;
     const int b = blockIdx.x * TPW + slot;
@@ -344,8 +350,11 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         F3_STAMP();
 
         // ---- forward sweep: sensitivities X_t = dx_t/dtheta, U_t, gradient
-        double acc = 0.0, lsum = 0.0;
-        const double dT = lane < NX ? xb[T * NX + lane] - dxb[T * NX + lane] : 0.0;      // terminal residual, requested ahead of the loops that hide its latency
+        double acc = 0.0;
+        [[maybe_unused]] double lsum = 0.0;
+        double dT;                                              // terminal residual (COT: terminal cotangent), requested ahead of the loops that hide its latency
+        if constexpr (COT) dT = lane < NX ? dxb[T * NX + lane] : 0.0;
+        else dT = lane < NX ? xb[T * NX + lane] - dxb[T * NX + lane] : 0.0;
         d4 X2 = z;
         {
             constexpr int DLX = Mdl::FWD_NVAR, DLU = Mdl::FWD_NVAR + NX;      // pool slots of x - x_demo, u - u_demo
@@ -453,13 +462,16 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         F3_STAMP();
         // terminal term (x_T - xd_T)' X_T   (cartpole_PDP.py:74)
         wave_lds_sync();
-        if (lane < NX) { dlT[lane] = dT; lsum += dT * dT; }
+        if (lane < NX) { dlT[lane] = dT; if constexpr (!COT) lsum += dT * dT; }
         wave_lds_sync();
 #pragma unroll
         for (int r = 0; r < 4; ++r) { int row = tile_row(lane, r); if (row < NX) acc += dlT[row] * X2[r]; }
         if (dxdp) store_dense(dxdp + ((int64_t)b * (T + 1) + T) * NX * NP, NX, NP, NP, 0, M, lane, X2);
         finite = finite && tile_finite(X2);
         acc = sum_over_rowgroups(acc);
+        if constexpr (COT) {                                    // no loss, no packed row (PDP_E_ARG at the entry point), nothing to wait for: every chunk has been consumed
+            if (lane >= M && lane < M + NP) grad[(int64_t)b * NP + (lane - M)] = acc;
+        } else {
         lsum = wave_sum(lsum);
         F3_W0();
         wg_wait_ge(fl + 4, 1);
@@ -469,6 +481,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         const int gstride = (flags & PDP_OC_PACKED) ? NP + 1 : NP;
         if (lane >= M && lane < M + NP) grad[(int64_t)b * gstride + (lane - M)] = acc;
         if (lane == 0) { loss[b] = lsum; if (flags & PDP_OC_PACKED) grad[(int64_t)b * gstride + NP] = lsum; }
+        }
         int st = 0;
         if (!__all(finite)) st |= PDP_STATUS_NONFINITE;
         if (!ok) st |= PDP_STATUS_PIVOT;
@@ -595,8 +608,8 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
             }
         }
         F3_STAMP();
-        // ---- forward chunks: lane = time step evaluates F', G', E and the loss terms x - x_demo, u - u_demo
-        double lsum = 0.0;
+        // ---- forward chunks: lane = time step evaluates F', G', E and the loss terms x - x_demo, u - u_demo (COT: the cotangents gx_t, gu_t take their slots)
+        [[maybe_unused]] double lsum = 0.0;
         {
             constexpr int DLX = Mdl::FWD_NVAR, DLU = Mdl::FWD_NVAR + NX;
             for (int c = 0; c < nchunkF; ++c) {
@@ -610,9 +623,17 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                     double xc[NX], uc[NU];
                     double* row = pool + bo + lane * FS;
 #pragma unroll
-                    for (int i = 0; i < NX; ++i) { xc[i] = xb[t * NX + i]; double d = xc[i] - dxb[t * NX + i]; row[DLX + i] = d; lsum += d * d; }
+                    for (int i = 0; i < NX; ++i) {
+                        xc[i] = xb[t * NX + i];
+                        if constexpr (COT) row[DLX + i] = t > 0 ? dxb[t * NX + i] : 0.0;       // gx_0 multiplies X_0 = 0: not loaded
+                        else { double d = xc[i] - dxb[t * NX + i]; row[DLX + i] = d; lsum += d * d; }
+                    }
 #pragma unroll
-                    for (int i = 0; i < NU; ++i) { uc[i] = ub[t * NU + i]; double d = uc[i] - dub[t * NU + i]; row[DLU + i] = d; lsum += d * d; }
+                    for (int i = 0; i < NU; ++i) {
+                        uc[i] = ub[t * NU + i];
+                        if constexpr (COT) row[DLU + i] = dub[t * NU + i];
+                        else { double d = uc[i] - dub[t * NU + i]; row[DLU + i] = d; lsum += d * d; }
+                    }
                     PackedSink s{row};
                     Mdl::eval_fwd(xc, uc, nullptr, th, pc, s);
                     row[F3::CF0] = 0.0;
@@ -622,9 +643,11 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                 wg_signal(fl + 2, g + 1);
             }
         }
+        if constexpr (!COT) {
         lsum = wave_sum(lsum);
         if (lane == 0) misc[4] = lsum;
         wg_signal(fl + 4, 1);
+        }
 #ifdef PDP_PHASE_TIMING
         F3_STAMP();
         if (lane == 0 && b == 0) { long long* o = (long long*)(loss + B) + 16; for (int i = 0; i < 12; ++i) o[i] = ts[i]; o[12] = twait; }

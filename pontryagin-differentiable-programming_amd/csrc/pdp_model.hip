@@ -126,7 +126,9 @@ template <class Mdl>
 int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const double* th, int tb, const double* dx, const double* du, double* x,
            double* lam, double* loss, double* grad, double* dxdp, double* dudp, double* ric, float* prec, int32_t* status, void* ws, int64_t wsb, void* st) {
     if constexpr (fused_oc_ok<Mdl>()) {
-        if (B <= 0 || T <= 0 || !u || !th || !dx || !du || !x || !lam || !loss || !grad || !ws) return PDP_E_ARG;
+        const bool cot = (flags & PDP_OC_COTANGENT) != 0;   // dx, du carry the cotangents of a caller's loss: no loss output, plain gradient only
+        if (B <= 0 || T <= 0 || !u || !th || !dx || !du || !x || !lam || (!loss && !cot) || !grad || !ws) return PDP_E_ARG;
+        if (cot && (dxdp || dudp || ric || prec || (flags & PDP_OC_PACKED))) return PDP_E_ARG;
         if (!(flags & PDP_OC_GIVEN_TRAJ) && !x0) return PDP_E_ARG;
         if (wsb < oc_ws_bytes<Mdl>(B, T)) return PDP_E_ARG;
         const size_t lds = fused_lds_bytes<Mdl>(T);
@@ -150,9 +152,14 @@ int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const dou
                     return launched();
                 };
                 if (ric || dxdp || dudp || prec) {          // sensitivity outputs (any of dxdp, dudp, the Riccati record): the instantiation that writes them with buffer stores
-                    if (tpw == 1) return go(oc_pdp_fused3_kernel<Mdl, 1, true>, 1);
-                    if (tpw == 2) return go(oc_pdp_fused3_kernel<Mdl, 2, true>, 2);
-                    return go(oc_pdp_fused3_kernel<Mdl, 4, true>, 4);
+                    if (tpw == 1) return go(oc_pdp_fused3_kernel<Mdl, 1, PDP_FUSED_RIC>, 1);
+                    if (tpw == 2) return go(oc_pdp_fused3_kernel<Mdl, 2, PDP_FUSED_RIC>, 2);
+                    return go(oc_pdp_fused3_kernel<Mdl, 4, PDP_FUSED_RIC>, 4);
+                }
+                if (cot) {
+                    if (tpw == 1) return go(oc_pdp_fused3_kernel<Mdl, 1, PDP_FUSED_COT>, 1);
+                    if (tpw == 2) return go(oc_pdp_fused3_kernel<Mdl, 2, PDP_FUSED_COT>, 2);
+                    return go(oc_pdp_fused3_kernel<Mdl, 4, PDP_FUSED_COT>, 4);
                 }
                 if (tpw == 1) return go(oc_pdp_fused3_kernel<Mdl, 1>, 1);
                 if (tpw == 2) return go(oc_pdp_fused3_kernel<Mdl, 2>, 2);
@@ -164,7 +171,8 @@ int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const dou
             hipLaunchKernelGGL(kern, dim3(B), dim3(64), lds, S(st), B, T, flags, x0, u, th, tb, dx, du, x, lam, loss, grad, dxdp, dudp, status, (double*)ws, ric, prec);
             return launched();
         };
-        return (ric || prec) ? go1(oc_pdp_fused_kernel<Mdl, true>) : go1(oc_pdp_fused_kernel<Mdl, false>);
+        if (cot) return go1(oc_pdp_fused_kernel<Mdl, PDP_FUSED_COT>);
+        return (ric || prec) ? go1(oc_pdp_fused_kernel<Mdl, PDP_FUSED_RIC>) : go1(oc_pdp_fused_kernel<Mdl, PDP_FUSED_PLAIN>);
     } else { return Mdl::KIND == PDP_KIND_OC ? PDP_E_SIZE : PDP_E_MODE; }
 }
 

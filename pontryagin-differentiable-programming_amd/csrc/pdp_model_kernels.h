@@ -570,7 +570,16 @@ __host__ __device__ inline size_t fused_lds_bytes(int T) {
     return sizeof(double) * (size_t)(RICCATI_SCRATCH + FusedLayout<Mdl>::NC + fused_pool_doubles<Mdl>(T) + Mdl::NX + Mdl::NP + Mdl::NPC + 8);
 }
 
-template <class Mdl, bool RIC = false>
+// instantiations of the fused OC unit (oc_pdp_fused_kernel here, oc_pdp_fused3_kernel in pdp_fused3_kernels.h) - a template parameter, never a run-time branch:
+//   PDP_FUSED_PLAIN  loss and gradient of the demonstration loss (the frozen default);
+//   PDP_FUSED_RIC    the same with the Riccati / prediction records (and, fused3, every sensitivity output) written;
+//   PDP_FUSED_COT    PDP_OC_COTANGENT: demo_x / demo_u carry the cotangents gx = dL/dx [B][T+1][n], gu = dL/du [B][T][m] of a caller's loss and take the place of
+//                    x - x_demo, u - u_demo in the contraction: grad = sum_t gx_t' X_t + gu_t' U_t.  No loss is formed (`loss` may be NULL); gx[b][0] is never loaded (X_0 = 0).
+#define PDP_FUSED_PLAIN 0
+#define PDP_FUSED_RIC 1
+#define PDP_FUSED_COT 2
+
+template <class Mdl, int MODE = PDP_FUSED_PLAIN>
 __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(int B, int T, int flags, const double* __restrict__ x0, const double* __restrict__ u,
                                                            const double* __restrict__ theta, int tb, const double* __restrict__ demo_x,
                                                            const double* __restrict__ demo_u, double* __restrict__ x, double* __restrict__ lam,
@@ -578,6 +587,8 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
                                                            double* __restrict__ dudp, int32_t* __restrict__ status, double* __restrict__ ws_gain,
                                                            double* __restrict__ riccati, float* __restrict__ prec) {
     using L = FusedLayout<Mdl>;
+    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT, "instantiation");
+    constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT;
     constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP, CH = L::CH, M = NU;
     constexpr int GSZ = fused_gain_doubles<Mdl>();         // per step: K [NU x NX] | k [NU x NP] | zero sink
     // SMALL (n <= 4: pendulum, cart-pole, robot arm): every matrix of the recursion fits the rows-0..3 register of its tile and every
@@ -891,7 +902,8 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
     PDP_STAMP();
 
     // ---------------- forward sweep: sensitivities X_t = dx_t/dtheta, U_t, loss and gradient -----------
-    double acc = 0.0, lsum = 0.0;
+    double acc = 0.0;
+    [[maybe_unused]] double lsum = 0.0;
     {
         wave_lds_sync();
         for (int i_ = lane; i_ < Mdl::FWD_NCONST; i_ += 64) blk[1 + i_] = Mdl::fwd_const(i_);
@@ -926,9 +938,17 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
                 double xc[NX], uc[NU];
                 double* row = pool + lane * L::FSTRIDE;
 #pragma unroll
-                for (int i = 0; i < NX; ++i) { xc[i] = xb[t * NX + i]; double d = xc[i] - dxb[t * NX + i]; row[DLX + i] = d; lsum += d * d; }
+                for (int i = 0; i < NX; ++i) {
+                    xc[i] = xb[t * NX + i];
+                    if constexpr (COT) row[DLX + i] = t > 0 ? dxb[t * NX + i] : 0.0;           // gx_0 multiplies X_0 = 0: not loaded
+                    else { double d = xc[i] - dxb[t * NX + i]; row[DLX + i] = d; lsum += d * d; }
+                }
 #pragma unroll
-                for (int i = 0; i < NU; ++i) { uc[i] = ub[t * NU + i]; double d = uc[i] - dub[t * NU + i]; row[DLU + i] = d; lsum += d * d; }
+                for (int i = 0; i < NU; ++i) {
+                    uc[i] = ub[t * NU + i];
+                    if constexpr (COT) row[DLU + i] = dub[t * NU + i];
+                    else { double d = uc[i] - dub[t * NU + i]; row[DLU + i] = d; lsum += d * d; }
+                }
                 PackedSink s{row};
                 Mdl::eval_fwd(xc, uc, nullptr, th, pc, s);
             }
@@ -974,7 +994,10 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
         }
         // terminal term (x_T - xd_T)' X_T   (cartpole_PDP.py:74)
         wave_lds_sync();
-        if (lane < NX) { double d = xb[T * NX + lane] - dxb[T * NX + lane]; dlT[lane] = d; lsum += d * d; }
+        if (lane < NX) {
+            if constexpr (COT) dlT[lane] = dxb[T * NX + lane];
+            else { double d = xb[T * NX + lane] - dxb[T * NX + lane]; dlT[lane] = d; lsum += d * d; }
+        }
         wave_lds_sync();
 #pragma unroll
         for (int r = 0; r < 4; ++r) { int row = tile_row(lane, r); if (row < NX) acc += dlT[row] * X2[r]; }
@@ -982,11 +1005,15 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
         finite = finite && tile_finite(X2);
     }
     acc = sum_over_rowgroups(acc);
+    if constexpr (COT) {                                    // no loss, no packed row (PDP_E_ARG at the entry point)
+        if (lane >= M && lane < M + NP) grad[(int64_t)b * NP + (lane - M)] = acc;
+    } else {
     lsum = wave_sum(lsum);
     // PDP_OC_PACKED: grad is [B][NP + 1] with the loss in the last column - the row the data-parallel iteration all-gathers
     const int gstride = (flags & PDP_OC_PACKED) ? NP + 1 : NP;
     if (lane >= M && lane < M + NP) grad[(int64_t)b * gstride + (lane - M)] = acc;
     if (lane == 0) { loss[b] = lsum; if (flags & PDP_OC_PACKED) grad[(int64_t)b * gstride + NP] = lsum; }
+    }
     int st = 0;
     if (!__all(finite)) st |= PDP_STATUS_NONFINITE;
     if (!ok) st |= PDP_STATUS_PIVOT;

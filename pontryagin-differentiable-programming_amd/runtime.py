@@ -554,11 +554,7 @@ class ModelLib:
         if rc == -2:
             # m + p > 16 (beyond the fused kernel's single parameter tile), n > 16 / m > 4 (beyond one tile per matrix: the size-generic LQR
             # kernel takes over - any n, m), or a horizon whose staging exceeds the LDS: the reference's own route, kernel by kernel
-            if not getattr(self, "_warned_materialised", False):
-                import warnings
-                warnings.warn("pdp_oc_pdp_grad_batched: problem outside the fused kernel's limits (n = %d, m = %d, p = %d, T = %d): taking the "
-                              "kernel-by-kernel route through HBM (several launches, roughly ten times slower)" % (self.n, self.m, p, T), RuntimeWarning)
-                self._warned_materialised = True
+            self._warn_materialised(T)
             self._oc_pdp_grad_materialised(u, theta, demo_x, demo_u, x0, x, lam, flags, loss, grad, status, dxdp, dudp)
             if packed:
                 pk[:, p].copy_(loss)
@@ -574,6 +570,64 @@ class ModelLib:
         if want_predict_record:
             out["predict_record"] = prec
         return out
+
+    def oc_pdp_vjp(self, u, theta, gx, gu, x0=None, x=None, lam=None, buffers=None):
+        """The fused unit as a vector-Jacobian product of the OC solution (PDP_OC_COTANGENT, include/pdp_hip.h): gx [B, T+1, n] = dL/dx and gu [B, T, m] = dL/du are the
+        cotangents of a caller's scalar loss L(x, u); grad [B, p] = sum_t gx_t' X_t + gu_t' U_t is dL/dtheta through the solution, X_t, U_t never leaving the chip.
+        gx[:, 0] is not read (X_0 = 0).  Trajectory arguments as in oc_pdp_grad: (x, lam) given (PDP_OC_GIVEN_TRAJ), else x0 and the kernel integrates u and the costates.
+        No loss is formed.  Returns dict(grad, x, lam, status); `buffers` (a dict the caller keeps) reuses the output tensors and the workspace between calls.
+        Problems beyond the fused kernels' limits take the kernel-by-kernel route, as in oc_pdp_grad."""
+        n, m, p = self.n, self.m, self.p
+        u_shape, gx_shape, gu_shape = tuple(np.shape(u)), tuple(np.shape(gx)), tuple(np.shape(gu))
+        if len(u_shape) != 3 or u_shape[2] != m:                # (shapes are judged before anything is converted or launched)
+            raise ValueError("oc_pdp_vjp: u must be [B, T, %d], got %s" % (m, u_shape))
+        B, T = u_shape[0], u_shape[1]
+        if gx_shape != (B, T + 1, n) or gu_shape != (B, T, m):
+            raise ValueError("oc_pdp_vjp: cotangents must be gx [B, T+1, n] = %s and gu [B, T, m] = %s, got %s and %s"
+                             % ((B, T + 1, n), (B, T, m), gx_shape, gu_shape))
+        if x is not None and (lam is None or tuple(np.shape(x)) != (B, T + 1, n) or tuple(np.shape(lam)) != (B, T, n)):
+            raise ValueError("oc_pdp_vjp: a given trajectory needs x %s and lam %s" % ((B, T + 1, n), (B, T, n)))
+        if x is None and (x0 is None or int(np.prod(np.shape(x0))) != B * n):
+            raise ValueError("oc_pdp_vjp: x0 [B, %d] is needed unless (x, lam) are given" % n)
+        torch = torch_cuda()
+        u, gx, gu = dev(u), dev(gx), dev(gu)
+        th, tb = self._theta(theta, B)
+        flags = 8                                               # PDP_OC_COTANGENT
+        if x is not None:
+            x, lam, flags = dev(x), dev(lam), flags | 1
+            x0 = None
+        else:
+            x0 = dev(x0).reshape(B, n)
+        bufs = buffers if buffers is not None else {}
+
+        def buf(key, shape, dtype=torch.float64):
+            t = bufs.get(key)
+            if t is None or tuple(t.shape) != tuple(shape):
+                t = torch.empty(shape, dtype=dtype, device="cuda")
+                bufs[key] = t
+            return t
+        if x is None:
+            x, lam = buf("x", (B, T + 1, n)), buf("lam", (B, T, n))
+        grad = buf("grad", (B, p))
+        status = buf("status", (B,), torch.int32)
+        nbytes = self.lib.pdp_oc_pdp_workspace_bytes(B, T)
+        ws = buf("ws", (max(nbytes, 8) // 8,))
+        rc = self.lib.pdp_oc_pdp_grad_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(gx), ptr(gu), ptr(x), ptr(lam), ptr(None),
+                                              ptr(grad), ptr(None), ptr(None), ptr(status), ptr(ws), nbytes, current_stream_ptr())
+        if rc == -2:
+            self._warn_materialised(T)
+            self._oc_pdp_grad_materialised(u, theta, gx, gu, x0, x, lam, flags, None, grad, status)
+            rc = 0
+        check(rc, "pdp_oc_pdp_grad_batched (PDP_OC_COTANGENT)")
+        return dict(grad=grad, x=x, lam=lam, status=status)
+
+    def _warn_materialised(self, T):
+        """once per model: the problem is outside the fused kernel's limits and takes the kernel-by-kernel route"""
+        if not getattr(self, "_warned_materialised", False):
+            import warnings
+            warnings.warn("pdp_oc_pdp_grad_batched: problem outside the fused kernel's limits (n = %d, m = %d, p = %d, T = %d): taking the "
+                          "kernel-by-kernel route through HBM (several launches, roughly ten times slower)" % (self.n, self.m, self.p, T), RuntimeWarning)
+            self._warned_materialised = True
 
     def oc_pdp_grad_prepared(self, u, theta, demo_x, demo_u, x0, packed_out=None):
         """The fused OC unit as a PREPARED call: every argument of pdp_oc_pdp_grad_batched marshalled once; the returned step() is one foreign call on the stream that is
@@ -637,7 +691,8 @@ class ModelLib:
     def _oc_pdp_grad_materialised(self, u, theta, demo_x, demo_u, x0, x, lam, flags, loss, grad, status, dxdp=None, dudp=None):
         """The PDP gradient unit by the reference's own route (PDP.py:272-314, 557-608 and the chain rule of cartpole_PDP.py:63-74), one
         kernel per stage: trajectory and costates (unless given), aux matrices to HBM, lqrSolver (column blocks for any p), contraction
-        with (x - x_demo, u - u_demo).  Fills the given output tensors."""
+        with (x - x_demo, u - u_demo) - or, with flags & 8 (PDP_OC_COTANGENT), with the cotangents that demo_x / demo_u then carry (row 0 of demo_x unread; no loss).
+        Fills the given output tensors."""
         torch = torch_cuda()
         B, T = u.shape[0], u.shape[1]
         n, m, p = self.n, self.m, self.p
@@ -647,8 +702,12 @@ class ModelLib:
         aux = self.oc_auxsys(x, u, lam, theta)
         X, U, _, st = lqr_solve(aux["dynF"], aux["dynG"], aux["Hxx"], aux["Huu"], aux["hxx"], aux["hxe"], E=aux["dynE"], Hxu=aux["Hxu"], Hxe=aux["Hxe"],
                                 Hue=aux["Hue"], want_costate=False)
-        ex, eu = x - demo_x, u - demo_u
-        loss.copy_((ex ** 2).sum(dim=(1, 2)) + (eu ** 2).sum(dim=(1, 2)))
+        if flags & 8:
+            ex, eu = demo_x.clone(), demo_u
+            ex[:, 0] = 0.0
+        else:
+            ex, eu = x - demo_x, u - demo_u
+            loss.copy_((ex ** 2).sum(dim=(1, 2)) + (eu ** 2).sum(dim=(1, 2)))
         g = torch.empty((B, p), dtype=torch.float64, device="cuda")
         core = load_core()
         core.pdp_cp_grad_contract_batched.restype = C.c_int
