@@ -567,7 +567,7 @@ def lqr_solver_mp(dynF, dynG, dynE, Hxx, Huu, Hxu, Hxe, Hue, hxx, hxe, ini_state
             PP[t - 1] = Q + tmp * (P * A)
             WW[t - 1] = N + tmp * (W + P * M)
         X = [cv(np.asarray(ini_state, float).reshape(n, -1))]
-        U = []
+        U, Lam = [], []
         for t in range(T):
             P, W = PP[t], WW[t]
             iH = Quu[t] ** -1
@@ -578,7 +578,8 @@ def lqr_solver_mp(dynF, dynG, dynE, Hxx, Huu, Hxu, Hxe, Hue, hxx, hxe, ini_state
             u = -iH * (Qxu[t].T * X[t] + Que[t]) - iH * G[t].T * ((I + P * R) ** -1) * (P * A * X[t] + P * M + W)
             X.append(F[t] * X[t] + G[t] * u + E[t])
             U.append(u)
+            Lam.append(P * X[-1] + W)
         tonp = lambda m_: np.array([[float(m_[r, c]) for c in range(m_.cols)] for r in range(m_.rows)])
-        return {"state_traj_opt": [tonp(x) for x in X], "control_traj_opt": [tonp(u) for u in U]}
+        return {"state_traj_opt": [tonp(x) for x in X], "control_traj_opt": [tonp(u) for u in U], "costate_traj_opt": [tonp(l) for l in Lam]}
     finally:
         mp.mp.dps = old

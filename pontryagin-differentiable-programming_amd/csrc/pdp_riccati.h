@@ -9,8 +9,9 @@
 //     Quu = Huu + G'PG,  Qux = Hxu' + G'PF,  Que = Hue + G'(PE + W)
 //     K = Quu^-1 Qux,  k = Quu^-1 Que,  P- = Hxx + F'PF - Qux'K,  W- = Hxe + F'(PE + W) - Qux'k
 // and the forward pass (PDP.py:588-608)  u = -K x - k,  x+ = F x + G u + E,  lambda+ = P x+ + W.
-// Only an m x m system is solved per step (m <= 4) instead of two n x n inversions; results agree with the
-// reference order of operations to rounding (tests: <= 1e-10 relative against oracle/pdp_oracle.py).
+// Only an m x m system is solved per step (m <= 4) instead of two n x n inversions.  Accuracy: against the same formulas in 40-digit arithmetic the results
+// stay within max(1e-10, the fp64 reference order's own error on the same input) of the largest entry, also where Quu is ill-conditioned (cheap controls on a
+// rank-deficient G: tests/test_gpu_riccati_conditioning.py, down to Huu ~ 1e-5); the cofactor fast paths of the solve are guarded for that (pdp_tile.h).
 //
 // Tile packing (16 columns per tile): the n x p sensitivity block shares a tile with the n x m control
 // block - Y2 = [G | E], HX2 = [Hxu | Hxe], HU2 = [Huu | Hue], W2 = [0 | W] - so one 16x16x16 product yields
@@ -119,7 +120,8 @@ PDP_DEV bool riccati_backward(d4& P, d4& W0, const d4 Ft, const d4 Y2, const d4 
         const double m20 = q[r2 * 16 + c0], m21 = q[r2 * 16 + c1], m22 = q[r2 * 16 + c2];
         double cof = m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20);
         cof = ((i + j) & 1) ? -cof : cof;
-        // Laplace expansion along row 0; the size of its terms against the size of their sum is the conditioning guard
+        // Laplace expansion along row 0; the size of its terms against the size of their sum is the conditioning guard (COFACTOR4_GUARD, pdp_tile.h: the
+        // cofactors cancel inside their 3x3 minors too, so the fast path is left at |det| / mag = 1e-2, where it still holds 1e-11)
         const double ac = Q2[0] * cof;               // lanes 0..3 hold a_0c C_0c (their element is (0, c)): one product, then 4 broadcasts
         const double t0 = readlane_f64(ac, 0), t1 = readlane_f64(ac, 1), t2 = readlane_f64(ac, 2), t3 = readlane_f64(ac, 3);
         const double det = (t0 + t1) + (t2 + t3), mag = (fabs(t0) + fabs(t1)) + (fabs(t2) + fabs(t3));
@@ -127,7 +129,7 @@ PDP_DEV bool riccati_backward(d4& P, d4& W0, const d4 Ft, const d4 Y2, const d4 
             const double a00 = readlane_f64(Q2[0], 0), a01 = readlane_f64(Q2[0], 1), a10 = readlane_f64(Q2[0], 16), a11 = readlane_f64(Q2[0], 17);
             g.pd = a00 > 0.0 && a00 * a11 - a01 * a10 > 0.0 && readlane_f64(cof, 51) > 0.0 && det > 0.0;
         }
-        if (fabs(det) > 1e-10 * mag && fabs(det) <= 1.7e308) {      // uniform branch
+        if (fabs(det) > COFACTOR4_GUARD * mag && fabs(det) <= 1.7e308) {      // uniform branch
             // 1/det: hardware reciprocal + one Newton step (the full IEEE division sequence is a 12-instruction dependent chain
             // in front of the gain MFMAs; det is nowhere near the subnormal / overflow ranges that sequence exists for)
             double rdet = __builtin_amdgcn_rcp(det);
@@ -244,7 +246,7 @@ PDP_DEV bool riccati_backward_aug(d4& P, const d4 Ft, const double Gblk, const d
             const double a00 = readlane_f64(Q2[0], 0), a01 = readlane_f64(Q2[0], 1), a10 = readlane_f64(Q2[0], 16), a11 = readlane_f64(Q2[0], 17);
             g.pd = a00 > 0.0 && a00 * a11 - a01 * a10 > 0.0 && readlane_f64(cof, 51) > 0.0 && det > 0.0;
         }
-        if (fabs(det) > 1e-10 * mag && fabs(det) <= 1.7e308) {
+        if (fabs(det) > COFACTOR4_GUARD * mag && fabs(det) <= 1.7e308) {
             double rdet = __builtin_amdgcn_rcp(det);
             rdet = fma(fma(-det, rdet, 1.0), rdet, rdet);
             Zrep = cof * rdet;

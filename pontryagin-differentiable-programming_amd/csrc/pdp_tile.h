@@ -260,9 +260,22 @@ PDP_DEV bool inverse_small(const double* a_in, double* inv) {
     return ok;
 }
 
+// Conditioning guards of the cofactor / adjugate fast paths.  A cofactor inverse cancels inside its minors as well as in the last sum of the determinant: it loses
+// about cond^2 eps where the pivoted elimination loses cond eps, so the fast path is left long before the determinant itself is in doubt.  Each guard compares |det|
+// with a quantity q that is free on its path; the thresholds come from the CPU sweep probes/riccati_guard_sweep.py (output: profiles/riccati_guard_sweep.txt), which
+// emulates the backward step with the unguarded fast path on cheap-control / rank-deficient-G problems against a 40-digit evaluation: above the threshold the fast path's
+// error in X, U, Lambda stayed <= 4.6e-12 (4 x 4) and <= 1.5e-12 (3 x 3), a tenth of the 1e-10 parity tolerance or less.  The shipped systems stay far above them
+// (smallest q along their demonstrations: quadrotor 0.81, rocket 0.98, robot arm 0.10).
+//   4 x 4 (riccati_backward, riccati_backward_aug):  q = |det| / sum of the |terms| of the Laplace expansion along row 0      error ~ eps / q^2
+//   3 x 3 (inverse_small_fast):                      q = |det| / |product of the diagonal|                                   error ~ 1e-16 / q
+//   2 x 2 (inverse_small_fast): the adjugate is a permutation of the entries, only det cancels: as accurate as the pivoted path at every q the sweep reached
+constexpr double COFACTOR4_GUARD = 1e-2;
+template <int M>
+constexpr double ADJUGATE_GUARD = (M >= 3) ? 1e-4 : 1e-10;
+
 // Inverse of an M x M matrix (M <= 4), uniform over the wave.  Fast path: cofactor (adjugate) formulas with ONE
 // division (fp64 division costs ~74 cycles on gfx950; Gauss-Jordan needs M of them in sequence); guarded by the
-// determinant test |det| > 1e-10 * |prod diag|, otherwise the pivoted Gauss-Jordan above takes over (uniform branch).
+// determinant test |det| > ADJUGATE_GUARD<M> * |prod diag| (above), otherwise the pivoted Gauss-Jordan above takes over (uniform branch).
 template <int M>
 PDP_DEV bool inverse_small_fast(const double* a, double* inv) {
     double dprod = 1.0;                        // |det| <= prod diag for SPD matrices (Hadamard): det / dprod measures conditioning
@@ -295,7 +308,7 @@ PDP_DEV bool inverse_small_fast(const double* a, double* inv) {
         c[12] = -a[4] * c3 + a[5] * c1 - a[6] * c0; c[13] = a[0] * c3 - a[1] * c1 + a[2] * c0;
         c[14] = -a[12] * s3 + a[13] * s1 - a[14] * s0; c[15] = a[8] * s3 - a[9] * s1 + a[10] * s0;
     }
-    if (!(fabs(det) > 1e-10 * fabs(dprod)) || !(fabs(det) <= 1.7e308)) return inverse_small<M>(a, inv);   // ill-conditioned / singular: pivoted path
+    if (!(fabs(det) > ADJUGATE_GUARD<M> * fabs(dprod)) || !(fabs(det) <= 1.7e308)) return inverse_small<M>(a, inv);   // ill-conditioned / singular: pivoted path
     // 1 / det: hardware reciprocal + one Newton step - the IEEE division sequence is a 12-instruction dependent chain in the middle of every backward step, and det
     // (guarded above against vanishing / overflowing) is nowhere near the ranges that sequence exists for; same form as the 4 x 4 path of riccati_backward
     double id = __builtin_amdgcn_rcp(det);
