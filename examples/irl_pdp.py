@@ -13,6 +13,11 @@ Examples/IRL/cartpole/generate_demos.py:38-43) through --demos.  Results are sav
 (results.loss_trace / parameter_trace / learning_rate / time_passed) so its plotting scripts keep working.
 
     python examples/irl_pdp.py --system cartpole --iters 200 --lr 1e-4 [--demos path/to/cartpole_demos.mat]
+
+--method lm: the same problem as nonlinear least squares (the loss is a sum of squares).  The fused kernel also returns the Gauss-Newton matrix J'J beside the gradient
+(PDP_GRAD_GAUSS_NEWTON), and a Levenberg-Marquardt loop (pdp_amd.irl.LMLoop; --iters bounds its evaluations) takes a handful of steps where gradient descent takes thousands:
+
+    python examples/irl_pdp.py --system cartpole --method lm
 """
 import argparse
 import os
@@ -41,6 +46,34 @@ def load_demos(path):
     return xs, us, d["true_parameter"].astype(float).flatten()
 
 
+def reference_last_loss(system):
+    """(steps, mean loss) where the reference's own stored gradient-descent run on the stored demonstrations ends (tests/golden/irltrace_<sys>.npz; that run starts from the
+    reference's initial parameter, row 0 of irltrace_head_<sys>.npz["param"], which --init replays), or None where the trace is not at hand"""
+    path = os.path.join(ROOT, "tests", "golden", "irltrace_%s.npz" % system)
+    if not os.path.exists(path):
+        return None
+    z = np.load(path)
+    return int(z["K"]), float(z["loss_next"][-1])
+
+
+def run_lm(a, oc, demo_x, demo_u, theta, true_parameter):
+    from pdp_amd.irl import LMLoop
+    t0 = time.time()
+    loop = LMLoop.for_irl(oc.model(), demo_x, demo_u, theta)
+    r = loop.run(max_evals=a.iters, loss_tol=a.loss_tol)
+    for k, (loss, th, lam) in enumerate(zip(r["loss_trace"], r["parameter_trace"], r["lambda_trace"])):
+        print("accepted %3d  loss %.6e  |theta - theta*| %.4e  next damping %.1e" % (k, loss, np.abs(th - true_parameter).max(), lam))
+    save = {"trail_no": 0, "loss_trace": r["loss_trace"], "parameter_trace": r["parameter_trace"], "learning_rate": 0.0, "time_passed": time.time() - t0}
+    if a.out:
+        sio.savemat(a.out, {"results": save})
+    ref = reference_last_loss(a.system) if a.demos is None else None
+    print("done: %d evaluations (%d rejected%s) x %d demos in %.2f s, final loss %.4e%s" % (
+        r["evaluations"], r["rejected"], ", stalled at the damping limit" if r["stalled"] else "", demo_x.shape[0], save["time_passed"], r["loss_trace"][-1],
+        "  (for comparison, another start: the reference's stored gradient-descent run on these demos, from its own initial parameter, ends at %.4e after %d steps)"
+        % (ref[1], ref[0]) if ref else ""))
+    return list(r["loss_trace"])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--system", default="cartpole", choices=["pendulum", "cartpole", "robotarm", "quadrotor", "rocket"])
@@ -56,6 +89,10 @@ def main():
                          "(primal: cheaper to write and read; enough where the multipliers move little per step, e.g. the quadrotor)")
     ap.add_argument("--graph", action="store_true",
                     help="keep the loop on the device and replay each iteration as one hipGraph (pdp_amd.irl.IRLLoop): no host work per iteration, traces written by the graph")
+    ap.add_argument("--method", default="gd", choices=["gd", "lm"],
+                    help="gd: the reference's gradient descent (default); lm: Levenberg-Marquardt on the Gauss-Newton matrix the fused kernel returns "
+                         "(--iters = most evaluations, --lr unused)")
+    ap.add_argument("--loss-tol", type=float, default=1e-16, help="--method lm: stop at this mean loss")
     ap.add_argument("--demos", default=None, help="<name>_demos.mat in the reference's schema (default: the stored demos of --system)")
     a = ap.parse_args()
 
@@ -76,6 +113,8 @@ def main():
     if a.init is not None:
         theta = np.load(a.init).astype(float).reshape(-1) if a.init.endswith(".npy") else np.array([float(v) for v in a.init.split(",")])
         assert theta.size == true_parameter.size, "--init: %d values for %d parameters" % (theta.size, true_parameter.size)
+    if a.method == "lm":
+        return run_lm(a, oc, demo_x, demo_u, theta, true_parameter)
     loss_trace, parameter_trace = [], []
     warm, predict, theta_prev = None, None, None
     fused = oc.model().n <= 16 and oc.model().m <= 4 and oc.model().m + oc.model().p <= 16      # the kernels that keep the sensitivities

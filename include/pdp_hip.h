@@ -300,6 +300,15 @@ int pdp_oc_solve_ms_batched(int B, int T, const double* x0, const double* theta,
                               the initial state does not depend on theta) - it may hold anything.  x, lam, status, PDP_OC_GIVEN_TRAJ and theta_bstride as in the default mode.
                               Plain gradient only: with any of dxdp, dudp, sens->riccati, sens->predict_record (a caller who stores the sensitivities can contract them) or with
                               PDP_OC_PACKED (there is no loss to pack) the call returns PDP_E_ARG */
+#define PDP_GRAD_GAUSS_NEWTON 16 /* (a bit of the same `flags`) the default unit, and with it the Gauss-Newton matrix of its sum-of-squares loss: grad is ONE PACKED ROW per trajectory,
+                              [B][p + 1 + p p] = gradient [p] | loss | G [p][p] row-major, with
+                                  G[b][i][j] = sum_{t<=T} X_t[:,i] . X_t[:,j] + sum_{t<T} U_t[:,i] . U_t[:,j]
+                              - no factor: with the residual vector r = (x - x_demo, u - u_demo) and J = dr/dtheta, grad = J'r (as in the default mode) and G = J'J belong together, so
+                              that solve(G + damping, grad) is a Gauss-Newton / Levenberg-Marquardt step.  X_t, U_t are the tiles the forward sweep holds in registers; they never
+                              leave the chip.  G[i][j] and G[j][i] are the same products summed in the same order: G is symmetric to the bit.  loss [B] is written as well; gradient,
+                              loss, x, lam, status, PDP_OC_GIVEN_TRAJ and theta_bstride as in the default mode.  Rows sum over a batch (and over ranks) like PDP_OC_PACKED rows.
+                              Plain gradient of the demonstration loss only: with PDP_OC_COTANGENT (a general loss needs its own Hessian), with PDP_OC_PACKED (one row layout per
+                              call) or with any of dxdp, dudp, sens->riccati, sens->predict_record the call returns PDP_E_ARG before anything is launched */
 int64_t pdp_oc_pdp_workspace_bytes(int B, int T);
 int pdp_oc_pdp_grad_batched(int B, int T, int flags, const double* x0, const double* u, const double* theta,
                             int theta_bstride, const double* demo_x, const double* demo_u, double* x, double* lam,

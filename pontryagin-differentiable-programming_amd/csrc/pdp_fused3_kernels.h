@@ -93,6 +93,9 @@ PDP_DEV BufMap f3_store_map(int R, int C, int ld, int coff, int lane) {
 // a caller's scalar loss L(x, u) and go into the DLX / DLU pool slots as they are - where the default forms x - x_demo, u - u_demo - so that
 // grad = sum_t gx_t' X_t + gu_t' U_t is the vector-Jacobian product of L through the OC solution, contracted in the same order into the same accumulators.
 // No loss is formed (no lsum, no misc[4] share, no hand-over of it: `loss` is not written and may be NULL) and gx[b][0] is never loaded (X_0 = 0).
+// MODE = PDP_FUSED_GN (PDP_GRAD_GAUSS_NEWTON; plain gradient only): the default unit, and in the forward sweep one more accumulator tile Gn += X_t' X_t + U_t' U_t - the
+// Gauss-Newton matrix J'J of the sum-of-squares loss, whose parameter block is rows and columns M .. M + NP - 1 of the tile.  grad is the packed row
+// [B][NP + 1 + NP NP] = gradient | loss | G row-major.  G[i][j] and G[j][i] are the same products in the same order: symmetric to the bit.
 template <class Mdl, int TPW = 4, int MODE = PDP_FUSED_PLAIN>
 __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, int flags, const double* __restrict__ x0, const double* __restrict__ u,
                                                             const double* __restrict__ theta, int tb, const double* __restrict__ demo_x,
@@ -109,8 +112,8 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
     // the wave index is uniform over the wave - said explicitly, or every pointer derived from it (trajectory, workspace, LDS slice) would be
     // carried per lane and every global access would pay 64-bit VALU address arithmetic
     static_assert(TPW == 1 || TPW == 2 || TPW == 4, "trajectories per workgroup");
-    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT, "instantiation");
-    constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT;
+    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT || MODE == PDP_FUSED_GN, "instantiation");
+    constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT, GN = MODE == PDP_FUSED_GN;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, slot = wid & (TPW - 1);
     const bool runner = wid < TPW;
     const int b = blockIdx.x * TPW + slot;
@@ -356,6 +359,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         if constexpr (COT) dT = lane < NX ? dxb[T * NX + lane] : 0.0;
         else dT = lane < NX ? xb[T * NX + lane] - dxb[T * NX + lane] : 0.0;
         d4 X2 = z;
+        [[maybe_unused]] d4 Gn = z;                             // GN: sum_t X_t' X_t + U_t' U_t
         {
             constexpr int DLX = Mdl::FWD_NVAR, DLU = Mdl::FWD_NVAR + NX;      // pool slots of x - x_demo, u - u_demo
             RowGather gFT, gGT, gE, gDX, gDU;
@@ -409,6 +413,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                     d4 DU = row_read<1>(rDU, imm);
                     d4 U2;
                     riccati_forward(KTc, kc, FT, GT, E2, Xc, U2, Xn);
+                    if constexpr (GN) { Gn = mma_tn(Xc, Xc, Gn); Gn = mma_tn_r0(U2, U2, Gn); }
                     acc += DX[0] * Xc[0] + DX[1] * Xc[1] + DX[2] * Xc[2] + DX[3] * Xc[3] + DU[0] * U2[0];
                     if constexpr (RIC) {
                         if (dxdp || dudp) {
@@ -468,6 +473,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         for (int r = 0; r < 4; ++r) { int row = tile_row(lane, r); if (row < NX) acc += dlT[row] * X2[r]; }
         if (dxdp) store_dense(dxdp + ((int64_t)b * (T + 1) + T) * NX * NP, NX, NP, NP, 0, M, lane, X2);
         finite = finite && tile_finite(X2);
+        if constexpr (GN) Gn = mma_tn(X2, X2, Gn);              // X_T
         acc = sum_over_rowgroups(acc);
         if constexpr (COT) {                                    // no loss, no packed row (PDP_E_ARG at the entry point), nothing to wait for: every chunk has been consumed
             if (lane >= M && lane < M + NP) grad[(int64_t)b * NP + (lane - M)] = acc;
@@ -478,9 +484,16 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         F3_W1();
         lsum += misc[4];                                        // the evaluator's share: sum over t < T of |x - xd|^2 + |u - ud|^2
         // PDP_OC_PACKED: grad is [B][NP + 1] with the loss in the last column - the row the data-parallel iteration all-gathers
+        if constexpr (GN) {                                     // the packed row gradient | loss | G (PDP_OC_PACKED is PDP_E_ARG at the entry point)
+            double* row = grad + (int64_t)b * (NP + 1 + NP * NP);
+            if (lane >= M && lane < M + NP) row[lane - M] = acc;
+            if (lane == 0) { loss[b] = lsum; row[NP] = lsum; }
+            store_dense(row + NP + 1, NP, NP, NP, M, M, lane, Gn);
+        } else {
         const int gstride = (flags & PDP_OC_PACKED) ? NP + 1 : NP;
         if (lane >= M && lane < M + NP) grad[(int64_t)b * gstride + (lane - M)] = acc;
         if (lane == 0) { loss[b] = lsum; if (flags & PDP_OC_PACKED) grad[(int64_t)b * gstride + NP] = lsum; }
+        }
         }
         int st = 0;
         if (!__all(finite)) st |= PDP_STATUS_NONFINITE;

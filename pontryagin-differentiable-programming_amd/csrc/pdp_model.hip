@@ -129,6 +129,8 @@ int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const dou
         const bool cot = (flags & PDP_OC_COTANGENT) != 0;   // dx, du carry the cotangents of a caller's loss: no loss output, plain gradient only
         if (B <= 0 || T <= 0 || !u || !th || !dx || !du || !x || !lam || (!loss && !cot) || !grad || !ws) return PDP_E_ARG;
         if (cot && (dxdp || dudp || ric || prec || (flags & PDP_OC_PACKED))) return PDP_E_ARG;
+        const bool gn = (flags & PDP_GRAD_GAUSS_NEWTON) != 0;   // grad is the packed row gradient | loss | G = J'J: plain gradient of the demonstration loss only
+        if (gn && (cot || dxdp || dudp || ric || prec || (flags & PDP_OC_PACKED))) return PDP_E_ARG;
         if (!(flags & PDP_OC_GIVEN_TRAJ) && !x0) return PDP_E_ARG;
         if (wsb < oc_ws_bytes<Mdl>(B, T)) return PDP_E_ARG;
         const size_t lds = fused_lds_bytes<Mdl>(T);
@@ -161,6 +163,11 @@ int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const dou
                     if (tpw == 2) return go(oc_pdp_fused3_kernel<Mdl, 2, PDP_FUSED_COT>, 2);
                     return go(oc_pdp_fused3_kernel<Mdl, 4, PDP_FUSED_COT>, 4);
                 }
+                if (gn) {
+                    if (tpw == 1) return go(oc_pdp_fused3_kernel<Mdl, 1, PDP_FUSED_GN>, 1);
+                    if (tpw == 2) return go(oc_pdp_fused3_kernel<Mdl, 2, PDP_FUSED_GN>, 2);
+                    return go(oc_pdp_fused3_kernel<Mdl, 4, PDP_FUSED_GN>, 4);
+                }
                 if (tpw == 1) return go(oc_pdp_fused3_kernel<Mdl, 1>, 1);
                 if (tpw == 2) return go(oc_pdp_fused3_kernel<Mdl, 2>, 2);
                 return go(oc_pdp_fused3_kernel<Mdl, 4>, 4);
@@ -172,6 +179,7 @@ int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const dou
             return launched();
         };
         if (cot) return go1(oc_pdp_fused_kernel<Mdl, PDP_FUSED_COT>);
+        if (gn) return go1(oc_pdp_fused_kernel<Mdl, PDP_FUSED_GN>);
         return (ric || prec) ? go1(oc_pdp_fused_kernel<Mdl, PDP_FUSED_RIC>) : go1(oc_pdp_fused_kernel<Mdl, PDP_FUSED_PLAIN>);
     } else { return Mdl::KIND == PDP_KIND_OC ? PDP_E_SIZE : PDP_E_MODE; }
 }

@@ -575,9 +575,12 @@ __host__ __device__ inline size_t fused_lds_bytes(int T) {
 //   PDP_FUSED_RIC    the same with the Riccati / prediction records (and, fused3, every sensitivity output) written;
 //   PDP_FUSED_COT    PDP_OC_COTANGENT: demo_x / demo_u carry the cotangents gx = dL/dx [B][T+1][n], gu = dL/du [B][T][m] of a caller's loss and take the place of
 //                    x - x_demo, u - u_demo in the contraction: grad = sum_t gx_t' X_t + gu_t' U_t.  No loss is formed (`loss` may be NULL); gx[b][0] is never loaded (X_0 = 0).
+//   PDP_FUSED_GN     PDP_GRAD_GAUSS_NEWTON: PDP_FUSED_PLAIN plus one accumulator tile in the forward sweep, Gn += X_t' X_t + U_t' U_t (the X_t, U_t tiles are in registers
+//                    there): the Gauss-Newton matrix G = J'J of the sum-of-squares loss.  grad is the packed row [B][p + 1 + p p] = gradient | loss | G row-major.
 #define PDP_FUSED_PLAIN 0
 #define PDP_FUSED_RIC 1
 #define PDP_FUSED_COT 2
+#define PDP_FUSED_GN 3
 
 template <class Mdl, int MODE = PDP_FUSED_PLAIN>
 __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(int B, int T, int flags, const double* __restrict__ x0, const double* __restrict__ u,
@@ -587,8 +590,8 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
                                                            double* __restrict__ dudp, int32_t* __restrict__ status, double* __restrict__ ws_gain,
                                                            double* __restrict__ riccati, float* __restrict__ prec) {
     using L = FusedLayout<Mdl>;
-    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT, "instantiation");
-    constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT;
+    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT || MODE == PDP_FUSED_GN, "instantiation");
+    constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT, GN = MODE == PDP_FUSED_GN;
     constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP, CH = L::CH, M = NU;
     constexpr int GSZ = fused_gain_doubles<Mdl>();         // per step: K [NU x NX] | k [NU x NP] | zero sink
     // SMALL (n <= 4: pendulum, cart-pole, robot arm): every matrix of the recursion fits the rows-0..3 register of its tile and every
@@ -919,6 +922,7 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
         const double* dxb = demo_x + (int64_t)b * (T + 1) * NX;
         const double* dub = demo_u + (int64_t)b * T * NU;
         d4 X2 = z;
+        [[maybe_unused]] d4 Gn = z;                         // GN: sum_t X_t' X_t + U_t' U_t; parameter block = rows and columns M .. M + NP - 1
         // feedback gains of step t are fetched one step ahead (each lane re-reads exactly what it stored)
         // K is read back transposed and replicated in the four column blocks (operand form of the 4-row product U = -K X - k)
         const TileMapBytes mKT = to_bytes_sink(make_rep4_map_transposed(NX, NU, NX, lane), GSZ0 - 1), mIK = make_tile_map_sink(NU, NP, NP, 0, M, lane, NU * NP);
@@ -975,6 +979,11 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
                 } else
                 riccati_forward(KTc, kc, FT, GT, E2, Xc, U2, Xn);
                 PDP_FINE(10, t == 20);
+                if constexpr (GN) {             // (SMALL: X_t and U_t live on register 0 in the ordinary column layout - parameters in columns M .. - with rows >= n / >= m zero)
+                    if constexpr (SMALL) Gn = mma_tn_r0(Xc, Xc, Gn);
+                    else Gn = mma_tn(Xc, Xc, Gn);
+                    Gn = mma_tn_r0(U2, U2, Gn);
+                }
                 acc += DX[0] * Xc[0] + DX[1] * Xc[1] + DX[2] * Xc[2] + DX[3] * Xc[3] + DU[0] * U2[0];
                 if (dxdp) store_dense(dxdp + ((int64_t)b * (T + 1) + t) * NX * NP, NX, NP, NP, 0, M, lane, Xc);
                 if (dudp) store_dense(dudp + ((int64_t)b * T + t) * NU * NP, NU, NP, NP, 0, M, lane, U2);
@@ -1003,6 +1012,11 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
         for (int r = 0; r < 4; ++r) { int row = tile_row(lane, r); if (row < NX) acc += dlT[row] * X2[r]; }
         if (dxdp) store_dense(dxdp + ((int64_t)b * (T + 1) + T) * NX * NP, NX, NP, NP, 0, M, lane, X2);
         finite = finite && tile_finite(X2);
+        if constexpr (GN) {                                 // X_T, and the packed row's G block (gradient and loss follow below)
+            if constexpr (SMALL) Gn = mma_tn_r0(X2, X2, Gn);
+            else Gn = mma_tn(X2, X2, Gn);
+            store_dense(grad + (int64_t)b * (NP + 1 + NP * NP) + NP + 1, NP, NP, NP, M, M, lane, Gn);
+        }
     }
     acc = sum_over_rowgroups(acc);
     if constexpr (COT) {                                    // no loss, no packed row (PDP_E_ARG at the entry point)
@@ -1010,9 +1024,9 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
     } else {
     lsum = wave_sum(lsum);
     // PDP_OC_PACKED: grad is [B][NP + 1] with the loss in the last column - the row the data-parallel iteration all-gathers
-    const int gstride = (flags & PDP_OC_PACKED) ? NP + 1 : NP;
+    const int gstride = GN ? NP + 1 + NP * NP : ((flags & PDP_OC_PACKED) ? NP + 1 : NP);      // (GN: PDP_OC_PACKED is PDP_E_ARG at the entry point)
     if (lane >= M && lane < M + NP) grad[(int64_t)b * gstride + (lane - M)] = acc;
-    if (lane == 0) { loss[b] = lsum; if (flags & PDP_OC_PACKED) grad[(int64_t)b * gstride + NP] = lsum; }
+    if (lane == 0) { loss[b] = lsum; if (GN || (flags & PDP_OC_PACKED)) grad[(int64_t)b * gstride + NP] = lsum; }
     }
     int st = 0;
     if (!__all(finite)) st |= PDP_STATUS_NONFINITE;

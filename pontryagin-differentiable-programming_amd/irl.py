@@ -10,6 +10,11 @@ flags and iteration counts of the solves are accumulated on the device and read 
 hipGraph on ROCm: every buffer, the parameter vector, the step and the traces live at fixed device addresses) and `IRLLoop.run(n)` replays it n times.  Measured
 (bench.py, `irl_loop_wall_clock`): with three launches per iteration and no synchronisation the Python-driven loop keeps the GPU as busy as the graph replay does (C3: 0.236 /
 0.245 ms per iteration, C2: 0.096 / 0.100 ms); the graph is for callers whose host thread is busy elsewhere.
+
+LMLoop / lm_step: the same IRL problem as nonlinear least squares.  The loss of the drivers is a sum of squares, and the fused unit's PDP_GRAD_GAUSS_NEWTON instantiation returns
+the Gauss-Newton matrix G = J'J beside the gradient J'r from the sensitivity tiles it holds anyway, so a Levenberg-Marquardt step costs one solve and one unit call, like a
+gradient-descent step, and a handful of them reach what thousands of descent steps do not.  A step is accepted or rejected on the loss: this loop is driven by the host (LMLoop.for_irl reads
+the device once per evaluation: rows and health flags in one copy) and is not graph-replayed.
 """
 import numpy as np
 
@@ -151,3 +156,124 @@ class IRLLoop(_DeviceLoop):
         r = super().results()
         r["newton_iterations_per_solve"] = r["newton_iterations"] / max(1, r["iterations"] * self.B)
         return r
+
+
+def lm_step(g, G, lam):
+    """Marquardt's scaled damping: step = solve(G + lam diag(diag G), g), a diagonal entry of 0 replaced by lam itself; the trial point is theta - step.  g [p] and G [p, p]
+    are host arrays (p <= 16 and G is a batch sum: numpy.linalg.solve on the host, lstsq where the damped matrix is still singular)."""
+    g, G = np.asarray(g, dtype=float).reshape(-1), np.asarray(G, dtype=float)
+    d = np.diag(G).copy()
+    A = G + np.diag(np.where(d == 0.0, lam, lam * d))
+    try:
+        return np.linalg.solve(A, g)
+    except np.linalg.LinAlgError:
+        return np.linalg.lstsq(A, g, rcond=None)[0]
+
+
+class LMLoop:
+    """Levenberg-Marquardt on a sum-of-squares loss.  evaluate(theta [p], numpy) -> (loss, g [p], G [p, p]) as host floats / numpy arrays with g = J'r, G = J'J in the same
+    scaling (half the gradient of loss = |r|^2, as the fused unit returns them), or None where theta cannot be evaluated (a solve that did not converge, a singular stage).
+    Schedule: the trial point theta - lm_step(g, G, lam) is accepted iff its loss is finite and strictly below the current one; then lam <- max(lam / down, lam_min), else
+    lam <- lam * up.  run() ends at max_evals evaluations, at loss <= loss_tol, or when lam > lam_max - no damping the schedule may try improves the loss any more: the fp64
+    floor of the problem, reported as results()["stalled"], not raised.
+    Out of scope: per-sample parameters (the fused unit serves them; the loop is the reference's shared-parameter setting) and a device-resident or graph-captured loop."""
+
+    def __init__(self, evaluate, theta0, lam0=1e-3, up=10.0, down=10.0, lam_min=1e-12, lam_max=1e8):
+        self.evaluate = evaluate
+        self.theta = np.array(theta0, dtype=float).reshape(-1)
+        self.lam, self.up, self.down, self.lam_min, self.lam_max = float(lam0), float(up), float(down), float(lam_min), float(lam_max)
+        self.current = None                     # (loss, g, G) at self.theta
+        self.evaluations = self.rejected = 0
+        self.stalled = False
+        self.on_accept = None                   # called after every accepted point (for_irl: keeps that point's solution as the next warm start)
+        self.loss_trace, self.parameter_trace, self.lambda_trace = [], [], []
+
+    def _eval(self, theta):
+        self.evaluations += 1
+        r = self.evaluate(theta)
+        if r is None:
+            return None
+        loss, g, G = float(r[0]), np.asarray(r[1], dtype=float).reshape(-1), np.asarray(r[2], dtype=float)
+        if not np.isfinite(loss):
+            return None
+        return loss, g, G
+
+    def start(self):
+        """the evaluation at theta0 (the first accepted point)"""
+        self.current = self._eval(self.theta)
+        if self.current is None:
+            raise RuntimeError("LMLoop: the initial parameter could not be evaluated")
+        self._record()
+
+    def _record(self):
+        self.loss_trace.append(self.current[0])
+        self.parameter_trace.append(self.theta.copy())
+        self.lambda_trace.append(self.lam)
+        if self.on_accept is not None:
+            self.on_accept()
+
+    def step(self):
+        """one trial: True if it was accepted"""
+        loss, g, G = self.current
+        trial = self.theta - lm_step(g, G, self.lam)
+        if np.isfinite(trial).all():
+            r = self._eval(trial)
+        else:
+            r, self.evaluations = None, self.evaluations + 1        # (a trial that cannot be formed still counts against the budget)
+        if r is not None and r[0] < loss:
+            self.theta, self.current = trial, r
+            self.lam = max(self.lam / self.down, self.lam_min)
+            self._record()
+            return True
+        self.rejected += 1
+        self.lam *= self.up
+        return False
+
+    def run(self, max_evals=50, loss_tol=0.0):
+        if self.current is None:
+            self.start()
+        while self.evaluations < max_evals and self.current[0] > loss_tol:
+            if self.lam > self.lam_max:
+                self.stalled = True
+                break
+            self.step()
+        return self.results()
+
+    def results(self):
+        """the reference's result fields over the ACCEPTED points (loss_trace, parameter_trace) + evaluations, rejected, lambda_trace (the damping after each accepted point),
+        stalled"""
+        return {"loss_trace": np.array(self.loss_trace), "parameter_trace": np.array(self.parameter_trace).reshape(len(self.parameter_trace), self.theta.size),
+                "lambda_trace": np.array(self.lambda_trace), "evaluations": self.evaluations, "rejected": self.rejected, "stalled": self.stalled,
+                "iterations": len(self.loss_trace)}
+
+    @classmethod
+    def for_irl(cls, mdl, demo_x, demo_u, theta0, tol=1e-10, max_iter=300, n_total=None, **kw):
+        """The IRL drivers' problem: mdl a runtime.ModelLib of an OC model, demo_x [B, T+1, n], demo_u [B, T, m] the demonstrations (this rank's shard under
+        torch.distributed; n_total as in parallel.allreduce_mean_packed), theta0 [p] shared by all of them.  evaluate(theta) solves every demonstration's OC problem
+        (oc_solve_ms: the first cold, later ones warm from COPIES of the last accepted solution, so that a rejected trial cannot damage it), runs the fused unit once with
+        gauss_newton=True on the solutions and hands the packed rows, with the count of samples whose solve did not converge or reported trouble or whose unit set a
+        status bit, to parallel.mean_row_checked: one all-reduce when a process group exchanges, one copy of p + 3 + p p doubles to the host.  A trial with such a sample on
+        ANY rank is None on EVERY rank (the decision travels with the rows: no rank skips a collective the others issue)."""
+        from . import parallel
+        demo_x, demo_u = rt.dev(demo_x), rt.dev(demo_u)
+        B, T, p = int(demo_u.shape[0]), int(demo_u.shape[1]), mdl.p
+        assert demo_x.shape == (B, T + 1, mdl.n) and demo_u.shape == (B, T, mdl.m)
+        x0 = demo_x[:, 0].contiguous()
+        bufs, state = {}, {"accepted": None, "trial": None}
+        informational = 128 | 512 | 1024 | 2048          # PDP_MS_RESTORED, PDP_MS_PREDICT_REJECTED, PDP_MS_SOC, PDP_MS_WATCHDOG
+
+        def evaluate(theta):
+            # no decision on this rank's own flags: solve and unit always run, the flags are counted on the device and travel with the rows, so that every rank issues
+            # the same collective and takes the same decision (parallel.mean_row_checked) - and the host reads the device once
+            s = mdl.oc_solve_ms(x0, theta, T, tol=tol, max_iter=max_iter, warm=state["accepted"])
+            out = mdl.oc_pdp_grad(s["control"], theta, demo_x, demo_u, x=s["state"], lam=s["costate"], gauss_newton=True, buffers=bufs)
+            bad = (s["converged_flags"] == 0) | ((s["status"] & ~informational) != 0) | (out["status"] != 0)
+            row = parallel.mean_row_checked(out["packed_gn"], bad, n_total)
+            if row is None:
+                return None
+            state["trial"] = (s["state"], s["control"], s["costate"])
+            return float(row[p]), row[:p].copy(), row[p + 1:].reshape(p, p).copy()
+
+        loop = cls(evaluate, theta0, **kw)
+        loop.on_accept = lambda: state.update(accepted=state["trial"])
+        return loop

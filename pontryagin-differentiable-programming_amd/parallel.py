@@ -112,6 +112,34 @@ def allreduce_mean_packed(packed, n_total=None):
     return s / float(n_total)
 
 
+def mean_loss_grad_gn(packed_gn, p, n_total=None):
+    """Batch mean over ALL trajectories of all ranks of the rows PDP_GRAD_GAUSS_NEWTON writes ([b, p + 1 + p p] = gradient | loss | G row-major, out["packed_gn"] of
+    ModelLib.oc_pdp_grad(gauss_newton=True)): (loss_mean, grad_mean [p], G_mean [p, p]).  Local row sum and ONE all-reduce of p + 1 + p p doubles
+    (allreduce_mean_packed sums rows of any width) - the whole exchange of a data-parallel Levenberg-Marquardt iteration."""
+    p = int(p)
+    if packed_gn.dim() != 2 or packed_gn.shape[1] != p + 1 + p * p:
+        raise ValueError("mean_loss_grad_gn: rows of p + 1 + p p = %d entries expected, got %s" % (p + 1 + p * p, tuple(packed_gn.shape)))
+    m = allreduce_mean_packed(packed_gn, n_total)
+    return m[p], m[:p], m[p + 1:].reshape(p, p)
+
+
+def mean_row_checked(packed, bad, n_total=None):
+    """The batch mean of per-sample rows [b, w] over all ranks TOGETHER with the decision whether the point they were taken at counts: `bad` (a tensor on the rows'
+    device, any shape) is this rank's count of samples that must not be used (an unconverged solve, a status bit).  Row sum, sum of `bad` and row count travel as ONE
+    message of w + 2 doubles - one all-reduce when a process group exchanges, and ONE copy to the host either way - so every rank sees the same count and takes the same
+    decision: None on EVERY rank if any rank counted a bad sample, else the mean row [w] as a numpy array.  A rank must never decide on its own flags before this call:
+    it would skip a collective the others issue (irl.LMLoop.for_irl).  n_total: the number of rows over all ranks (None: the exchanged count)."""
+    w = packed.shape[1]
+    extra = torch.stack([bad.to(packed.dtype).sum(), torch.tensor(float(packed.shape[0]), dtype=packed.dtype, device=packed.device)])
+    s = torch.cat([packed.sum(dim=0), extra])
+    if exchange_active():
+        all_reduce_(s)
+    h = s.cpu().numpy()
+    if not h[w] == 0.0:                                     # (a NaN count is bad as well)
+        return None
+    return h[:w] / float(h[w + 1] if n_total is None else n_total)
+
+
 def mean_loss_grad(loss, grad, n_total=None, mode="allgather"):
     """the reference's batch mean of (loss, gradient) over ALL trajectories of all ranks.
     mode "allgather": every rank receives every per-sample row and reduces locally (for callers that also want the rows);

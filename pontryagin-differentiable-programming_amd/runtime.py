@@ -495,7 +495,7 @@ class ModelLib:
         return out
 
     def oc_pdp_grad(self, u, theta, demo_x, demo_u, x0=None, x=None, lam=None, want_sens=False, buffers=None, packed=False, want_riccati=False,
-                    want_predict_record=False):
+                    want_predict_record=False, gauss_newton=False):
         """Fused forward + Riccati + PDP gradient.  Give (x, lam) to use an optimal trajectory (PDP_OC_GIVEN_TRAJ),
         else x0 and the kernel integrates u and the costates itself.  Returns dict(loss, grad, x, lam, status[, dxdp, dudp][, riccati]).
         packed: the kernel writes gradient and loss as one [B, p+1] tensor (PDP_OC_PACKED; out["packed"], out["grad"] is a view of it).
@@ -503,7 +503,13 @@ class ModelLib:
         out["riccati"] [B, T, n n + n p + 1] = P_{t+1} | W_{t+1} | one scratch word per stage (pdp_oc_pdp_grad_sens_batched).
         want_predict_record: out["predict_record"], float32 [B, T, 2 n p + m p + n (n + 1) / 2] - the same information packed in single precision, what an IRL loop
         hands to the next oc_solve_ms(predict=dict(dtheta=..., record=...)) (2.4 times less memory traffic than the fp64 outputs).  want_predict_record="primal"
-        (PDP_OC_RECORD_PRIMAL): only the X | U part of the record is written - for oc_solve_ms(predict=dict(..., primal=True)), the prediction of states and controls."""
+        (PDP_OC_RECORD_PRIMAL): only the X | U part of the record is written - for oc_solve_ms(predict=dict(..., primal=True)), the prediction of states and controls.
+        gauss_newton (PDP_GRAD_GAUSS_NEWTON): the kernel also contracts the sensitivity tiles of its forward sweep with themselves and writes ONE row per trajectory,
+        out["packed_gn"] [B, p + 1 + p p] = gradient | loss | G row-major, G = J'J = sum_t X_t' X_t + U_t' U_t the Gauss-Newton matrix of the sum-of-squares loss (no
+        factor: grad = J'r and G belong together); out["grad"] and out["gn"] [B, p, p] are views of it.  Not together with want_sens, want_riccati, want_predict_record or
+        packed (ValueError).  Beyond the fused kernels' limits the row is filled from the materialised sensitivities (two einsums): one layout either way."""
+        if gauss_newton and (want_sens or want_riccati or want_predict_record or packed):
+            raise ValueError("oc_pdp_grad: gauss_newton=True goes with the plain gradient only - not with want_sens, want_riccati, want_predict_record or packed")
         torch = torch_cuda()
         u, demo_x, demo_u = dev(u), dev(demo_x), dev(demo_u)
         B, T = u.shape[0], u.shape[1]
@@ -530,6 +536,9 @@ class ModelLib:
         if packed:
             pk = buf("packed", (B, p + 1))
             grad, flags = pk[:, :p], flags | 2
+        elif gauss_newton:
+            pk = buf("packed_gn", (B, p + 1 + p * p))
+            grad, flags = pk[:, :p], flags | 16
         else:
             pk = grad = buf("grad", (B, p))
         status = buf("status", (B,), torch.int32)
@@ -555,14 +564,21 @@ class ModelLib:
             # m + p > 16 (beyond the fused kernel's single parameter tile), n > 16 / m > 4 (beyond one tile per matrix: the size-generic LQR
             # kernel takes over - any n, m), or a horizon whose staging exceeds the LDS: the reference's own route, kernel by kernel
             self._warn_materialised(T)
+            if gauss_newton:                                    # the sensitivities through HBM, contracted here: the same row
+                dxdp, dudp = torch.empty((B, T + 1, n, p), dtype=torch.float64, device="cuda"), torch.empty((B, T, m, p), dtype=torch.float64, device="cuda")
             self._oc_pdp_grad_materialised(u, theta, demo_x, demo_u, x0, x, lam, flags, loss, grad, status, dxdp, dudp)
-            if packed:
+            if packed or gauss_newton:
                 pk[:, p].copy_(loss)
+            if gauss_newton:
+                pk[:, p + 1:].copy_((torch.einsum("btip,btiq->bpq", dxdp, dxdp) + torch.einsum("btip,btiq->bpq", dudp, dudp)).reshape(B, p * p))
             rc = 0
         check(rc, "pdp_oc_pdp_grad_batched")
         out = dict(loss=loss, grad=grad, x=x, lam=lam, status=status)
         if packed:
             out["packed"] = pk
+        if gauss_newton:
+            out["packed_gn"] = pk
+            out["gn"] = pk[:, p + 1:].view(B, p, p)
         if want_sens:
             out.update(dxdp=dxdp, dudp=dudp)
         if want_riccati:
