@@ -514,11 +514,9 @@ def compile_core(force=False):
     return _build(os.path.join(LIB_DIR, "libpdp_hip.so"), deps, ["-I", CSRC, os.path.join(CSRC, "pdp_lqr.hip")], force, flags=CORE_FLAGS)
 
 
-def kernel_resources(lib, count_scratch_instructions=False):
-    """Register / scratch usage of every kernel in a built library, read from the gfx950 code object's metadata notes (llvm-objcopy ->
-    clang-offload-bundler -> llvm-readelf --notes): {demangled-ish kernel name: dict(vgpr, agpr, sgpr, spill, scratch, lds)}.  Used by the no-spill
-    test (tests/test_abi_and_host.py) and by bench.py, which prints the dominant kernel's figures into its roofline entry."""
-    import re
+def code_object_text(lib, disassemble=True):
+    """The gfx950 code object of a built library as text: (llvm-readelf --notes, llvm-objdump -d --no-show-raw-insn or "").  The fat binary is cut out of the
+    library with llvm-objcopy and unbundled with clang-offload-bundler; kernel_resources and probes/code_object_diff.py read the two texts."""
     import tempfile
     llvm = os.path.join(os.path.dirname(os.path.dirname(HIPCC)), "lib", "llvm", "bin")
     with tempfile.TemporaryDirectory() as d:
@@ -526,7 +524,16 @@ def kernel_resources(lib, count_scratch_instructions=False):
         _run([os.path.join(llvm, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, lib])
         _run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
         notes = _run([os.path.join(llvm, "llvm-readelf"), "--notes", co])
-        dis = _run([os.path.join(llvm, "llvm-objdump"), "-d", "--no-show-raw-insn", co]) if count_scratch_instructions else ""
+        dis = _run([os.path.join(llvm, "llvm-objdump"), "-d", "--no-show-raw-insn", co]) if disassemble else ""
+    return notes, dis
+
+
+def kernel_resources(lib, count_scratch_instructions=False):
+    """Register / scratch usage of every kernel in a built library, read from the gfx950 code object's metadata notes (llvm-objcopy ->
+    clang-offload-bundler -> llvm-readelf --notes): {demangled-ish kernel name: dict(vgpr, agpr, sgpr, spill, scratch, lds)}.  Used by the no-spill
+    test (tests/test_abi_and_host.py) and by bench.py, which prints the dominant kernel's figures into its roofline entry."""
+    import re
+    notes, dis = code_object_text(lib, disassemble=count_scratch_instructions)
     nscr = {}
     if dis:                                                   # scratch_load / scratch_store instructions per kernel symbol
         cur = None

@@ -9,21 +9,13 @@
 #include "../../include/pdp_hip.h"
 #include "pdp_lqr_kernels.h"
 #include "pdp_lqr_stream_kernels.h"
-#include <cstdlib>
+#include "pdp_launch.h"
 
 using namespace pdp;
 
 namespace {
 
-constexpr int MAX_NT = 4;
-
-inline int launched() {
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    fprintf(stderr, "[pdp_hip] kernel launch failed: %s\n", hipGetErrorString(e));
-    return PDP_E_LAUNCH;
-}
-#define PDP_CLEAR() (void)hipGetLastError()   // parameter tiles: p <= (16 - m) + 16 * (MAX_NT - 1)
+constexpr int MAX_NT = 4;   // parameter tiles: p <= (16 - m) + 16 * (MAX_NT - 1)
 
 // U_t = Ux X + Ue ; X+ = F X + G U.   Generic n <= 16, m <= 16.  A wavefront carries NT tiles of 16 parameter columns (grid.y covers
 // the rest), so F, G and Ux are read once per NT tiles; the operands of step t+1 stream in while step t computes (see RunPtr).
@@ -248,19 +240,6 @@ __global__ void __launch_bounds__(64) sysid_aux_generic_kernel(int B, int T, int
     }
 }
 
-template <int M>
-int launch_lqr(const pdp_lqr_problem& pr, int nt, double* X, double* U, double* Lam, int32_t* status, double* wg, double* wpw, hipStream_t s) {
-    dim3 grid(pr.B), block(64);
-    PDP_CLEAR();
-    switch (nt) {
-        case 1: hipLaunchKernelGGL((lqr_solve_kernel<M, 1>), grid, block, 0, s, pr, X, U, Lam, status, wg, wpw); break;
-        case 2: hipLaunchKernelGGL((lqr_solve_kernel<M, 2>), grid, block, 0, s, pr, X, U, Lam, status, wg, wpw); break;
-        case 3: hipLaunchKernelGGL((lqr_solve_kernel<M, 3>), grid, block, 0, s, pr, X, U, Lam, status, wg, wpw); break;
-        default: hipLaunchKernelGGL((lqr_solve_kernel<M, 4>), grid, block, 0, s, pr, X, U, Lam, status, wg, wpw); break;
-    }
-    return launched();
-}
-
 }  // namespace
 
 extern "C" {
@@ -268,7 +247,7 @@ extern "C" {
 const char* pdp_hip_version(void) { return "pdp_hip 0.1 gfx950"; }
 
 #ifdef PDP_LQS_TIMING      // probe builds only (probes/lqr_stream_timing.py)
-int pdp_lqs_read_stamps(long long* out, void* stream) { hipLaunchKernelGGL(lqs_read_stamps, dim3(1), dim3(64), 0, (hipStream_t)stream, out); return launched(); }
+int pdp_lqs_read_stamps(long long* out, void* stream) { return launch(lqs_read_stamps, dim3(1), dim3(64), 0, (hipStream_t)stream, out); }
 #endif
 
 // gains (+ P, W for the costate output) per stage; systems beyond one tile per matrix whose working set does not fit the LDS add their scratch per trajectory
@@ -286,21 +265,17 @@ int pdp_lqr_solve_batched(const pdp_lqr_problem* prob, double* X, double* U, dou
     const pdp_lqr_problem& pr = *prob;
     if (pr.B <= 0 || pr.T <= 0 || pr.n <= 0 || pr.m <= 0 || pr.p <= 0) return PDP_E_ARG;
     if (!pr.F.ptr || !pr.G.ptr || !pr.Hxx.ptr || !pr.Huu.ptr || !pr.hxx.ptr) return PDP_E_ARG;
+    const hipStream_t s = (hipStream_t)stream;
     if (pr.n > 16 || pr.m > 4) {                   // beyond one tile per matrix: the size-generic kernel (any n, m; p <= 32 per launch - the callers cut more into column blocks)
         if (pr.p > GEN_PMAX) return PDP_E_SIZE;
         if (workspace_bytes < pdp_lqr_workspace_bytes(pr.B, pr.T, pr.n, pr.m, pr.p, Lam != nullptr)) return PDP_E_ARG;
         double* wg = (double*)workspace;
         double* wpw = Lam ? wg + (int64_t)pr.B * pr.T * ((int64_t)pr.n * pr.m + (int64_t)pr.m * pr.p) : nullptr;
         double* wscr = wg + (int64_t)pr.B * pr.T * lqr_stage_doubles(pr.n, pr.m, pr.p, Lam != nullptr);
-        PDP_CLEAR();
-        if (lqr_generic_in_lds(pr.n, pr.m, pr.p)) {
-            const size_t lds = sizeof(double) * lqr_generic_lds_doubles(pr.n, pr.m, pr.p);
-            (void)hipFuncSetAttribute((const void*)lqr_solve_generic_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(lqr_solve_generic_kernel<false>, dim3(pr.B), dim3(64), lds, (hipStream_t)stream, pr, X, U, Lam, status, wg, wpw, (double*)nullptr);
-        } else {
-            hipLaunchKernelGGL(lqr_solve_generic_kernel<true>, dim3(pr.B), dim3(64), 0, (hipStream_t)stream, pr, X, U, Lam, status, wg, wpw, wscr);
-        }
-        return launched();
+        if (lqr_generic_in_lds(pr.n, pr.m, pr.p))
+            return launch(lqr_solve_generic_kernel<false>, dim3(pr.B), dim3(64), sizeof(double) * lqr_generic_lds_doubles(pr.n, pr.m, pr.p), s, pr, X, U, Lam, status, wg,
+                          wpw, (double*)nullptr);
+        return launch(lqr_solve_generic_kernel<true>, dim3(pr.B), dim3(64), 0, s, pr, X, U, Lam, status, wg, wpw, wscr);
     }
     for (const pdp_mat* mt : {&pr.F, &pr.G, &pr.E, &pr.Hxx, &pr.Hxu, &pr.Hxe, &pr.Huu, &pr.Hue})       // per-lane byte strides are 32-bit
         if (mt->tstride < 0 || mt->tstride > (INT32_MAX >> 3)) return PDP_E_SIZE;
@@ -310,89 +285,46 @@ int pdp_lqr_solve_batched(const pdp_lqr_problem* prob, double* X, double* U, dou
     if (workspace_bytes < pdp_lqr_workspace_bytes(pr.B, pr.T, pr.n, pr.m, pr.p, Lam != nullptr)) return PDP_E_ARG;
     double* wg = (double*)workspace;
     double* wpw = Lam ? wg + (int64_t)pr.B * pr.T * (pr.n * pr.m + pr.m * pr.p) : nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    if (pr.n <= 4 && pr.m + pr.p <= 16) {          // small systems: four trajectories per wavefront, block-diagonal in the tile
-        const dim3 grid((pr.B + 3) / 4), block(64);
-        PDP_CLEAR();
-        switch (pr.m) {
-            case 1: hipLaunchKernelGGL((lqr_solve_small_kernel<1>), grid, block, 0, s, pr, X, U, Lam, status, wg, wpw); break;
-            case 2: hipLaunchKernelGGL((lqr_solve_small_kernel<2>), grid, block, 0, s, pr, X, U, Lam, status, wg, wpw); break;
-            case 3: hipLaunchKernelGGL((lqr_solve_small_kernel<3>), grid, block, 0, s, pr, X, U, Lam, status, wg, wpw); break;
-            default: hipLaunchKernelGGL((lqr_solve_small_kernel<4>), grid, block, 0, s, pr, X, U, Lam, status, wg, wpw); break;
-        }
-        return launched();
-    }
     // dense matrices from HBM, one parameter tile: the runner / streamer kernel (pdp_lqr_stream_kernels.h); PDP_LQR_VARIANT=1 keeps the one-wave kernel
-    static const int variant = [] { const char* e = std::getenv("PDP_LQR_VARIANT"); return e ? std::atoi(e) : 2; }();
-    if (variant == 2 && nt == 1 && lqs_ok(pr.n, pr.m, pr.p, Lam != nullptr)) {
-        const dim3 grid((pr.B + 3) / 4), block(512);
-        PDP_CLEAR();
-        auto go = [&](auto kern) {
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            hipLaunchKernelGGL(kern, grid, block, 160 * 1024, s, pr, X, U, Lam, status, wg, wpw);
-        };
-        const bool nl12 = lqs_lines(pr.n, pr.m, pr.p, Lam != nullptr) <= 12;      // lines per ring slot: 12 (C3 sizes and smaller) or 16
-        switch (pr.m) {
-            case 1: if (nl12) go(lqr_solve_stream_kernel<1, 12>); else go(lqr_solve_stream_kernel<1, 16>); break;
-            case 2: if (nl12) go(lqr_solve_stream_kernel<2, 12>); else go(lqr_solve_stream_kernel<2, 16>); break;
-            case 3: if (nl12) go(lqr_solve_stream_kernel<3, 12>); else go(lqr_solve_stream_kernel<3, 16>); break;
-            default: if (nl12) go(lqr_solve_stream_kernel<4, 12>); else go(lqr_solve_stream_kernel<4, 16>); break;
-        }
-        return launched();
-    }
-    switch (pr.m) {
-        case 1: return launch_lqr<1>(pr, nt, X, U, Lam, status, wg, wpw, s);
-        case 2: return launch_lqr<2>(pr, nt, X, U, Lam, status, wg, wpw, s);
-        case 3: return launch_lqr<3>(pr, nt, X, U, Lam, status, wg, wpw, s);
-        default: return launch_lqr<4>(pr, nt, X, U, Lam, status, wg, wpw, s);
-    }
+    static const int variant = env_int("PDP_LQR_VARIANT", 2);
+    return with_int<1, 2, 3, 4>(pr.m, [&](auto M) {        // (m <= 4 here)
+        if (pr.n <= 4 && pr.m + pr.p <= 16)          // small systems: four trajectories per wavefront, block-diagonal in the tile
+            return launch(lqr_solve_small_kernel<M()>, dim3((pr.B + 3) / 4), dim3(64), 0, s, pr, X, U, Lam, status, wg, wpw);
+        if (variant == 2 && nt == 1 && lqs_ok(pr.n, pr.m, pr.p, Lam != nullptr))
+            return with_int<12, 16>(lqs_lines(pr.n, pr.m, pr.p, Lam != nullptr) <= 12 ? 12 : 16, [&](auto NL) {      // lines per ring slot: 12 (C3 sizes and smaller) or 16
+                return launch(lqr_solve_stream_kernel<M(), NL()>, dim3((pr.B + 3) / 4), dim3(512), 160 * 1024, s, pr, X, U, Lam, status, wg, wpw);
+            });
+        return with_int<1, 2, 3, 4>(nt, [&](auto NT) { return launch(lqr_solve_kernel<M(), NT()>, dim3(pr.B), dim3(64), 0, s, pr, X, U, Lam, status, wg, wpw); });
+    });
 }
 
 int pdp_cp_aux_integrate_batched(int B, int T, int n, int m, int p, const double* F, const double* G, const double* Ux, const double* Ue,
                                  const double* X0, double* X, double* U, void* stream) {
     if (B <= 0 || T <= 0 || n <= 0 || m <= 0 || p <= 0 || !F || !G || !Ux || !Ue || !X || !U) return PDP_E_ARG;
-    PDP_CLEAR();
-    if (n > 16 || m > 16) {         // beyond one tile per matrix: lane per (trajectory, column), any size
-        hipLaunchKernelGGL(cp_aux_generic_kernel, dim3((unsigned)(((int64_t)B * p + 63) / 64)), dim3(64), 0, (hipStream_t)stream, B, T, n, m, p, F, G, Ux, Ue, X0, X, U);
-        return launched();
-    }
+    const hipStream_t s = (hipStream_t)stream;
+    if (n > 16 || m > 16)           // beyond one tile per matrix: lane per (trajectory, column), any size
+        return launch(cp_aux_generic_kernel, dim3((unsigned)(((int64_t)B * p + 63) / 64)), dim3(64), 0, s, B, T, n, m, p, F, G, Ux, Ue, X0, X, U);
     const int ntile = (p + 15) / 16;
-    if (ntile == 1) hipLaunchKernelGGL(cp_aux_kernel<1>, dim3(B, 1), dim3(64), 0, (hipStream_t)stream, B, T, n, m, p, F, G, Ux, Ue, X0, X, U);
-    else hipLaunchKernelGGL(cp_aux_kernel<2>, dim3(B, (ntile + 1) / 2), dim3(64), 0, (hipStream_t)stream, B, T, n, m, p, F, G, Ux, Ue, X0, X, U);
-    return launched();
+    return with_int<1, 2>(ntile, [&](auto NT) { return launch(cp_aux_kernel<NT()>, dim3(B, (ntile + NT() - 1) / NT()), dim3(64), 0, s, B, T, n, m, p, F, G, Ux, Ue, X0, X, U); });
 }
 
 int pdp_cp_grad_contract_batched(int B, int T, int n, int m, int p, const double* dcx, const double* dcu, const double* dhx, const double* X,
                                  const double* U, double* grad, void* stream) {
     if (B <= 0 || T <= 0 || n <= 0 || m <= 0 || p <= 0 || !dcx || !dcu || !dhx || !X || !U || !grad) return PDP_E_ARG;
-    PDP_CLEAR();
-    hipLaunchKernelGGL(cp_grad_contract_kernel, dim3((p + 63) / 64, B), dim3(64), 0, (hipStream_t)stream, B, T, n, m, p, dcx, dcu, dhx, X, U, grad);
-    return launched();
+    return launch(cp_grad_contract_kernel, dim3((p + 63) / 64, B), dim3(64), 0, (hipStream_t)stream, B, T, n, m, p, dcx, dcu, dhx, X, U, grad);
 }
 
 int pdp_gd_update_batched(int B, int p, const double* loss, const double* grad, int grad_bstride, const int32_t* status, const int32_t* converged, const int32_t* iterations,
                           double lr, double* theta, double* dtheta, double* loss_trace, double* parameter_trace, int64_t trace_len, int64_t* counters, void* stream) {
     if (B <= 0 || p <= 0 || !loss || !grad || grad_bstride < p || !theta || !dtheta || !counters) return PDP_E_ARG;
-    PDP_CLEAR();
-    if (p + 1 > 1024) {
-        hipLaunchKernelGGL(gd_update_wide_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, B, p, loss, grad, grad_bstride, status, converged, iterations, lr, theta, dtheta,
-                           loss_trace, parameter_trace, (long long)trace_len, (long long*)counters);
-        return launched();
-    }
-    hipLaunchKernelGGL(gd_update_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, B, p, loss, grad, grad_bstride, status, converged, iterations, lr, theta, dtheta, loss_trace,
-                       parameter_trace, (long long)trace_len, (long long*)counters);
-    return launched();
+    return launch(p + 1 > 1024 ? gd_update_wide_kernel : gd_update_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, B, p, loss, grad, grad_bstride, status, converged,
+                  iterations, lr, theta, dtheta, loss_trace, parameter_trace, (long long)trace_len, (long long*)counters);
 }
 
 int pdp_sysid_aux_integrate_batched(int B, int T, int n, int p, const double* F, const double* E, const double* X0, double* X, void* stream) {
     if (B <= 0 || T <= 0 || n <= 0 || p <= 0 || !F || !E || !X) return PDP_E_ARG;
-    PDP_CLEAR();
-    if (n > 16) {
-        hipLaunchKernelGGL(sysid_aux_generic_kernel, dim3((unsigned)(((int64_t)B * p + 63) / 64)), dim3(64), 0, (hipStream_t)stream, B, T, n, p, F, E, X0, X);
-        return launched();
-    }
-    hipLaunchKernelGGL(sysid_aux_kernel, dim3(B, (p + 15) / 16), dim3(64), 0, (hipStream_t)stream, B, T, n, p, F, E, X0, X);
-    return launched();
+    if (n > 16) return launch(sysid_aux_generic_kernel, dim3((unsigned)(((int64_t)B * p + 63) / 64)), dim3(64), 0, (hipStream_t)stream, B, T, n, p, F, E, X0, X);
+    return launch(sysid_aux_kernel, dim3(B, (p + 15) / 16), dim3(64), 0, (hipStream_t)stream, B, T, n, p, F, E, X0, X);
 }
 
 }  // extern "C"

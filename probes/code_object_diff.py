@@ -1,0 +1,67 @@
+"""Are the gfx950 code objects of two builds the same kernels?  python probes/code_object_diff.py <libdir A> <libdir B>   (no GPU needed)
+
+For every library (*.so) of the two directories - e.g. pontryagin-differentiable-programming_amd/lib of a checkout of the parent commit and of the working tree,
+both after __graft_entry__.build() - the code object is unbundled (codegen.code_object_text) and compared:
+  (a) the set of symbols in the disassembly (kernels and device functions) is the same;
+  (b) per symbol the instruction text is the same.  The trailing `// address: encoding` comment of a line is dropped (a kernel may sit elsewhere in the code object
+      when the host code instantiates the templates in another order), and for the same reason the literal of the s_add_u32 / s_addc_u32 pair directly behind an
+      s_getpc_b64 is masked: a pc-relative offset to constant data.  Every other operand of every instruction must agree;
+  (c) per kernel the metadata entry (registers, spills, scratch, LDS, kernel arguments) is the same text.
+Exit status 1 on any difference.  What a host-only change of csrc/*.hip is checked with: profiles/launch_layer_code_object_diff.txt."""
+import glob
+import os
+import re
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from pdp_amd import codegen  # noqa: E402
+
+
+def symbols(dis):
+    """{symbol: [instruction text]} with the comments dropped and the pc-relative literals masked; how many literals were masked"""
+    out, cur, after_getpc, masked = {}, None, 0, 0
+    for ln in dis.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(\S+)>:", ln)
+        if m:
+            cur, after_getpc = out.setdefault(m.group(1), []), 0
+            continue
+        ins = ln.split("//")[0].strip()
+        if cur is None or not ins:
+            continue
+        if after_getpc and re.match(r"s_addc?_u32 ", ins):
+            ins, after_getpc, masked = re.sub(r",\s*\S+$", ", <pcrel>", ins), after_getpc - 1, masked + 1
+        else:
+            after_getpc = 2 if ins.startswith("s_getpc_b64") else 0
+        cur.append(ins)
+    return out, masked
+
+
+def metadata(notes):
+    return {re.search(r"\.name:\s*(\S+)", ent).group(1): ent for ent in notes.split("- .agpr_count:")[1:]}
+
+
+def main(dir_a, dir_b):
+    names = [sorted(os.path.basename(p) for p in glob.glob(os.path.join(d, "*.so"))) for d in (dir_a, dir_b)]
+    bad = int(names[0] != names[1])
+    if bad:
+        print("DIFFERENT sets of libraries: %s" % sorted(set(names[0]) ^ set(names[1])))
+    for lib in sorted(set(names[0]) & set(names[1])):
+        (na, da), (nb, db) = (codegen.code_object_text(os.path.join(d, lib)) for d in (dir_a, dir_b))
+        (sa, masked), (sb, _) = symbols(da), symbols(db)
+        ma, mb = metadata(na), metadata(nb)
+        moved = list(sa) != list(sb)
+        diffs = ["symbol set: %s" % sorted(set(sa) ^ set(sb))] if set(sa) != set(sb) else []
+        diffs += ["instructions of %s" % s for s in sa if s in sb and sa[s] != sb[s]]
+        diffs += ["kernel set of the metadata: %s" % sorted(set(ma) ^ set(mb))] if set(ma) != set(mb) else []
+        diffs += ["metadata of %s" % s for s in ma if s in mb and ma[s] != mb[s]]
+        print("%-52s %3d kernels %4d symbols %8d instructions %5d pc-relative literals masked  order %s  %s"
+              % (lib, len(ma), len(sa), sum(len(v) for v in sa.values()), masked, "moved" if moved else "same ", "DIFFERENT" if diffs else "identical"))
+        for d in diffs:
+            print("    " + d)
+        bad += len(diffs)
+    print("code objects %s" % ("DIFFER" if bad else "identical: same symbols, same instructions, same metadata in every library"))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1], sys.argv[2]))
