@@ -18,6 +18,11 @@ Examples/IRL/cartpole/generate_demos.py:38-43) through --demos.  Results are sav
 (PDP_GRAD_GAUSS_NEWTON), and a Levenberg-Marquardt loop (pdp_amd.irl.LMLoop; --iters bounds its evaluations) takes a handful of steps where gradient descent takes thousands:
 
     python examples/irl_pdp.py --system cartpole --method lm
+
+Demonstrations with gaps (--method lm): --every K keeps the states at t = K, 2K, ... <= T, --observe i,j,... the listed state components, --no-controls no control; every
+other entry becomes NaN = not observed (PDP_GRAD_SKIP_MISSING), and the solves start from the demonstrations' own first states:
+
+    python examples/irl_pdp.py --system cartpole --method lm --every 10 --observe 0,1 --no-controls
 """
 import argparse
 import os
@@ -56,10 +61,32 @@ def reference_last_loss(system):
     return int(z["K"]), float(z["loss_next"][-1])
 
 
+def mask_demos(demo_x, demo_u, every=None, observe=None, no_controls=False):
+    """the demonstrations with every entry that is not observed set to NaN: states at t = every, 2 every, ... <= T (None: every step), components `observe` (None: all),
+    controls all or none"""
+    T, n = demo_u.shape[1], demo_x.shape[2]
+    steps = np.arange(T + 1) if every is None else np.arange(every, T + 1, every)
+    comps = np.arange(n) if observe is None else np.asarray(observe, dtype=int)
+    mx = np.full(demo_x.shape, np.nan)
+    mx[:, steps[:, None], comps[None, :]] = demo_x[:, steps[:, None], comps[None, :]]
+    return mx, (np.full(demo_u.shape, np.nan) if no_controls else demo_u.copy())
+
+
 def run_lm(a, oc, demo_x, demo_u, theta, true_parameter):
     from pdp_amd.irl import LMLoop
     t0 = time.time()
-    loop = LMLoop.for_irl(oc.model(), demo_x, demo_u, theta)
+    sparse = a.every is not None or a.observe is not None or a.no_controls
+    if sparse:
+        assert a.every is None or a.every >= 1, "--every: a positive number of steps"
+        observe = None if a.observe is None else [int(v) for v in a.observe.split(",")]
+        assert observe is None or all(0 <= i < demo_x.shape[2] for i in observe), "--observe: state components 0 .. %d" % (demo_x.shape[2] - 1)
+        ini_state = demo_x[:, 0].copy()
+        demo_x, demo_u = mask_demos(demo_x, demo_u, a.every, observe, a.no_controls)
+        print("observed: %d of %d state entries, %d of %d control entries per demonstration" % (
+            int((~np.isnan(demo_x[0])).sum()), demo_x[0].size, int((~np.isnan(demo_u[0])).sum()), demo_u[0].size))
+        loop = LMLoop.for_irl(oc.model(), demo_x, demo_u, theta, ini_state=ini_state, skip_missing=True)
+    else:
+        loop = LMLoop.for_irl(oc.model(), demo_x, demo_u, theta)
     r = loop.run(max_evals=a.iters, loss_tol=a.loss_tol)
     for k, (loss, th, lam) in enumerate(zip(r["loss_trace"], r["parameter_trace"], r["lambda_trace"])):
         print("accepted %3d  loss %.6e  |theta - theta*| %.4e  next damping %.1e" % (k, loss, np.abs(th - true_parameter).max(), lam))
@@ -93,6 +120,9 @@ def main():
                     help="gd: the reference's gradient descent (default); lm: Levenberg-Marquardt on the Gauss-Newton matrix the fused kernel returns "
                          "(--iters = most evaluations, --lr unused)")
     ap.add_argument("--loss-tol", type=float, default=1e-16, help="--method lm: stop at this mean loss")
+    ap.add_argument("--every", type=int, default=None, help="--method lm: only the states at t = K, 2K, ... <= T are observed (default: every step)")
+    ap.add_argument("--observe", default=None, help="--method lm: comma-separated state components that are observed (default: all)")
+    ap.add_argument("--no-controls", action="store_true", help="--method lm: no control is observed")
     ap.add_argument("--demos", default=None, help="<name>_demos.mat in the reference's schema (default: the stored demos of --system)")
     a = ap.parse_args()
 
@@ -113,6 +143,7 @@ def main():
     if a.init is not None:
         theta = np.load(a.init).astype(float).reshape(-1) if a.init.endswith(".npy") else np.array([float(v) for v in a.init.split(",")])
         assert theta.size == true_parameter.size, "--init: %d values for %d parameters" % (theta.size, true_parameter.size)
+    assert a.method == "lm" or (a.every is None and a.observe is None and not a.no_controls), "--every / --observe / --no-controls go with --method lm"
     if a.method == "lm":
         return run_lm(a, oc, demo_x, demo_u, theta, true_parameter)
     loss_trace, parameter_trace = [], []

@@ -309,6 +309,19 @@ int pdp_oc_solve_ms_batched(int B, int T, const double* x0, const double* theta,
                               loss, x, lam, status, PDP_OC_GIVEN_TRAJ and theta_bstride as in the default mode.  Rows sum over a batch (and over ranks) like PDP_OC_PACKED rows.
                               Plain gradient of the demonstration loss only: with PDP_OC_COTANGENT (a general loss needs its own Hessian), with PDP_OC_PACKED (one row layout per
                               call) or with any of dxdp, dudp, sens->riccati, sens->predict_record the call returns PDP_E_ARG before anything is launched */
+#define PDP_GRAD_SKIP_MISSING 32 /* (a bit of the same `flags`) demonstrations with gaps: an entry of demo_x [B][T+1][n] or demo_u [B][T][m] that is NaN is NOT OBSERVED - its residual is
+                              dropped from loss, its term from grad and, with PDP_GRAD_GAUSS_NEWTON, its Jacobian row from G.  With the 0/1 masks wx[t][i], wu[t][i] (0 where the
+                              demonstration entry is NaN):
+                                  loss       = sum wx (x - x_demo)^2 + sum wu (u - u_demo)^2
+                                  grad[j]    = sum_{t<=T} sum_i wx[t][i] (x - x_demo)[t][i] X_t[i][j] + sum_{t<T} sum_i wu[t][i] (u - u_demo)[t][i] U_t[i][j]
+                                  G[i][j]    = sum_{t<=T} sum_k wx[t][k] X_t[k][i] X_t[k][j] + sum_{t<T} sum_k wu[t][k] U_t[k][i] U_t[k][j]
+                              The absent terms are selected away, never multiplied by 0.  Only NaN marks an absence: +-inf propagates as without the flag, and without the flag a NaN
+                              behaves as it always did.  A missing entry sets no status bit; a trajectory with nothing observed yields exact zeros in loss, grad and G.  G stays
+                              symmetric to the bit (both operands of every product carry the mask).  x0 is an argument of its own: demo_x[b][0] may be all NaN.  x, lam, status,
+                              PDP_OC_GIVEN_TRAJ, theta_bstride and the row layouts ([B][p], [B][p + 1] with PDP_OC_PACKED, [B][p + 1 + p p] with PDP_GRAD_GAUSS_NEWTON) are unchanged.
+                              An observed entry whose own state or control is NaN leaves a NaN in loss and drops out of grad and G; status reports such a trajectory as before.
+                              Not with PDP_OC_COTANGENT (cotangents are the caller's numbers: a NaN there is an error, not an absence) and not with any of dxdp, dudp,
+                              sens->riccati, sens->predict_record: PDP_E_ARG before anything is launched */
 int64_t pdp_oc_pdp_workspace_bytes(int B, int T);
 int pdp_oc_pdp_grad_batched(int B, int T, int flags, const double* x0, const double* u, const double* theta,
                             int theta_bstride, const double* demo_x, const double* demo_u, double* x, double* lam,

@@ -184,19 +184,23 @@ class OCSys(_CasadiFrontEnd):
         return self.model().oc_auxsys(state_traj, u, costate_traj, self._theta(auxvar_value, u.shape[0]))
 
     def pdp_grad_batch(self, control_traj, auxvar_value, demo_state, demo_control, ini_state=None, state_traj=None, costate_traj=None,
-                       want_sens=False, buffers=None, want_riccati=False, want_predict_record=False, want_gauss_newton=False):
+                       want_sens=False, buffers=None, want_riccati=False, want_predict_record=False, want_gauss_newton=False, skip_missing=False):
         """Fused forward + Riccati + PDP gradient for a batch (the body of the IRL drivers' demo loop,
         Examples/IRL/cartpole/cartpole_PDP.py:45-74): returns dict(loss [B], grad [B,p], x, lam, status[, dxdp, dudp][, riccati]).
         want_predict_record (or want_sens + want_riccati, the same in fp64): everything the next OC solve's predicted start needs
         (ocsolver.solve_batch(..., predict=dict(dtheta=..., record=out["predict_record"]))).
         want_gauss_newton (plain gradient only): also out["gn"] [B,p,p], the Gauss-Newton matrix J'J of the sum-of-squares loss, and out["packed_gn"] [B, p+1+p*p] =
-        gradient | loss | G, the row irl.LMLoop and parallel.mean_loss_grad_gn reduce (PDP_GRAD_GAUSS_NEWTON, include/pdp_hip.h)."""
+        gradient | loss | G, the row irl.LMLoop and parallel.mean_loss_grad_gn reduce (PDP_GRAD_GAUSS_NEWTON, include/pdp_hip.h).
+        skip_missing (with the plain gradient or want_gauss_newton): a NaN in demo_state / demo_control is an entry that was not observed and is left out of loss,
+        gradient and G (PDP_GRAD_SKIP_MISSING); demo_state[:, 0] may be all NaN when ini_state is given."""
+        if skip_missing and (want_sens or want_riccati or want_predict_record):
+            raise ValueError("pdp_grad_batch: skip_missing goes with the plain gradient or want_gauss_newton only")
         if want_gauss_newton and (want_sens or want_riccati or want_predict_record):
             raise ValueError("pdp_grad_batch: want_gauss_newton goes with the plain gradient only")
         u = runtime.dev(control_traj)
         return self.model().oc_pdp_grad(u, self._theta(auxvar_value, u.shape[0]), demo_state, demo_control, x0=ini_state, x=state_traj,
                                         lam=costate_traj, want_sens=want_sens, buffers=buffers, want_riccati=want_riccati, want_predict_record=want_predict_record,
-                                        gauss_newton=want_gauss_newton)
+                                        gauss_newton=want_gauss_newton, skip_missing=skip_missing)
 
     def pdp_vjp_batch(self, control_traj, auxvar_value, grad_state, grad_control, ini_state=None, state_traj=None, costate_traj=None, buffers=None):
         """The gradient of ANY scalar loss L(state, control) through the OC solution, for a batch: grad_state [B,T+1,n] = dL/dstate and grad_control [B,T,m] = dL/dcontrol

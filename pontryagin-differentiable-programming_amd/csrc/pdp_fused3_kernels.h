@@ -96,6 +96,11 @@ PDP_DEV BufMap f3_store_map(int R, int C, int ld, int coff, int lane) {
 // MODE = PDP_FUSED_GN (PDP_GRAD_GAUSS_NEWTON; plain gradient only): the default unit, and in the forward sweep one more accumulator tile Gn += X_t' X_t + U_t' U_t - the
 // Gauss-Newton matrix J'J of the sum-of-squares loss, whose parameter block is rows and columns M .. M + NP - 1 of the tile.  grad is the packed row
 // [B][NP + 1 + NP NP] = gradient | loss | G row-major.  G[i][j] and G[j][i] are the same products in the same order: symmetric to the bit.
+// MODE = PDP_FUSED_MISS / PDP_FUSED_GN_MISS (PDP_GRAD_SKIP_MISSING on the plain / the Gauss-Newton unit): a NaN in demo_x / demo_u is an entry that was not observed.  No
+// change of the LDS layout: the demonstration's NaN, left in the DLX / DLU slot in place of the residual, IS the mark (the evaluator adds nothing to lsum for it), and the runner, which holds the residual
+// tiles DX, DU - the residual of a row broadcast over its columns - element-aligned with the sensitivity tiles Xc, U2, SELECTS 0.0 for both wherever the residual is NaN
+// (a compare and a select per tile register; never a product with 0: 0 inf must not appear) before it contracts them.  Both operands of every G product carry the same
+// row mask: G stays symmetric to the bit.  The terminal row goes the same way through dT / dlT.  tile_finite keeps looking at the unmasked sensitivities.
 template <class Mdl, int TPW = 4, int MODE = PDP_FUSED_PLAIN>
 __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, int flags, const double* __restrict__ x0, const double* __restrict__ u,
                                                             const double* __restrict__ theta, int tb, const double* __restrict__ demo_x,
@@ -112,8 +117,10 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
     // the wave index is uniform over the wave - said explicitly, or every pointer derived from it (trajectory, workspace, LDS slice) would be
     // carried per lane and every global access would pay 64-bit VALU address arithmetic
     static_assert(TPW == 1 || TPW == 2 || TPW == 4, "trajectories per workgroup");
-    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT || MODE == PDP_FUSED_GN, "instantiation");
-    constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT, GN = MODE == PDP_FUSED_GN;
+    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT || MODE == PDP_FUSED_GN || MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS,
+                  "instantiation");
+    constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT, GN = MODE == PDP_FUSED_GN || MODE == PDP_FUSED_GN_MISS;
+    constexpr bool MISS = MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, slot = wid & (TPW - 1);
     const bool runner = wid < TPW;
     const int b = blockIdx.x * TPW + slot;
@@ -356,7 +363,9 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         double acc = 0.0;
         [[maybe_unused]] double lsum = 0.0;
         double dT;                                              // terminal residual (COT: terminal cotangent), requested ahead of the loops that hide its latency
+        [[maybe_unused]] bool obsT = true;                      // MISS: the terminal entry of this lane was observed (the demonstration's entry is not NaN)
         if constexpr (COT) dT = lane < NX ? dxb[T * NX + lane] : 0.0;
+        else if constexpr (MISS) { const double dd = lane < NX ? dxb[T * NX + lane] : 0.0; obsT = dd == dd; dT = lane < NX ? (obsT ? xb[T * NX + lane] - dd : dd) : 0.0; }
         else dT = lane < NX ? xb[T * NX + lane] - dxb[T * NX + lane] : 0.0;
         d4 X2 = z;
         [[maybe_unused]] d4 Gn = z;                             // GN: sum_t X_t' X_t + U_t' U_t
@@ -413,8 +422,17 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                     d4 DU = row_read<1>(rDU, imm);
                     d4 U2;
                     riccati_forward(KTc, kc, FT, GT, E2, Xc, U2, Xn);
+                    if constexpr (MISS) {                          // a NaN residual marks a row that was not observed: residual and sensitivity row are selected away
+                        d4 Xm, Um = z;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { const bool obs = DX[r] == DX[r]; Xm[r] = obs ? Xc[r] : 0.0; DX[r] = obs ? DX[r] : 0.0; }
+                        { const bool obs = DU[0] == DU[0]; Um[0] = obs ? U2[0] : 0.0; DU[0] = obs ? DU[0] : 0.0; }
+                        if constexpr (GN) { Gn = mma_tn(Xm, Xm, Gn); Gn = mma_tn_r0(Um, Um, Gn); }
+                        acc += DX[0] * Xm[0] + DX[1] * Xm[1] + DX[2] * Xm[2] + DX[3] * Xm[3] + DU[0] * Um[0];
+                    } else {
                     if constexpr (GN) { Gn = mma_tn(Xc, Xc, Gn); Gn = mma_tn_r0(U2, U2, Gn); }
                     acc += DX[0] * Xc[0] + DX[1] * Xc[1] + DX[2] * Xc[2] + DX[3] * Xc[3] + DU[0] * U2[0];
+                    }
                     if constexpr (RIC) {
                         if (dxdp || dudp) {
                             buf_store(rsSX, (unsigned)(t * NX * NP) * 8u, mSX, Xc);
@@ -467,13 +485,28 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         F3_STAMP();
         // terminal term (x_T - xd_T)' X_T   (cartpole_PDP.py:74)
         wave_lds_sync();
-        if (lane < NX) { dlT[lane] = dT; if constexpr (!COT) lsum += dT * dT; }
+        if (lane < NX) {
+            dlT[lane] = dT;
+            if constexpr (MISS) lsum += obsT ? dT * dT : 0.0;
+            else if constexpr (!COT) lsum += dT * dT;
+        }
         wave_lds_sync();
+        [[maybe_unused]] d4 X2m = z;                            // MISS: X_T with the rows that were not observed selected away
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { int row = tile_row(lane, r); if (row < NX) acc += dlT[row] * X2[r]; }
+        for (int r = 0; r < 4; ++r) {
+            int row = tile_row(lane, r);
+            if constexpr (MISS) {
+                if (row < NX) { const double d = dlT[row]; const bool obs = d == d; X2m[r] = obs ? X2[r] : 0.0; acc += (obs ? d : 0.0) * X2m[r]; }
+            } else {
+            if (row < NX) acc += dlT[row] * X2[r];
+            }
+        }
         if (dxdp) store_dense(dxdp + ((int64_t)b * (T + 1) + T) * NX * NP, NX, NP, NP, 0, M, lane, X2);
         finite = finite && tile_finite(X2);
-        if constexpr (GN) Gn = mma_tn(X2, X2, Gn);              // X_T
+        if constexpr (GN) {                                     // X_T
+            if constexpr (MISS) Gn = mma_tn(X2m, X2m, Gn);
+            else Gn = mma_tn(X2, X2, Gn);
+        }
         acc = sum_over_rowgroups(acc);
         if constexpr (COT) {                                    // no loss, no packed row (PDP_E_ARG at the entry point), nothing to wait for: every chunk has been consumed
             if (lane >= M && lane < M + NP) grad[(int64_t)b * NP + (lane - M)] = acc;
@@ -639,12 +672,14 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                     for (int i = 0; i < NX; ++i) {
                         xc[i] = xb[t * NX + i];
                         if constexpr (COT) row[DLX + i] = t > 0 ? dxb[t * NX + i] : 0.0;       // gx_0 multiplies X_0 = 0: not loaded
+                        else if constexpr (MISS) { const double dd = dxb[t * NX + i], d = xc[i] - dd; row[DLX + i] = dd == dd ? d : dd; lsum += dd == dd ? d * d : 0.0; }
                         else { double d = xc[i] - dxb[t * NX + i]; row[DLX + i] = d; lsum += d * d; }
                     }
 #pragma unroll
                     for (int i = 0; i < NU; ++i) {
                         uc[i] = ub[t * NU + i];
                         if constexpr (COT) row[DLU + i] = dub[t * NU + i];
+                        else if constexpr (MISS) { const double dd = dub[t * NU + i], d = uc[i] - dd; row[DLU + i] = dd == dd ? d : dd; lsum += dd == dd ? d * d : 0.0; }
                         else { double d = uc[i] - dub[t * NU + i]; row[DLU + i] = d; lsum += d * d; }
                     }
                     PackedSink s{row};

@@ -105,15 +105,19 @@ int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const dou
     if constexpr (fused_oc_ok<Mdl>()) {
         const bool cot = (flags & PDP_OC_COTANGENT) != 0;   // dx, du carry the cotangents of a caller's loss: no loss output, plain gradient only
         const bool gn = (flags & PDP_GRAD_GAUSS_NEWTON) != 0;   // grad is the packed row gradient | loss | G = J'J: plain gradient of the demonstration loss only
+        const bool miss = (flags & PDP_GRAD_SKIP_MISSING) != 0;   // a NaN in dx / du is an entry that was not observed: plain or Gauss-Newton unit, no sensitivity output
         const bool records = ric || prec, sens = records || dxdp || dudp;          // the Riccati / prediction records; any sensitivity output
         if (B <= 0 || T <= 0 || !u || !th || !dx || !du || !x || !lam || (!loss && !cot) || !grad || !ws) return PDP_E_ARG;
         if ((cot || gn) && (sens || (flags & PDP_OC_PACKED) || (cot && gn))) return PDP_E_ARG;
+        if (miss && (cot || sens)) return PDP_E_ARG;
         if (!(flags & PDP_OC_GIVEN_TRAJ) && !x0) return PDP_E_ARG;
         if (wsb < oc_ws_bytes<Mdl>(B, T)) return PDP_E_ARG;
         const size_t lds = fused_lds_bytes<Mdl>(T);
         if (lds > 160 * 1024) return PDP_E_SIZE;
         // the instantiation (a kernel's MODE): with records - and, fused3 only, with any sensitivity output - the one that writes them with buffer stores
-        auto mode = [&](bool rec) { return rec ? PDP_FUSED_RIC : (cot ? PDP_FUSED_COT : (gn ? PDP_FUSED_GN : PDP_FUSED_PLAIN)); };
+        auto mode = [&](bool rec) {
+            return rec ? PDP_FUSED_RIC : (cot ? PDP_FUSED_COT : (gn ? (miss ? PDP_FUSED_GN_MISS : PDP_FUSED_GN) : (miss ? PDP_FUSED_MISS : PDP_FUSED_PLAIN)));
+        };
         auto run = [&](auto kern, int wgs, int threads, size_t lds_bytes) {
             return launch(kern, dim3(wgs), dim3(threads), lds_bytes, S(st), B, T, flags, x0, u, th, tb, dx, du, x, lam, loss, grad, dxdp, dudp, status, (double*)ws, ric, prec);
         };
@@ -125,12 +129,12 @@ int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const dou
             if (variant == 3 && fused3_ok<Mdl>(T)) {
                 static const int tpw_env = env_int("PDP_FUSED_TPW", 0);          // (overrides the batch rule)
                 const int tpw = tpw_env ? tpw_env : traj_per_workgroup(B, device_cu_count(), 4);
-                return with_int<PDP_FUSED_RIC, PDP_FUSED_COT, PDP_FUSED_GN, PDP_FUSED_PLAIN>(mode(sens), [&](auto MODE) {
+                return with_int<PDP_FUSED_RIC, PDP_FUSED_COT, PDP_FUSED_GN, PDP_FUSED_MISS, PDP_FUSED_GN_MISS, PDP_FUSED_PLAIN>(mode(sens), [&](auto MODE) {
                     return with_int<1, 2, 4>(tpw, [&](auto K) { return run(oc_pdp_fused3_kernel<Mdl, K(), MODE()>, (B + K() - 1) / K(), 128 * K(), K() * 40 * 1024); });
                 });
             }
         }
-        return with_int<PDP_FUSED_COT, PDP_FUSED_GN, PDP_FUSED_RIC, PDP_FUSED_PLAIN>(mode(records), [&](auto MODE) { return run(oc_pdp_fused_kernel<Mdl, MODE()>, B, 64, lds); });
+        return with_int<PDP_FUSED_COT, PDP_FUSED_GN, PDP_FUSED_RIC, PDP_FUSED_MISS, PDP_FUSED_GN_MISS, PDP_FUSED_PLAIN>(mode(records), [&](auto MODE) { return run(oc_pdp_fused_kernel<Mdl, MODE()>, B, 64, lds); });
     } else { return Mdl::KIND == PDP_KIND_OC ? PDP_E_SIZE : PDP_E_MODE; }
 }
 

@@ -577,10 +577,15 @@ __host__ __device__ inline size_t fused_lds_bytes(int T) {
 //                    x - x_demo, u - u_demo in the contraction: grad = sum_t gx_t' X_t + gu_t' U_t.  No loss is formed (`loss` may be NULL); gx[b][0] is never loaded (X_0 = 0).
 //   PDP_FUSED_GN     PDP_GRAD_GAUSS_NEWTON: PDP_FUSED_PLAIN plus one accumulator tile in the forward sweep, Gn += X_t' X_t + U_t' U_t (the X_t, U_t tiles are in registers
 //                    there): the Gauss-Newton matrix G = J'J of the sum-of-squares loss.  grad is the packed row [B][p + 1 + p p] = gradient | loss | G row-major.
+//   PDP_FUSED_MISS, PDP_FUSED_GN_MISS   PDP_GRAD_SKIP_MISSING on PDP_FUSED_PLAIN / PDP_FUSED_GN: a NaN in demo_x / demo_u is an entry that was not observed.  The lane-per-step
+//                    pass leaves the NaN in the residual's pool slot (DLX / DLU) and adds nothing to the loss for it; the forward sweep selects 0.0 for the residual and for
+//                    the sensitivity row wherever the residual tile DX / DU (element-aligned with X_t / U_t) is NaN, then contracts as before.  Same LDS layout.
 #define PDP_FUSED_PLAIN 0
 #define PDP_FUSED_RIC 1
 #define PDP_FUSED_COT 2
 #define PDP_FUSED_GN 3
+#define PDP_FUSED_MISS 4
+#define PDP_FUSED_GN_MISS 5
 
 template <class Mdl, int MODE = PDP_FUSED_PLAIN>
 __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(int B, int T, int flags, const double* __restrict__ x0, const double* __restrict__ u,
@@ -590,8 +595,10 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
                                                            double* __restrict__ dudp, int32_t* __restrict__ status, double* __restrict__ ws_gain,
                                                            double* __restrict__ riccati, float* __restrict__ prec) {
     using L = FusedLayout<Mdl>;
-    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT || MODE == PDP_FUSED_GN, "instantiation");
-    constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT, GN = MODE == PDP_FUSED_GN;
+    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT || MODE == PDP_FUSED_GN || MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS,
+                  "instantiation");
+    constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT, GN = MODE == PDP_FUSED_GN || MODE == PDP_FUSED_GN_MISS;
+    constexpr bool MISS = MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS;
     constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP, CH = L::CH, M = NU;
     constexpr int GSZ = fused_gain_doubles<Mdl>();         // per step: K [NU x NX] | k [NU x NP] | zero sink
     // SMALL (n <= 4: pendulum, cart-pole, robot arm): every matrix of the recursion fits the rows-0..3 register of its tile and every
@@ -945,12 +952,14 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
                 for (int i = 0; i < NX; ++i) {
                     xc[i] = xb[t * NX + i];
                     if constexpr (COT) row[DLX + i] = t > 0 ? dxb[t * NX + i] : 0.0;           // gx_0 multiplies X_0 = 0: not loaded
+                    else if constexpr (MISS) { const double dd = dxb[t * NX + i], d = xc[i] - dd; row[DLX + i] = dd == dd ? d : dd; lsum += dd == dd ? d * d : 0.0; }
                     else { double d = xc[i] - dxb[t * NX + i]; row[DLX + i] = d; lsum += d * d; }
                 }
 #pragma unroll
                 for (int i = 0; i < NU; ++i) {
                     uc[i] = ub[t * NU + i];
                     if constexpr (COT) row[DLU + i] = dub[t * NU + i];
+                    else if constexpr (MISS) { const double dd = dub[t * NU + i], d = uc[i] - dd; row[DLU + i] = dd == dd ? d : dd; lsum += dd == dd ? d * d : 0.0; }
                     else { double d = uc[i] - dub[t * NU + i]; row[DLU + i] = d; lsum += d * d; }
                 }
                 PackedSink s{row};
@@ -979,12 +988,25 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
                 } else
                 riccati_forward(KTc, kc, FT, GT, E2, Xc, U2, Xn);
                 PDP_FINE(10, t == 20);
+                if constexpr (MISS) {           // a NaN residual marks a row that was not observed: residual and sensitivity row are selected away (SMALL: register 0 only)
+                    d4 Xm = z, Um = z;
+#pragma unroll
+                    for (int r = 0; r < NRT; ++r) { const bool obs = DX[r] == DX[r]; Xm[r] = obs ? Xc[r] : 0.0; DX[r] = obs ? DX[r] : 0.0; }
+                    { const bool obs = DU[0] == DU[0]; Um[0] = obs ? U2[0] : 0.0; DU[0] = obs ? DU[0] : 0.0; }
+                    if constexpr (GN) {
+                        if constexpr (SMALL) Gn = mma_tn_r0(Xm, Xm, Gn);
+                        else Gn = mma_tn(Xm, Xm, Gn);
+                        Gn = mma_tn_r0(Um, Um, Gn);
+                    }
+                    acc += DX[0] * Xm[0] + DX[1] * Xm[1] + DX[2] * Xm[2] + DX[3] * Xm[3] + DU[0] * Um[0];
+                } else {
                 if constexpr (GN) {             // (SMALL: X_t and U_t live on register 0 in the ordinary column layout - parameters in columns M .. - with rows >= n / >= m zero)
                     if constexpr (SMALL) Gn = mma_tn_r0(Xc, Xc, Gn);
                     else Gn = mma_tn(Xc, Xc, Gn);
                     Gn = mma_tn_r0(U2, U2, Gn);
                 }
                 acc += DX[0] * Xc[0] + DX[1] * Xc[1] + DX[2] * Xc[2] + DX[3] * Xc[3] + DU[0] * U2[0];
+                }
                 if (dxdp) store_dense(dxdp + ((int64_t)b * (T + 1) + t) * NX * NP, NX, NP, NP, 0, M, lane, Xc);
                 if (dudp) store_dense(dudp + ((int64_t)b * T + t) * NU * NP, NU, NP, NP, 0, M, lane, U2);
                 if constexpr (RIC) {
@@ -1005,14 +1027,27 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
         wave_lds_sync();
         if (lane < NX) {
             if constexpr (COT) dlT[lane] = dxb[T * NX + lane];
+            else if constexpr (MISS) { const double dd = dxb[T * NX + lane], d = xb[T * NX + lane] - dd; dlT[lane] = dd == dd ? d : dd; lsum += dd == dd ? d * d : 0.0; }
             else { double d = xb[T * NX + lane] - dxb[T * NX + lane]; dlT[lane] = d; lsum += d * d; }
         }
         wave_lds_sync();
+        [[maybe_unused]] d4 X2m = z;                        // MISS: X_T with the rows that were not observed selected away
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { int row = tile_row(lane, r); if (row < NX) acc += dlT[row] * X2[r]; }
+        for (int r = 0; r < 4; ++r) {
+            int row = tile_row(lane, r);
+            if constexpr (MISS) {
+                if (row < NX) { const double d = dlT[row]; const bool obs = d == d; X2m[r] = obs ? X2[r] : 0.0; acc += (obs ? d : 0.0) * X2m[r]; }
+            } else {
+            if (row < NX) acc += dlT[row] * X2[r];
+            }
+        }
         if (dxdp) store_dense(dxdp + ((int64_t)b * (T + 1) + T) * NX * NP, NX, NP, NP, 0, M, lane, X2);
         finite = finite && tile_finite(X2);
         if constexpr (GN) {                                 // X_T, and the packed row's G block (gradient and loss follow below)
+            if constexpr (MISS) {
+                if constexpr (SMALL) Gn = mma_tn_r0(X2m, X2m, Gn);
+                else Gn = mma_tn(X2m, X2m, Gn);
+            } else
             if constexpr (SMALL) Gn = mma_tn_r0(X2, X2, Gn);
             else Gn = mma_tn(X2, X2, Gn);
             store_dense(grad + (int64_t)b * (NP + 1 + NP * NP) + NP + 1, NP, NP, NP, M, M, lane, Gn);

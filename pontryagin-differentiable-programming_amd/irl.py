@@ -247,18 +247,27 @@ class LMLoop:
                 "iterations": len(self.loss_trace)}
 
     @classmethod
-    def for_irl(cls, mdl, demo_x, demo_u, theta0, tol=1e-10, max_iter=300, n_total=None, **kw):
+    def for_irl(cls, mdl, demo_x, demo_u, theta0, tol=1e-10, max_iter=300, n_total=None, ini_state=None, skip_missing=False, **kw):
         """The IRL drivers' problem: mdl a runtime.ModelLib of an OC model, demo_x [B, T+1, n], demo_u [B, T, m] the demonstrations (this rank's shard under
         torch.distributed; n_total as in parallel.allreduce_mean_packed), theta0 [p] shared by all of them.  evaluate(theta) solves every demonstration's OC problem
         (oc_solve_ms: the first cold, later ones warm from COPIES of the last accepted solution, so that a rejected trial cannot damage it), runs the fused unit once with
         gauss_newton=True on the solutions and hands the packed rows, with the count of samples whose solve did not converge or reported trouble or whose unit set a
         status bit, to parallel.mean_row_checked: one all-reduce when a process group exchanges, one copy of p + 3 + p p doubles to the host.  A trial with such a sample on
-        ANY rank is None on EVERY rank (the decision travels with the rows: no rank skips a collective the others issue)."""
+        ANY rank is None on EVERY rank (the decision travels with the rows: no rank skips a collective the others issue).
+        skip_missing: demonstrations with gaps - a NaN in demo_x / demo_u is an entry that was not observed (PDP_GRAD_SKIP_MISSING: a keyframe every k steps, positions
+        without velocities, no recorded controls = demo_u all NaN); loss, gradient and G are formed over the observed entries only.  ini_state [B, n] replaces
+        demo_x[:, 0] as the initial state of the solves - needed where the first row of a demonstration is not (fully) observed: with skip_missing a NaN in the initial
+        state the solves would start from is a ValueError here, before any launch."""
+        if skip_missing:                            # judged on what the caller gave (a host array is not moved to the device first)
+            first = ini_state if ini_state is not None else (demo_x if hasattr(demo_x, "data_ptr") else np.asarray(demo_x, dtype=float))[:, 0]
+            if bool(first.isnan().any()) if hasattr(first, "data_ptr") else bool(np.isnan(np.asarray(first, dtype=float)).any()):
+                raise ValueError("LMLoop.for_irl: skip_missing=True and the initial state (%s) holds a NaN: give ini_state [B, n]"
+                                 % ("demo_x[:, 0]" if ini_state is None else "ini_state"))
         from . import parallel
         demo_x, demo_u = rt.dev(demo_x), rt.dev(demo_u)
         B, T, p = int(demo_u.shape[0]), int(demo_u.shape[1]), mdl.p
         assert demo_x.shape == (B, T + 1, mdl.n) and demo_u.shape == (B, T, mdl.m)
-        x0 = demo_x[:, 0].contiguous()
+        x0 = (demo_x[:, 0] if ini_state is None else rt.dev(ini_state).reshape(B, mdl.n)).contiguous()
         bufs, state = {}, {"accepted": None, "trial": None}
         informational = 128 | 512 | 1024 | 2048          # PDP_MS_RESTORED, PDP_MS_PREDICT_REJECTED, PDP_MS_SOC, PDP_MS_WATCHDOG
 
@@ -266,7 +275,7 @@ class LMLoop:
             # no decision on this rank's own flags: solve and unit always run, the flags are counted on the device and travel with the rows, so that every rank issues
             # the same collective and takes the same decision (parallel.mean_row_checked) - and the host reads the device once
             s = mdl.oc_solve_ms(x0, theta, T, tol=tol, max_iter=max_iter, warm=state["accepted"])
-            out = mdl.oc_pdp_grad(s["control"], theta, demo_x, demo_u, x=s["state"], lam=s["costate"], gauss_newton=True, buffers=bufs)
+            out = mdl.oc_pdp_grad(s["control"], theta, demo_x, demo_u, x=s["state"], lam=s["costate"], gauss_newton=True, skip_missing=skip_missing, buffers=bufs)
             bad = (s["converged_flags"] == 0) | ((s["status"] & ~informational) != 0) | (out["status"] != 0)
             row = parallel.mean_row_checked(out["packed_gn"], bad, n_total)
             if row is None:

@@ -495,7 +495,7 @@ class ModelLib:
         return out
 
     def oc_pdp_grad(self, u, theta, demo_x, demo_u, x0=None, x=None, lam=None, want_sens=False, buffers=None, packed=False, want_riccati=False,
-                    want_predict_record=False, gauss_newton=False):
+                    want_predict_record=False, gauss_newton=False, skip_missing=False):
         """Fused forward + Riccati + PDP gradient.  Give (x, lam) to use an optimal trajectory (PDP_OC_GIVEN_TRAJ),
         else x0 and the kernel integrates u and the costates itself.  Returns dict(loss, grad, x, lam, status[, dxdp, dudp][, riccati]).
         packed: the kernel writes gradient and loss as one [B, p+1] tensor (PDP_OC_PACKED; out["packed"], out["grad"] is a view of it).
@@ -507,7 +507,14 @@ class ModelLib:
         gauss_newton (PDP_GRAD_GAUSS_NEWTON): the kernel also contracts the sensitivity tiles of its forward sweep with themselves and writes ONE row per trajectory,
         out["packed_gn"] [B, p + 1 + p p] = gradient | loss | G row-major, G = J'J = sum_t X_t' X_t + U_t' U_t the Gauss-Newton matrix of the sum-of-squares loss (no
         factor: grad = J'r and G belong together); out["grad"] and out["gn"] [B, p, p] are views of it.  Not together with want_sens, want_riccati, want_predict_record or
-        packed (ValueError).  Beyond the fused kernels' limits the row is filled from the materialised sensitivities (two einsums): one layout either way."""
+        packed (ValueError).  Beyond the fused kernels' limits the row is filled from the materialised sensitivities (two einsums): one layout either way.
+        skip_missing (PDP_GRAD_SKIP_MISSING): a NaN in demo_x / demo_u marks an entry that was not observed - its residual is left out of the loss, its term out of the
+        gradient and, with gauss_newton, its Jacobian row out of G (only NaN: an inf propagates as always).  demo_x[:, 0] may be all NaN when x0 is given.  Alone, with
+        packed or with gauss_newton; with want_sens, want_riccati or want_predict_record: ValueError (and oc_pdp_vjp has no such switch: a NaN cotangent is an error).
+        Beyond the fused kernels' limits the same rows come from the materialised sensitivities, masked and contracted with torch.einsum."""
+        if skip_missing and (want_sens or want_riccati or want_predict_record):
+            raise ValueError("oc_pdp_grad: skip_missing=True goes with the gradient, packed or gauss_newton rows only - not with want_sens, want_riccati or "
+                             "want_predict_record")
         if gauss_newton and (want_sens or want_riccati or want_predict_record or packed):
             raise ValueError("oc_pdp_grad: gauss_newton=True goes with the plain gradient only - not with want_sens, want_riccati, want_predict_record or packed")
         torch = torch_cuda()
@@ -548,6 +555,8 @@ class ModelLib:
         prec = buf("predict_record", (B, T, int(self.lib.pdp_oc_predict_record_floats())), torch.float32) if want_predict_record else None
         if want_predict_record == "primal":
             flags |= 4
+        if skip_missing:
+            flags |= 32
         nbytes = self.lib.pdp_oc_pdp_workspace_bytes(B, T)
         ws = buf("ws", (max(nbytes, 8) // 8,))
         if want_riccati or want_predict_record:
@@ -564,9 +573,20 @@ class ModelLib:
             # m + p > 16 (beyond the fused kernel's single parameter tile), n > 16 / m > 4 (beyond one tile per matrix: the size-generic LQR
             # kernel takes over - any n, m), or a horizon whose staging exceeds the LDS: the reference's own route, kernel by kernel
             self._warn_materialised(T)
-            if gauss_newton:                                    # the sensitivities through HBM, contracted here: the same row
+            if gauss_newton or skip_missing:                    # the sensitivities through HBM, contracted here: the same row
                 dxdp, dudp = torch.empty((B, T + 1, n, p), dtype=torch.float64, device="cuda"), torch.empty((B, T, m, p), dtype=torch.float64, device="cuda")
-            self._oc_pdp_grad_materialised(u, theta, demo_x, demo_u, x0, x, lam, flags, loss, grad, status, dxdp, dudp)
+            if skip_missing:
+                # the want_sens launch on the demonstrations with their NaNs replaced by zeros gives x, lam, status and the sensitivities; loss and gradient are
+                # re-formed here from the masked residuals (selected, not multiplied: an inf in an absent slot cannot exist - only NaN is absent)
+                wx, wu = ~torch.isnan(demo_x), ~torch.isnan(demo_u)
+                zero = torch.zeros((), dtype=torch.float64, device="cuda")
+                self._oc_pdp_grad_materialised(u, theta, torch.where(wx, demo_x, zero), torch.where(wu, demo_u, zero), x0, x, lam, flags, loss, grad, status, dxdp, dudp)
+                ex, eu = torch.where(wx, x - demo_x, zero), torch.where(wu, u - demo_u, zero)
+                loss.copy_((ex ** 2).sum(dim=(1, 2)) + (eu ** 2).sum(dim=(1, 2)))
+                dxdp, dudp = torch.where(wx[..., None], dxdp, zero), torch.where(wu[..., None], dudp, zero)
+                grad.copy_(torch.einsum("bti,btip->bp", ex, dxdp) + torch.einsum("bti,btip->bp", eu, dudp))
+            else:
+                self._oc_pdp_grad_materialised(u, theta, demo_x, demo_u, x0, x, lam, flags, loss, grad, status, dxdp, dudp)
             if packed or gauss_newton:
                 pk[:, p].copy_(loss)
             if gauss_newton:
