@@ -5,6 +5,12 @@ generate_traj.py (struct <stem>_iodata with batch_inputs / batch_states / true_p
 Examples/SysID/quadrotor/generate_traj.py:36-42) through --data.
 
     python examples/sysid_pdp.py --system quadrotor --iters 2000 --lr 1e-4 [--data path/to/uav_iodata.mat]
+
+--method lm: the same problem as nonlinear least squares (pdp_amd.irl.LMLoop.for_sysid: Levenberg-Marquardt on the Gauss-Newton matrix the fused kernel returns with the
+gradient, one launch per evaluation) - a handful of evaluations instead of thousands of descent steps.  With it, partial data: --every K keeps the samples at
+t = K, 2K, ... only, --observe i,j,... only those state components; every other entry becomes NaN = not observed, and the rollouts start from the recorded initial states.
+
+    python examples/sysid_pdp.py --system pendulum --method lm --every 2 --observe 0
 """
 import argparse
 import os
@@ -41,7 +47,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--graph", action="store_true", help="keep the loop on the device (pdp_amd.irl.GDLoop: two launches per iteration, replayed as a hipGraph); equal horizons only")
     ap.add_argument("--data", default=None, help="<stem>_iodata.mat in the reference's schema (default: the stored data of --system)")
+    ap.add_argument("--method", default="gd", choices=["gd", "lm"], help="gd: the reference's gradient descent; lm: Levenberg-Marquardt (at most min(--iters, 100) evaluations)")
+    ap.add_argument("--every", type=int, default=1, help="--method lm: only the samples at t = K, 2K, ... are observed")
+    ap.add_argument("--observe", default=None, help="--method lm: only these state components are observed (comma-separated indices)")
     a = ap.parse_args()
+    partial = a.every > 1 or a.observe is not None
+    if partial and a.method != "lm":
+        ap.error("--every / --observe need --method lm")
     env, dt = zoo.make_env(a.system, "sysid")
     sid = PDP.SysID(a.system)
     sid.setAuxvarVariable(env.dyn_auxvar)
@@ -55,7 +67,23 @@ def main():
     theta = true_parameter + a.sigma * rng.random(true_parameter.size) - a.sigma / 2
     loss_trace, parameter_trace = [], []
     t0 = time.time()
-    if a.graph:
+    if a.method == "lm":
+        from pdp_amd.irl import LMLoop
+        if partial:
+            comps = [int(c) for c in a.observe.split(",")] if a.observe is not None else list(range(states.shape[2]))
+            masked = np.full_like(states, np.nan)
+            for t in range(a.every, states.shape[1], a.every):
+                masked[:, t, comps] = states[:, t, comps]
+            loop = LMLoop.for_sysid(sid.model(), inputs, masked, theta, ini_state=states[:, 0], skip_missing=True)
+        else:
+            loop = LMLoop.for_sysid(sid.model(), inputs, states, theta)
+        r = loop.run(max_evals=min(a.iters, 100), loss_tol=1e-20)
+        loss_trace, parameter_trace = list(r["loss_trace"]), list(r["parameter_trace"])
+        for k in range(len(loss_trace)):
+            print("accepted %3d  loss %.6e  lambda %.1e  theta %s" % (k, loss_trace[k], r["lambda_trace"][k], np.array2string(parameter_trace[k], precision=4)))
+        print("%d evaluations, %d rejected%s" % (r["evaluations"], r["rejected"], ", stalled" if r["stalled"] else ""))
+        theta, a.iters = parameter_trace[-1], len(loss_trace)
+    elif a.graph:
         from pdp_amd import runtime as rt
         from pdp_amd.irl import GDLoop
         mdl = sid.model()
@@ -67,7 +95,7 @@ def main():
         theta = parameter_trace[-1]
         for k in range(0, a.iters, max(1, a.iters // 10)):
             print("iter %5d  loss %.6e  theta %s" % (k, loss_trace[k], np.array2string(parameter_trace[k], precision=4)))
-    for k in range(0 if not a.graph else a.iters, a.iters):
+    for k in range(0 if not (a.graph or a.method == "lm") else a.iters, a.iters):
         loss, dp = sid.step(batch_inputs, batch_states, theta)
         theta = theta - a.lr * dp
         loss_trace.append(loss)

@@ -193,9 +193,13 @@ __global__ void __launch_bounds__(128 * TPW) cp_step_poly2_kernel(int B, int T, 
 // Fused SysID.step (reference PDP/PDP.py:1178-1296: integrateSys with the given controls, getAuxSys, integrateAuxSys X_{t+1} = F X_t + E, chain rule with the
 // prediction error) as the same two-wave pipeline: wave R rolls the model out along the recorded controls, wave S follows a chunk behind with the Jacobians, the
 // prediction errors and the sensitivity recursion.  Same arithmetic in the same order as sysid_step_kernel (bit-identical, tests/test_gpu_cp_pair.py).
-template <class Mdl, int NT, int TPW>
+// MODE, Ini: as in sysid_step_kernel (PDP_SYSID_GN / PDP_SYSID_GN_MISS: `grad` is the packed row grad | loss | G, the trailing argument is x0 [B][NX] or NULL).
+template <class Mdl, int NT, int TPW, int MODE = PDP_SYSID_PLAIN, class... Ini>
 __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, const double* __restrict__ u, const double* __restrict__ xobs,
-                                                                 const double* __restrict__ theta, int tb, double* __restrict__ loss, double* __restrict__ grad, int slice) {
+                                                                 const double* __restrict__ theta, int tb, double* __restrict__ loss, double* __restrict__ grad, int slice,
+                                                                 Ini... ini) {
+    static_assert(MODE == PDP_SYSID_PLAIN || (NT == 1 && sizeof...(Ini) == 1 && (MODE == PDP_SYSID_GN || MODE == PDP_SYSID_GN_MISS)), "sysid_step2_kernel: MODE");
+    constexpr bool GN = MODE != PDP_SYSID_PLAIN, MISS = MODE == PDP_SYSID_GN_MISS;
     constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP, CH = Mdl::CHUNK;
     constexpr int NC = 1 + Mdl::PATH_NCONST, DLX = Mdl::PATH_NVAR, STRIDE = (Mdl::PATH_NVAR + NX) | 1;
     static_assert(TPW == 1 || TPW == 2 || TPW == 4, "trajectories per workgroup");
@@ -228,6 +232,12 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
         double xc[NX], xn[NX], uc[NU], un[NU];
 #pragma unroll
         for (int i = 0; i < NX; ++i) xc[i] = ob[i];                       // ini_state = batch_states[i][0] (PDP.py:1269)
+        if constexpr (GN) {
+            if (const double* x0 = sysid_ini(ini...)) {
+#pragma unroll
+                for (int i = 0; i < NX; ++i) xc[i] = x0[(int64_t)bb * NX + i];
+            }
+        }
         if (lane == 0) {
 #pragma unroll
             for (int i = 0; i < NX; ++i) xs[i] = xc[i];
@@ -257,6 +267,7 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
             make_gather(gE[j], lane, NC, STRIDE, [j](int r, int c) { return (r < NX && 16 * j + c < NP) ? Mdl::path_code(1, r * NP + 16 * j + c) : -1; });
         d4 X[NT];
         double acc[NT], lsum = 0.0;
+        [[maybe_unused]] d4 Gn = z;                        // GN: sum_t X_t' X_t
 #pragma unroll
         for (int j = 0; j < NT; ++j) { X[j] = z; acc[j] = 0.0; }
         const int nchunk = (T + CH - 1) / CH;
@@ -270,7 +281,10 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
                 double xc[NX], uc[NU];
                 double* row = pool + lane * STRIDE;
 #pragma unroll
-                for (int i = 0; i < NX; ++i) { xc[i] = xs[t * NX + i]; double d = xc[i] - ob[t * NX + i]; row[DLX + i] = d; lsum += d * d; }
+                for (int i = 0; i < NX; ++i) {
+                    if constexpr (!MISS) { xc[i] = xs[t * NX + i]; double d = xc[i] - ob[t * NX + i]; row[DLX + i] = d; lsum += d * d; }
+                    else { xc[i] = xs[t * NX + i]; const double o = ob[t * NX + i], d = xc[i] - o; row[DLX + i] = d; lsum += o == o ? d * d : 0.0; }
+                }
 #pragma unroll
                 for (int i = 0; i < NU; ++i) uc[i] = us[t * NU + i];
                 PackedSink s{row};
@@ -283,24 +297,53 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
                     d4 E = gather_tile(blk, gE[j], tl);
+                    if constexpr (MISS) {
+                        d4 Xm;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { const bool obs = DX[r] == DX[r]; Xm[r] = obs ? X[j][r] : 0.0; DX[r] = obs ? DX[r] : 0.0; }
+                        acc[j] += DX[0] * Xm[0] + DX[1] * Xm[1] + DX[2] * Xm[2] + DX[3] * Xm[3];
+                        Gn = mma_tn(Xm, Xm, Gn);
+                    } else {
                     acc[j] += DX[0] * X[j][0] + DX[1] * X[j][1] + DX[2] * X[j][2] + DX[3] * X[j][3];
+                    if constexpr (GN) Gn = mma_tn(X[j], X[j], Gn);
+                    }
                     X[j] = mma_tn(FT, X[j], E);
                 }
             }
         }
         wg_wait_ge(fl, T);                                   // x_T
         wave_lds_sync();
+        if constexpr (!MISS) {
         if (lane < NX) { double d = xs[T * NX + lane] - ob[T * NX + lane]; dlT[lane] = d; lsum += d * d; }
+        } else {
+            if (lane < NX) { const double o = ob[T * NX + lane], d = xs[T * NX + lane] - o; dlT[lane] = d; lsum += o == o ? d * d : 0.0; }
+        }
         wave_lds_sync();
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { int row = tile_row(lane, r); if (row < NX) acc[j] += dlT[row] * X[j][r]; }
+            for (int r = 0; r < 4; ++r) {
+                int row = tile_row(lane, r);
+                if constexpr (MISS) {
+                    if (row < NX) { const double d = dlT[row]; const bool obs = d == d; X[j][r] = obs ? X[j][r] : 0.0; acc[j] += (obs ? d : 0.0) * X[j][r]; }
+                } else {
+                if (row < NX) acc[j] += dlT[row] * X[j][r];
+                }
+            }
             double a = sum_over_rowgroups(acc[j]);
+            if constexpr (GN) {
+                Gn = mma_tn(X[j], X[j], Gn);               // X_T (MISS: its unobserved rows selected to 0 above)
+                if (mine) {
+                    if (lane < NP) grad[(int64_t)b * (NP + 1 + NP * NP) + lane] = a;
+                    store_dense(grad + (int64_t)b * (NP + 1 + NP * NP) + NP + 1, NP, NP, NP, 0, 0, lane, Gn);
+                }
+            } else {
             if (mine && lane < 16 && 16 * j + lane < NP) grad[(int64_t)b * NP + 16 * j + lane] = a;
+            }
         }
         lsum = wave_sum(lsum);
         if (mine && lane == 0) loss[b] = lsum;
+        if constexpr (GN) { if (mine && lane == 0) grad[(int64_t)b * (NP + 1 + NP * NP) + NP] = lsum; }
     }
 }
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include "../../include/pdp_hip.h"
+#include "../../include/pdp_hip_sysid_gn.h"
 #ifndef PDP_MODEL_HEADER
 #error "compile with -DPDP_MODEL_HEADER=\"generated/<model>.h\""
 #endif
@@ -540,19 +541,28 @@ inline bool sysid_prepass(int B) {
     static const int env = env_int("PDP_SYSID_PREPASS", -1);
     return env >= 0 ? env != 0 : B > 8 * device_cu_count();
 }
+// workgroups per CU that the pool rows of the given-trajectory kernel are sized for (sysid_rows_given): three wavefronts per SIMD at the plain instantiation's 162
+// VGPRs; the Gauss-Newton instantiations carry one more accumulator tile (quadrotor: 174 / 176 VGPRs, no spill) and get two per SIMD - their rows are sized for the
+// eight workgroups that are resident
+template <int MODE> constexpr int SYSID_GIVEN_WGS = MODE == PDP_SYSID_PLAIN ? 12 : 8;
 template <class Mdl>
 int64_t sysid_step_ws_bytes(int B, int T) {
     if constexpr (Mdl::KIND == PDP_KIND_SYSID) return sysid_prepass(B) ? (int64_t)B * (T + 1) * Mdl::NX * (int64_t)sizeof(double) : 0;
     else return 0;
 }
-template <class Mdl>
-int sysid_step(int B, int T, const double* u, const double* xobs, const double* th, int tb, double* loss, double* grad, void* ws, int64_t wsb, void* st) {
-    if constexpr (Mdl::KIND == PDP_KIND_SYSID && Mdl::NX <= 16 && Mdl::NP <= 64) {
+// MODE (PDP_SYSID_PLAIN / PDP_SYSID_GN / PDP_SYSID_GN_MISS): the instantiation of the fused kernels.  The Gauss-Newton modes write the packed row grad | loss | G through
+// `grad`, start the rollouts from x0 [B][n] (NULL: x_obs[:, 0]) - in the kernels through their trailing argument, in the pre-pass through its pointer and stride - and
+// exist for p <= 16.  Same dispatch, thresholds and switches in every mode.
+template <class Mdl, int MODE = PDP_SYSID_PLAIN>
+int sysid_step(int B, int T, const double* u, const double* xobs, const double* th, int tb, double* loss, double* grad, void* ws, int64_t wsb, void* st,
+               const double* x0 = nullptr) {
+    if constexpr (Mdl::KIND == PDP_KIND_SYSID && Mdl::NX <= 16 && Mdl::NP <= (MODE == PDP_SYSID_PLAIN ? 64 : 16)) {
         if (B <= 0 || T <= 0 || !u || !xobs || !th || !loss || !grad) return PDP_E_ARG;
         const double* xgiven = nullptr;
         if (ws && sysid_prepass(B)) {           // (no workspace: the kernel rolls out itself, whatever the batch)
             if (wsb < sysid_step_ws_bytes<Mdl>(B, T)) return PDP_E_ARG;
-            if (const int rc = launch(sysid_integrate_kernel<Mdl>, dim3((B + 63) / 64), dim3(64), 0, S(st), B, T, xobs, (int)((T + 1) * Mdl::NX), u, th, tb, (double*)ws); rc != 0)
+            if (const int rc = launch(sysid_integrate_kernel<Mdl>, dim3((B + 63) / 64), dim3(64), 0, S(st), B, T, x0 ? x0 : xobs,
+                                      (int)(x0 ? Mdl::NX : (T + 1) * Mdl::NX), u, th, tb, (double*)ws); rc != 0)
                 return rc;
             xgiven = (const double*)ws;
         }
@@ -560,7 +570,7 @@ int sysid_step(int B, int T, const double* u, const double* xobs, const double* 
         static const int rows_env = env_int("PDP_SYSID_ROWS", 0), wgs_env = env_int("PDP_SYSID_GIVEN_WGS", 0);
         const int cus = device_cu_count();
         const int rows = rows_env > 0 ? (rows_env < Mdl::CHUNK ? rows_env : Mdl::CHUNK)
-                         : (xgiven ? sysid_rows_given<Mdl>(T, wgs_env > 0 ? wgs_env : 12) : sysid_rows<Mdl>(B, T, cus));
+                         : (xgiven ? sysid_rows_given<Mdl>(T, wgs_env > 0 ? wgs_env : SYSID_GIVEN_WGS<MODE>) : sysid_rows<Mdl>(B, T, cus));
         const size_t lds = sizeof(double) * (size_t)sysid_slice<Mdl>(T, rows, xgiven != nullptr);
         if (lds > 150 * 1024) return PDP_E_SIZE;
         // PDP_SYSID_VARIANT: 2 = rollout wave + sensitivity wave per trajectory (pdp_cp_pair_kernels.h), the default; 1 = one wavefront per trajectory
@@ -571,12 +581,19 @@ int sysid_step(int B, int T, const double* u, const double* xobs, const double* 
             const int slice = sysid_slice<Mdl>(T), tpw = traj_per_workgroup(B, cus, 2);
             if (slice * tpw * (int)sizeof(double) <= 160 * 1024)
                 return with_int<1, 2>(tpw, [&](auto K) {
+                    if constexpr (MODE == PDP_SYSID_PLAIN)
                     return launch(sysid_step2_kernel<Mdl, NT, K()>, dim3((B + K() - 1) / K()), dim3(128 * K()), slice * K() * sizeof(double), S(st), B, T, u, xobs, th, tb, loss,
                                   grad, slice);
+                    else
+                        return launch(sysid_step2_kernel<Mdl, NT, K(), MODE, const double*>, dim3((B + K() - 1) / K()), dim3(128 * K()), slice * K() * sizeof(double), S(st),
+                                      B, T, u, xobs, th, tb, loss, grad, slice, x0);
                 });
         }
         return with_bool(xgiven != nullptr, [&](auto GIVEN) {
+            if constexpr (MODE == PDP_SYSID_PLAIN)
             return launch(sysid_step_kernel<Mdl, NT, GIVEN()>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad, rows, xgiven);
+            else
+                return launch(sysid_step_kernel<Mdl, NT, GIVEN(), MODE, const double*>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad, rows, xgiven, x0);
         });
     } else { return Mdl::KIND == PDP_KIND_SYSID ? PDP_E_SIZE : PDP_E_MODE; }
 }
@@ -681,6 +698,12 @@ int64_t pdp_sysid_step_workspace_bytes(int B, int T) { return sysid_step_ws_byte
 int pdp_sysid_step_ws_batched(int B, int T, const double* u, const double* x_obs, const double* theta, int tb, double* loss, double* grad, void* workspace,
                               int64_t workspace_bytes, void* stream) {
     return sysid_step<PdpModel>(B, T, u, x_obs, theta, tb, loss, grad, workspace, workspace_bytes, stream);
+}
+int pdp_sysid_step_gn_batched(int B, int T, const double* u, const double* x_obs, const double* x0, const double* theta, int tb, int flags, double* loss, double* packed,
+                              void* workspace, int64_t workspace_bytes, void* stream) {
+    if (B <= 0 || T <= 0 || !u || !x_obs || !theta || !loss || !packed || (flags & ~PDP_GRAD_SKIP_MISSING)) return PDP_E_ARG;
+    return (flags & PDP_GRAD_SKIP_MISSING) ? sysid_step<PdpModel, PDP_SYSID_GN_MISS>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0)
+                                           : sysid_step<PdpModel, PDP_SYSID_GN>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0);
 }
 
 }  // extern "C"

@@ -1785,11 +1785,30 @@ __host__ inline int sysid_rows(int B, int T, int cus) {
     const int fit = (160 * 1024 / 8 / 8 - 64 - sysid_slice<Mdl>(T, 0)) / stride;      // (64 doubles of slack for the allocation granularity)
     return fit >= 4 ? (fit < Mdl::CHUNK ? fit : Mdl::CHUNK) : Mdl::CHUNK;
 }
+// MODE of the fused SysID.step kernels (sysid_step_kernel below, sysid_step2_kernel in pdp_cp_pair_kernels.h; pdp_sysid_step_gn_batched selects 1 / 2):
+//   PDP_SYSID_PLAIN    loss and gradient: the code of pdp_sysid_step_batched, unchanged by the other two (their additions sit under `if constexpr`)
+//   PDP_SYSID_GN       plus one accumulator tile Gn += X_t' X_t beside the gradient's acc += DX . X (the X_t tile is in registers anyway; both MFMA operands are the
+//                      same tile, so G = sum_{t<=T} X_t' X_t, X_0 = 0, is symmetric to the bit).  `grad` is then ONE PACKED ROW per trajectory, grad [p] | loss | G [p][p]
+//                      (the layout of PDP_GRAD_GAUSS_NEWTON), and the rollout starts from the trailing argument x0 [B][NX] (NULL: x_obs[:, 0]); row 0 adds
+//                      |x0 - x_obs_0|^2 to the loss and - X_0 = 0 - nothing to gradient and G
+//   PDP_SYSID_GN_MISS  PDP_SYSID_GN where a NaN in x_obs is an entry that was not observed (the semantics of PDP_GRAD_SKIP_MISSING): the lane-per-step pass leaves the
+//                      NaN residual in the DLX slot and adds nothing to the loss for it; the sensitivity loop SELECTS (never multiplies by 0) the residual and the row of
+//                      X_t to 0 where the residual is NaN, for the gradient and for Gn; the recursion X_{t+1} = F X_t + E runs on the unmasked X.  An OBSERVED entry whose own
+//                      state is not finite leaves a NaN in the loss: a diverged rollout stays visible (there is no status word here)
+// Both new modes exist for one parameter tile only (NT == 1, p <= 16: what irl.lm_step solves on the host).
+#define PDP_SYSID_PLAIN 0
+#define PDP_SYSID_GN 1
+#define PDP_SYSID_GN_MISS 2
+PDP_DEV const double* sysid_ini() { return nullptr; }                     // the trailing x0 argument of the Gauss-Newton modes (PDP_SYSID_PLAIN has none)
+PDP_DEV const double* sysid_ini(const double* x0) { return x0; }
+
 // Fused SysID.step per trajectory: rollout (uniform, x kept in LDS) then X_{t+1} = F X_t + E on MFMA tiles.
-template <class Mdl, int NT, bool GIVEN = false>
+template <class Mdl, int NT, bool GIVEN = false, int MODE = PDP_SYSID_PLAIN, class... Ini>
 __global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const double* __restrict__ u, const double* __restrict__ xobs,
                                                          const double* __restrict__ theta, int tb, double* __restrict__ loss, double* __restrict__ grad, int CH,
-                                                         const double* __restrict__ xgiven_) {
+                                                         const double* __restrict__ xgiven_, Ini... ini) {
+    static_assert(MODE == PDP_SYSID_PLAIN || (NT == 1 && sizeof...(Ini) == 1 && (MODE == PDP_SYSID_GN || MODE == PDP_SYSID_GN_MISS)), "sysid_step_kernel: MODE");
+    constexpr bool GN = MODE != PDP_SYSID_PLAIN, MISS = MODE == PDP_SYSID_GN_MISS;
     const double* __restrict__ xgiven = GIVEN ? xgiven_ : nullptr;      // (a template parameter: each instantiation keeps its own register allocation)
     // xgiven [B][T+1][NX] (GIVEN): the trajectory, rolled out beforehand by sysid_integrate_kernel with ONE LANE per trajectory - the mode for batches with several
     // trajectories per SIMD: the rollout below runs one trajectory on all 64 lanes (the same value in every lane), which is the right thing while the SIMD has nothing
@@ -1822,6 +1841,12 @@ __global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const doub
         double xc[NX], xn[NX], uc[NU], un[NU];
 #pragma unroll
         for (int i = 0; i < NX; ++i) xc[i] = ob[i];                       // ini_state = batch_states[i][0] (PDP.py:1269)
+        if constexpr (GN) {
+            if (const double* x0 = sysid_ini(ini...)) {
+#pragma unroll
+                for (int i = 0; i < NX; ++i) xc[i] = x0[(int64_t)b * NX + i];
+            }
+        }
         if (lane == 0) {
 #pragma unroll
             for (int i = 0; i < NX; ++i) xs[i] = xc[i];
@@ -1849,6 +1874,7 @@ __global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const doub
         make_gather(gE[j], lane, NC, STRIDE, [j](int r, int c) { return (r < NX && 16 * j + c < NP) ? Mdl::path_code(1, r * NP + 16 * j + c) : -1; });
     d4 X[NT];
     double acc[NT], lsum = 0.0;
+    [[maybe_unused]] d4 Gn = z;                            // GN: sum_t X_t' X_t
 #pragma unroll
     for (int j = 0; j < NT; ++j) { X[j] = z; acc[j] = 0.0; }
     const int nchunk = (T + CH - 1) / CH;
@@ -1861,7 +1887,10 @@ __global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const doub
             double xc[NX], uc[NU];
             double* row = pool + lane * STRIDE;
 #pragma unroll
-            for (int i = 0; i < NX; ++i) { xc[i] = xg ? xg[t * NX + i] : xs[t * NX + i]; double d = xc[i] - ob[t * NX + i]; row[DLX + i] = d; lsum += d * d; }
+            for (int i = 0; i < NX; ++i) {
+                if constexpr (!MISS) { xc[i] = xg ? xg[t * NX + i] : xs[t * NX + i]; double d = xc[i] - ob[t * NX + i]; row[DLX + i] = d; lsum += d * d; }
+                else { xc[i] = xg ? xg[t * NX + i] : xs[t * NX + i]; const double o = ob[t * NX + i], d = xc[i] - o; row[DLX + i] = d; lsum += o == o ? d * d : 0.0; }
+            }
 #pragma unroll
             for (int i = 0; i < NU; ++i) uc[i] = xg ? ub[t * NU + i] : us[t * NU + i];
             PackedSink s{row};
@@ -1874,23 +1903,50 @@ __global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const doub
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 d4 E = gather_tile(blk, gE[j], tl);
+                if constexpr (MISS) {
+                    d4 Xm;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { const bool obs = DX[r] == DX[r]; Xm[r] = obs ? X[j][r] : 0.0; DX[r] = obs ? DX[r] : 0.0; }
+                    acc[j] += DX[0] * Xm[0] + DX[1] * Xm[1] + DX[2] * Xm[2] + DX[3] * Xm[3];
+                    Gn = mma_tn(Xm, Xm, Gn);
+                } else {
                 acc[j] += DX[0] * X[j][0] + DX[1] * X[j][1] + DX[2] * X[j][2] + DX[3] * X[j][3];
+                if constexpr (GN) Gn = mma_tn(X[j], X[j], Gn);
+                }
                 X[j] = mma_tn(FT, X[j], E);
             }
         }
     }
     __syncthreads();
+    if constexpr (!MISS) {
     if (lane < NX) { double d = (xg ? xg[T * NX + lane] : xs[T * NX + lane]) - ob[T * NX + lane]; dlT[lane] = d; lsum += d * d; }
+    } else {
+        if (lane < NX) { const double o = ob[T * NX + lane], d = (xg ? xg[T * NX + lane] : xs[T * NX + lane]) - o; dlT[lane] = d; lsum += o == o ? d * d : 0.0; }
+    }
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { int row = tile_row(lane, r); if (row < NX) acc[j] += dlT[row] * X[j][r]; }
+        for (int r = 0; r < 4; ++r) {
+            int row = tile_row(lane, r);
+            if constexpr (MISS) {
+                if (row < NX) { const double d = dlT[row]; const bool obs = d == d; X[j][r] = obs ? X[j][r] : 0.0; acc[j] += (obs ? d : 0.0) * X[j][r]; }
+            } else {
+            if (row < NX) acc[j] += dlT[row] * X[j][r];
+            }
+        }
         double a = sum_over_rowgroups(acc[j]);
+        if constexpr (GN) {
+            if (lane < NP) grad[(int64_t)b * (NP + 1 + NP * NP) + lane] = a;
+            Gn = mma_tn(X[j], X[j], Gn);                   // X_T (MISS: its unobserved rows selected to 0 above)
+            store_dense(grad + (int64_t)b * (NP + 1 + NP * NP) + NP + 1, NP, NP, NP, 0, 0, lane, Gn);
+        } else {
         if (lane < 16 && 16 * j + lane < NP) grad[(int64_t)b * NP + 16 * j + lane] = a;
+        }
     }
     lsum = wave_sum(lsum);
     if (lane == 0) loss[b] = lsum;
+    if constexpr (GN) { if (lane == 0) grad[(int64_t)b * (NP + 1 + NP * NP) + NP] = lsum; }
 }
 
 }  // namespace pdp

@@ -14,7 +14,8 @@ hipGraph on ROCm: every buffer, the parameter vector, the step and the traces li
 LMLoop / lm_step: the same IRL problem as nonlinear least squares.  The loss of the drivers is a sum of squares, and the fused unit's PDP_GRAD_GAUSS_NEWTON instantiation returns
 the Gauss-Newton matrix G = J'J beside the gradient J'r from the sensitivity tiles it holds anyway, so a Levenberg-Marquardt step costs one solve and one unit call, like a
 gradient-descent step, and a handful of them reach what thousands of descent steps do not.  A step is accepted or rejected on the loss: this loop is driven by the host (LMLoop.for_irl reads
-the device once per evaluation: rows and health flags in one copy) and is not graph-replayed.
+the device once per evaluation: rows and health flags in one copy) and is not graph-replayed.  LMLoop.for_sysid is the same loop on SysID.step, whose loss is a sum of
+squares with no inner solve: one launch per evaluation (pdp_sysid_step_gn_batched), complete or partial (NaN) data.
 """
 import numpy as np
 
@@ -286,3 +287,30 @@ class LMLoop:
         loop = cls(evaluate, theta0, **kw)
         loop.on_accept = lambda: state.update(accepted=state["trial"])
         return loop
+
+    @classmethod
+    def for_sysid(cls, mdl, inputs, states, theta0, n_total=None, ini_state=None, skip_missing=False, **kw):
+        """The SysID drivers' problem (Examples/SysID/*/..._PDP.py) as nonlinear least squares: mdl a runtime.ModelLib of a SysID model, inputs [B, T, m] and states
+        [B, T+1, n] the recorded data (this rank's shard under torch.distributed; n_total as in parallel.allreduce_mean_packed), theta0 [p] shared by all trajectories.
+        evaluate(theta) is ONE launch - sysid_step with gauss_newton=True: loss, gradient and G = J'J from the sensitivity tiles of the fused kernel - and hands the packed
+        rows, with the count of rows that hold a non-finite entry (a diverged rollout: SysID has no status word), to parallel.mean_row_checked: one all-reduce when a
+        process group exchanges, one copy of p + 3 + p p doubles to the host; a trial with such a row on ANY rank is None on EVERY rank.
+        skip_missing: partial data - a NaN in `states` is an entry that was not observed (encoders without velocities, a sample every k steps); ini_state [B, n] replaces
+        states[:, 0] as the initial state of the rollouts, needed where the first row is not fully observed (a NaN there is a ValueError before any launch)."""
+        from . import parallel
+        torch = rt.torch_cuda()
+        inputs, states = rt.dev(inputs), rt.dev(states)
+        B, T, p = int(inputs.shape[0]), int(inputs.shape[1]), mdl.p
+        assert states.shape == (B, T + 1, mdl.n) and inputs.shape == (B, T, mdl.m)
+        x0 = rt.dev(ini_state).reshape(B, mdl.n).contiguous() if ini_state is not None else None
+        bufs = {}
+
+        def evaluate(theta):
+            out = mdl.sysid_step(inputs, states, theta, gauss_newton=True, skip_missing=skip_missing, ini_state=x0, buffers=bufs)
+            bad = (~torch.isfinite(out["packed_gn"])).any(dim=1)
+            row = parallel.mean_row_checked(out["packed_gn"], bad, n_total)                # (a bad row makes the point None before its sums are read)
+            if row is None:
+                return None
+            return float(row[p]), row[:p].copy(), row[p + 1:].reshape(p, p).copy()
+
+        return cls(evaluate, theta0, **kw)

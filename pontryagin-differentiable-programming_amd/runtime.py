@@ -64,6 +64,7 @@ MODEL_SYMBOLS = ["pdp_model_get_info", "pdp_oc_rollout_batched", "pdp_oc_rollout
                  "pdp_cp_integrate_batched", "pdp_cp_auxsys_batched",
                  "pdp_cp_step_workspace_bytes", "pdp_cp_step_batched", "pdp_sysid_integrate_batched", "pdp_sysid_auxsys_batched", "pdp_sysid_step_batched",
                  "pdp_sysid_step_workspace_bytes", "pdp_sysid_step_ws_batched"]
+MODEL_EXT_SYMBOLS = ["pdp_sysid_step_gn_batched"]        # declared in the extension headers (include/pdp_hip_sysid_gn.h): include/pdp_hip.h is pinned at its entry points
 
 _core = None
 
@@ -279,6 +280,8 @@ _MODEL_SIGS = {
     "pdp_sysid_step_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
     "pdp_sysid_step_workspace_bytes": (_I64, [_I, _I]),
     "pdp_sysid_step_ws_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I64, _VP]),
+    # include/pdp_hip_sysid_gn.h
+    "pdp_sysid_step_gn_batched": (_I, [_I, _I, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I64, _VP]),
 }
 _models = {}
 
@@ -872,15 +875,9 @@ class ModelLib:
         check(self.lib.pdp_sysid_auxsys_batched(B, T, ptr(x), ptr(u), ptr(th), tb, ptr(F), ptr(E), current_stream_ptr()), "pdp_sysid_auxsys_batched")
         return F, E
 
-    def sysid_step(self, u, xobs, theta):
-        """SysID.step per trajectory (pdp_sysid_step_ws_batched).  Models beyond the fused kernels' tiles (n > 16 or p > 64) take the reference's own route kernel by kernel -
-        integrateDyn -> getAuxSys -> integrateAuxSys (size-generic kernels) -> the chain rule of PDP.py:1285-1291 as two tensor contractions: no size is refused."""
+    def _sysid_workspace(self, B, T):
+        """(workspace tensor or None, its bytes) of the fused SysID.step entry points"""
         torch = torch_cuda()
-        u, xobs = dev(u), dev(xobs)
-        B, T = u.shape[0], u.shape[1]
-        th, tb = self._theta(theta, B)
-        loss = torch.empty((B,), dtype=torch.float64, device="cuda")
-        grad = torch.empty((B, self.p), dtype=torch.float64, device="cuda")
         nbytes = int(self.lib.pdp_sysid_step_workspace_bytes(B, T))              # > 0: large batch, the trajectories are rolled out beforehand, one lane each
         ws = None
         if nbytes > 0:
@@ -899,6 +896,27 @@ class ModelLib:
                 pinned.add((B, T))
             for key in [k for k in cache if k not in pinned][:max(0, len(cache) - len(pinned) - 8)]:
                 del cache[key]
+        return ws, nbytes
+
+    def sysid_step(self, u, xobs, theta, gauss_newton=False, skip_missing=False, ini_state=None, buffers=None):
+        """SysID.step per trajectory (pdp_sysid_step_ws_batched): (loss [B], grad [B, p]).  Models beyond the fused kernels' tiles (n > 16 or p > 64) take the reference's own
+        route kernel by kernel - integrateDyn -> getAuxSys -> integrateAuxSys (size-generic kernels) -> the chain rule of PDP.py:1285-1291 as two tensor contractions: no size
+        is refused.
+        gauss_newton: the step as a nonlinear least-squares evaluation (pdp_sysid_step_gn_batched, one launch): returns dict(packed_gn [B, p + 1 + p p] = grad | loss | G
+        per trajectory, and loss [B], grad [B, p], gn [B, p, p] as VIEWS of it), G = sum_t X_t' X_t the Gauss-Newton matrix of the loss (what irl.LMLoop.for_sysid
+        averages).  skip_missing: a NaN in xobs is an entry that was not observed (PDP_GRAD_SKIP_MISSING): loss, gradient and G over the observed entries; a NaN in the
+        initial state the rollouts would start from is a ValueError before any launch.  ini_state [B, n]: the initial state of the rollouts instead of xobs[:, 0]; row 0 then
+        adds |ini_state - xobs_0|^2 to the loss.  skip_missing or ini_state without gauss_newton return (loss, grad) from the same launch.  Beyond the fused kernels' tiles
+        (n > 16 or p > 16) the same row is contracted from the materialised sensitivities.  buffers: a dict the caller keeps - the output tensors are reused between calls."""
+        if gauss_newton or skip_missing or ini_state is not None:
+            return self._sysid_step_gn(u, xobs, theta, gauss_newton, skip_missing, ini_state, buffers)
+        torch = torch_cuda()
+        u, xobs = dev(u), dev(xobs)
+        B, T = u.shape[0], u.shape[1]
+        th, tb = self._theta(theta, B)
+        loss = torch.empty((B,), dtype=torch.float64, device="cuda")
+        grad = torch.empty((B, self.p), dtype=torch.float64, device="cuda")
+        ws, nbytes = self._sysid_workspace(B, T)
         rc = self.lib.pdp_sysid_step_ws_batched(B, T, ptr(u), ptr(xobs), ptr(th), tb, ptr(loss), ptr(grad), ptr(ws), nbytes, current_stream_ptr())
         if rc == -2:
             x = self.sysid_integrate(xobs[:, 0].contiguous(), u, th)
@@ -908,6 +926,48 @@ class ModelLib:
             return (d * d).sum(dim=(1, 2)), torch.einsum("bti,btip->bp", d, X)
         check(rc, "pdp_sysid_step_ws_batched")
         return loss, grad
+
+    def _sysid_step_gn(self, u, xobs, theta, gauss_newton, skip_missing, ini_state, buffers):
+        if skip_missing:                            # judged on what the caller gave (a host array is not moved to the device first)
+            first = ini_state if ini_state is not None else (xobs if hasattr(xobs, "data_ptr") else np.asarray(xobs, dtype=float))[:, 0]
+            if bool(first.isnan().any()) if hasattr(first, "data_ptr") else bool(np.isnan(np.asarray(first, dtype=float)).any()):
+                raise ValueError("sysid_step: skip_missing=True and the initial state (%s) holds a NaN: give ini_state [B, n]"
+                                 % ("xobs[:, 0]" if ini_state is None else "ini_state"))
+        torch = torch_cuda()
+        u, xobs = dev(u), dev(xobs)
+        B, T, n, p = u.shape[0], u.shape[1], self.n, self.p
+        x0 = dev(ini_state).reshape(B, n).contiguous() if ini_state is not None else None
+        th, tb = self._theta(theta, B)
+        bufs = buffers if buffers is not None else {}
+
+        def buf(key, shape):
+            t = bufs.get(key)
+            if t is None or tuple(t.shape) != tuple(shape):
+                t = bufs[key] = torch.empty(shape, dtype=torch.float64, device="cuda")
+            return t
+        loss, packed = buf("loss", (B,)), buf("packed_gn", (B, p + 1 + p * p))
+        ws, nbytes = self._sysid_workspace(B, T)
+        rc = self.lib.pdp_sysid_step_gn_batched(B, T, ptr(u), ptr(xobs), ptr(x0), ptr(th), tb, 32 if skip_missing else 0, ptr(loss), ptr(packed), ptr(ws), nbytes,
+                                                current_stream_ptr())
+        if rc == -2:                                # beyond the fused kernels' tiles: the same row from the materialised sensitivities
+            x = self.sysid_integrate(x0 if x0 is not None else xobs[:, 0].contiguous(), u, th)
+            F, E = self.sysid_auxsys(x, u, th)
+            X = sysid_aux_integrate(F, E)                                           # [B, T+1, n, p]
+            d = x - xobs
+            if skip_missing:                        # selects, as in the kernels: an observed entry with a non-finite state keeps its NaN in the loss
+                zero = torch.zeros((), dtype=torch.float64, device="cuda")
+                packed[:, p] = torch.where(xobs == xobs, d * d, zero).sum(dim=(1, 2))
+                obs = d == d
+                d, X = torch.where(obs, d, zero), torch.where(obs[..., None], X, zero)
+            else:
+                packed[:, p] = (d * d).sum(dim=(1, 2))
+            packed[:, :p] = torch.einsum("bti,btip->bp", d, X)
+            packed[:, p + 1:] = torch.einsum("btip,btiq->bpq", X, X).reshape(B, p * p)
+            rc = 0
+        check(rc, "pdp_sysid_step_gn_batched")
+        if not gauss_newton:
+            return packed[:, p], packed[:, :p]
+        return dict(packed_gn=packed, loss=packed[:, p], grad=packed[:, :p], gn=packed[:, p + 1:].view(B, p, p))
 
 
 def load_model(path):
