@@ -1,0 +1,124 @@
+// pdp_chain_rule.h - the chain rule of the sum-of-squares loss through the sensitivity tiles of a forward sweep, once, for the four fused units:
+// oc_pdp_fused_kernel (pdp_model_kernels.h), oc_pdp_fused3_kernel (pdp_fused3_kernels.h), sysid_step_kernel (pdp_model_kernels.h) and sysid_step2_kernel
+// (pdp_cp_pair_kernels.h).  With the residuals d_t = x_t - x_demo,t (OC: also u_t - u_demo,t) and the sensitivities X_t = dx_t/dtheta, U_t = du_t/dtheta:
+//     loss = sum_t |d_t|^2      grad = sum_t d_t' X_t (+ d_t' U_t)      G = sum_t X_t' X_t (+ U_t' U_t)   (Gauss-Newton, J'J)
+// A unit's lane-per-step pass leaves d_t in the DLX / DLU slots of its LDS pool row (residual_slot); its sensitivity loop gathers them as the tiles DX, DU - the
+// residual of a row broadcast over its columns, element-aligned with X_t, U_t - and contracts step by step (contract_step); the stage T, which no pool row
+// holds, goes through the dlT staging and the same mask (observed).  Everything is forced inline, and NO ADDRESS
+// IS FORMED INSIDE A HELPER (no pointer parameter is indexed; a reference names one element the caller chose): an address formed in a helper is simplified on its
+// own before the helper is inlined and then no longer folds with the kernel's other addresses as its own text did.  That is why the terminal row's loop over
+// dlT[row] stays in the kernels - as terminal_row(dlT, ...) it changed the LDS addressing, and with it the instructions, of the frozen instantiations, which
+// are to compile to what they compiled to with the text in place (profiles/chain_rule_code_object_diff.txt).
+//
+// The modes - a template parameter of the kernels, never a run-time branch; an instantiation contains only its own arms:
+//   PDP_FUSED_PLAIN  loss and gradient of the demonstration loss (the frozen default);
+//   PDP_FUSED_RIC    the same with the Riccati / prediction records (and, fused3, every sensitivity output) written;
+//   PDP_FUSED_COT    PDP_OC_COTANGENT: demo_x / demo_u carry the cotangents gx = dL/dx [B][T+1][n], gu = dL/du [B][T][m] of a caller's scalar loss L(x, u) and go
+//                    into the slots as they are, so that grad = sum_t gx_t' X_t + gu_t' U_t is the vector-Jacobian product of L through the OC solution,
+//                    contracted in the same order into the same accumulators.  No loss is formed (`loss` may be NULL); gx[b][0] is never loaded (X_0 = 0).
+//   PDP_FUSED_GN     PDP_GRAD_GAUSS_NEWTON: PDP_FUSED_PLAIN plus one accumulator tile Gn += X_t' X_t + U_t' U_t (the tiles are in registers anyway).  Both MFMA
+//                    operands are the same tile: G[i][j] and G[j][i] are the same products in the same order, symmetric to the bit.  grad is then ONE PACKED ROW
+//                    per trajectory, [B][p + 1 + p p] = gradient | loss | G row-major.  OC tiles carry the parameter block in rows and columns M .. M + p - 1.
+//   PDP_FUSED_MISS, PDP_FUSED_GN_MISS   PDP_GRAD_SKIP_MISSING on PDP_FUSED_PLAIN / PDP_FUSED_GN: a NaN in demo_x / demo_u is an entry that was not observed.  No
+//                    change of the LDS layout: the NaN left in the slot in place of the residual IS the mark (nothing is added to the loss for it), and the
+//                    sensitivity loop SELECTS 0.0 for the residual and for the row of X_t / U_t wherever the residual tile is NaN (a compare and a select per tile
+//                    register; never a product with 0: 0 inf must not appear) before it contracts.  Both operands of every G product carry the same row mask.
+//                    The recursion itself and tile_finite keep looking at the unmasked sensitivities.
+//   PDP_SYSID_PLAIN  loss and gradient of SysID.step (no control part; NT parameter tiles of 16 columns, parameters at column 0);
+//   PDP_SYSID_GN     as PDP_FUSED_GN (G = sum_{t<=T} X_t' X_t); the rollout starts from the trailing argument x0 [B][NX] (NULL: x_obs[:, 0]), and row 0 adds
+//                    |x0 - x_obs_0|^2 to the loss and - X_0 = 0 - nothing to gradient and G;
+//   PDP_SYSID_GN_MISS   PDP_SYSID_GN with the semantics of PDP_GRAD_SKIP_MISSING.  An OBSERVED entry whose own state is not finite leaves a NaN in the loss: a
+//                    diverged rollout stays visible (there is no status word here).
+//                    Both SysID Gauss-Newton modes exist for one parameter tile only (NT == 1, p <= 16: what irl.lm_step solves on the host).
+#pragma once
+#include "pdp_tile.h"
+
+#define PDP_FUSED_PLAIN 0
+#define PDP_FUSED_RIC 1
+#define PDP_FUSED_COT 2
+#define PDP_FUSED_GN 3
+#define PDP_FUSED_MISS 4
+#define PDP_FUSED_GN_MISS 5
+
+#define PDP_SYSID_PLAIN 0
+#define PDP_SYSID_GN 1
+#define PDP_SYSID_GN_MISS 2
+
+namespace pdp {
+
+// what the residual slot holds and what it adds to the loss.  The two MISS rules differ only in WHICH NaN marks an entry that was not observed: the
+// demonstration's own (OC units) or the difference's (SysID units); nothing but the select (observed) ever reads it.
+enum Residual { RES_PLAIN, RES_MISS, RES_MISS_DIFF };
+
+template <int MODE>
+struct FusedMode {
+    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT || MODE == PDP_FUSED_GN || MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS,
+                  "instantiation");
+    static constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT, GN = MODE == PDP_FUSED_GN || MODE == PDP_FUSED_GN_MISS;
+    static constexpr bool MISS = MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS;
+    static constexpr Residual RES = MISS ? RES_MISS : RES_PLAIN;          // (COT forms no residual: the cotangent takes the slot as it is)
+};
+template <int MODE, int NT, int NINI>                      // NT parameter tiles, NINI trailing kernel arguments (the x0 of the Gauss-Newton modes)
+struct SysidMode {
+    static_assert(MODE == PDP_SYSID_PLAIN || (NT == 1 && NINI == 1 && (MODE == PDP_SYSID_GN || MODE == PDP_SYSID_GN_MISS)), "instantiation");
+    static constexpr bool GN = MODE != PDP_SYSID_PLAIN, MISS = MODE == PDP_SYSID_GN_MISS;
+    static constexpr Residual RES = MISS ? RES_MISS_DIFF : RES_PLAIN;
+};
+
+// ---- the residual-slot rule.  v: the state / control entry; dd: the demonstration's entry.  residual_value is what goes into
+// the slot, residual_square its share of the loss (a missing entry: none).  residual_slot does both for one entry, the store between them as the kernels
+// always had it; `slot` is the caller's LDS element - no address is formed in here.
+template <Residual RES>
+PDP_DEV double residual_value(double v, double dd) {
+    if constexpr (RES == RES_MISS) { const double d = v - dd; return dd == dd ? d : dd; }
+    else return v - dd;
+}
+template <Residual RES>
+PDP_DEV double residual_square(double d, double dd) {
+    if constexpr (RES == RES_PLAIN) return d * d;
+    else return dd == dd ? d * d : 0.0;
+}
+template <Residual RES>
+PDP_DEV void residual_slot(double& slot, double v, double dd, double& lsum) {
+    const double d = residual_value<RES>(v, dd);
+    slot = d;
+    lsum += residual_square<RES>(d, dd);
+}
+
+// ---- the select-don't-multiply mask: v where the residual d of its row was observed; MISS: 0.0 where d is NaN (never a product with 0: 0 inf must not appear)
+template <bool MISS>
+PDP_DEV double observed(double d, double v) {
+    if constexpr (MISS) return d == d ? v : 0.0;
+    else return v;
+}
+
+// ---- Gn + X' X: both MFMA operands are the same tile.  SMALL (n <= 4): X lives on register 0 of its tile
+template <bool SMALL>
+PDP_DEV d4 gram_add(const d4 X, d4 Gn) {
+    if constexpr (SMALL) return mma_tn_r0(X, X, Gn);
+    else return mma_tn(X, X, Gn);
+}
+
+// ---- one step of the sensitivity loop.  DX, DU: the residual tiles of the step; X, U: its sensitivity tiles.  NR: the registers of DX that carry residuals
+// (n <= 4: 1); U (m <= 4 rows) lives on register 0.  mask_step, once per step of the OC units: with MISS the residuals and the sensitivity rows selected to 0 where
+// the residual is NaN (the selects are spelled on the tile elements, not through observed(): the form the kernels compiled from).  The SysID units have no control
+// part - contract_step without DU, U and gram_add, not a zero tile that would cost an MFMA - and keep the three lines of their MISS arm in their own text: through
+// mask_step their skip-missing instantiations gained or lost one to three instructions (profiles/chain_rule_code_object_diff.txt).
+template <bool MISS, int NR>
+PDP_DEV void mask_step(d4& DX, d4& DU, const d4 X, const d4 U, d4& Xm, d4& Um) {      // Xm, Um: X, U with MISS' mask
+    if constexpr (MISS) {
+        Xm = zero4(); Um = zero4();
+#pragma unroll
+        for (int r = 0; r < NR; ++r) { const bool obs = DX[r] == DX[r]; Xm[r] = obs ? X[r] : 0.0; DX[r] = obs ? DX[r] : 0.0; }
+        { const bool obs = DU[0] == DU[0]; Um[0] = obs ? U[0] : 0.0; DU[0] = obs ? DU[0] : 0.0; }
+    } else { Xm = X; Um = U; }
+}
+// Gn + X' X + U' U (without U: gram_add).  Called under `if constexpr (GN)`: an instantiation without G must not name its Gn tile inside the step's lambda (the
+// capture alone changes the code of the frozen instantiations)
+template <bool SMALL>
+PDP_DEV d4 gram_step(const d4 X, const d4 U, d4 Gn) { return mma_tn_r0(U, U, gram_add<SMALL>(X, Gn)); }
+// this lane's share of the gradient: DX . X (+ DU . U, the same left-to-right sum)
+PDP_DEV double contract_step(const d4 DX, const d4 X) { return DX[0] * X[0] + DX[1] * X[1] + DX[2] * X[2] + DX[3] * X[3]; }
+PDP_DEV double contract_step(const d4 DX, const d4 DU, const d4 X, const d4 U) { return contract_step(DX, X) + DU[0] * U[0]; }
+
+}  // namespace pdp

@@ -193,13 +193,12 @@ __global__ void __launch_bounds__(128 * TPW) cp_step_poly2_kernel(int B, int T, 
 // Fused SysID.step (reference PDP/PDP.py:1178-1296: integrateSys with the given controls, getAuxSys, integrateAuxSys X_{t+1} = F X_t + E, chain rule with the
 // prediction error) as the same two-wave pipeline: wave R rolls the model out along the recorded controls, wave S follows a chunk behind with the Jacobians, the
 // prediction errors and the sensitivity recursion.  Same arithmetic in the same order as sysid_step_kernel (bit-identical, tests/test_gpu_cp_pair.py).
-// MODE, Ini: as in sysid_step_kernel (PDP_SYSID_GN / PDP_SYSID_GN_MISS: `grad` is the packed row grad | loss | G, the trailing argument is x0 [B][NX] or NULL).
+// MODE, Ini: as in sysid_step_kernel (pdp_chain_rule.h).
 template <class Mdl, int NT, int TPW, int MODE = PDP_SYSID_PLAIN, class... Ini>
 __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, const double* __restrict__ u, const double* __restrict__ xobs,
                                                                  const double* __restrict__ theta, int tb, double* __restrict__ loss, double* __restrict__ grad, int slice,
                                                                  Ini... ini) {
-    static_assert(MODE == PDP_SYSID_PLAIN || (NT == 1 && sizeof...(Ini) == 1 && (MODE == PDP_SYSID_GN || MODE == PDP_SYSID_GN_MISS)), "sysid_step2_kernel: MODE");
-    constexpr bool GN = MODE != PDP_SYSID_PLAIN, MISS = MODE == PDP_SYSID_GN_MISS;
+    using SM = SysidMode<MODE, NT, sizeof...(Ini)>;
     constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP, CH = Mdl::CHUNK;
     constexpr int NC = 1 + Mdl::PATH_NCONST, DLX = Mdl::PATH_NVAR, STRIDE = (Mdl::PATH_NVAR + NX) | 1;
     static_assert(TPW == 1 || TPW == 2 || TPW == 4, "trajectories per workgroup");
@@ -232,7 +231,7 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
         double xc[NX], xn[NX], uc[NU], un[NU];
 #pragma unroll
         for (int i = 0; i < NX; ++i) xc[i] = ob[i];                       // ini_state = batch_states[i][0] (PDP.py:1269)
-        if constexpr (GN) {
+        if constexpr (SM::GN) {
             if (const double* x0 = sysid_ini(ini...)) {
 #pragma unroll
                 for (int i = 0; i < NX; ++i) xc[i] = x0[(int64_t)bb * NX + i];
@@ -281,10 +280,7 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
                 double xc[NX], uc[NU];
                 double* row = pool + lane * STRIDE;
 #pragma unroll
-                for (int i = 0; i < NX; ++i) {
-                    if constexpr (!MISS) { xc[i] = xs[t * NX + i]; double d = xc[i] - ob[t * NX + i]; row[DLX + i] = d; lsum += d * d; }
-                    else { xc[i] = xs[t * NX + i]; const double o = ob[t * NX + i], d = xc[i] - o; row[DLX + i] = d; lsum += o == o ? d * d : 0.0; }
-                }
+                for (int i = 0; i < NX; ++i) { xc[i] = xs[t * NX + i]; residual_slot<SM::RES>(row[DLX + i], xc[i], ob[t * NX + i], lsum); }
 #pragma unroll
                 for (int i = 0; i < NU; ++i) uc[i] = us[t * NU + i];
                 PackedSink s{row};
@@ -297,15 +293,15 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
                     d4 E = gather_tile(blk, gE[j], tl);
-                    if constexpr (MISS) {
+                    if constexpr (SM::MISS) {         // (pdp_chain_rule.h: mask_step, in this kernel's own text; NT == 1)
                         d4 Xm;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) { const bool obs = DX[r] == DX[r]; Xm[r] = obs ? X[j][r] : 0.0; DX[r] = obs ? DX[r] : 0.0; }
-                        acc[j] += DX[0] * Xm[0] + DX[1] * Xm[1] + DX[2] * Xm[2] + DX[3] * Xm[3];
-                        Gn = mma_tn(Xm, Xm, Gn);
+                        acc[j] += contract_step(DX, Xm);
+                        Gn = gram_add<false>(Xm, Gn);
                     } else {
-                    acc[j] += DX[0] * X[j][0] + DX[1] * X[j][1] + DX[2] * X[j][2] + DX[3] * X[j][3];
-                    if constexpr (GN) Gn = mma_tn(X[j], X[j], Gn);
+                    acc[j] += contract_step(DX, X[j]);
+                    if constexpr (SM::GN) Gn = gram_add<false>(X[j], Gn);
                     }
                     X[j] = mma_tn(FT, X[j], E);
                 }
@@ -313,26 +309,25 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
         }
         wg_wait_ge(fl, T);                                   // x_T
         wave_lds_sync();
-        if constexpr (!MISS) {
-        if (lane < NX) { double d = xs[T * NX + lane] - ob[T * NX + lane]; dlT[lane] = d; lsum += d * d; }
-        } else {
-            if (lane < NX) { const double o = ob[T * NX + lane], d = xs[T * NX + lane] - o; dlT[lane] = d; lsum += o == o ? d * d : 0.0; }
+        if (lane < NX) {
+            if constexpr (SM::MISS) { const double o = ob[T * NX + lane]; residual_slot<SM::RES>(dlT[lane], xs[T * NX + lane], o, lsum); }      // (x_obs first, as in sysid_step_kernel)
+            else residual_slot<SM::RES>(dlT[lane], xs[T * NX + lane], ob[T * NX + lane], lsum);
         }
         wave_lds_sync();
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                int row = tile_row(lane, r);
-                if constexpr (MISS) {
+                const int row = tile_row(lane, r);
+                if constexpr (SM::MISS) {              // (observed(), in this kernel's own text: through it two of the five models' instantiations lost an instruction; X_T is masked in place)
                     if (row < NX) { const double d = dlT[row]; const bool obs = d == d; X[j][r] = obs ? X[j][r] : 0.0; acc[j] += (obs ? d : 0.0) * X[j][r]; }
                 } else {
                 if (row < NX) acc[j] += dlT[row] * X[j][r];
                 }
             }
             double a = sum_over_rowgroups(acc[j]);
-            if constexpr (GN) {
-                Gn = mma_tn(X[j], X[j], Gn);               // X_T (MISS: its unobserved rows selected to 0 above)
+            if constexpr (SM::GN) {
+                Gn = gram_add<false>(X[j], Gn);            // X_T
                 if (mine) {
                     if (lane < NP) grad[(int64_t)b * (NP + 1 + NP * NP) + lane] = a;
                     store_dense(grad + (int64_t)b * (NP + 1 + NP * NP) + NP + 1, NP, NP, NP, 0, 0, lane, Gn);
@@ -343,7 +338,7 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
         }
         lsum = wave_sum(lsum);
         if (mine && lane == 0) loss[b] = lsum;
-        if constexpr (GN) { if (mine && lane == 0) grad[(int64_t)b * (NP + 1 + NP * NP) + NP] = lsum; }
+        if constexpr (SM::GN) { if (mine && lane == 0) grad[(int64_t)b * (NP + 1 + NP * NP) + NP] = lsum; }
     }
 }
 

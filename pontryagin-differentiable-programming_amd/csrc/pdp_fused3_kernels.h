@@ -89,18 +89,8 @@ PDP_DEV BufMap f3_store_map(int R, int C, int ld, int coff, int lane) {
 // leaves the Riccati matrices P_{t+1}, W_{t+1} of every stage (PP[t], WW[t] of the reference's lqrSolver, PDP.py:561-580) in `riccati` [B][T][n n + n p + 1] - with
 // dxdp / dudp they give the first-order change of the optimal (x, u, lambda) with theta (pdp_oc_predict_batched) - and all three are written with range-checked
 // buffer stores (an output that is NULL is a resource of size 0).  A template parameter, not a run-time branch: the default kernel keeps its instruction stream.
-// MODE = PDP_FUSED_COT (PDP_OC_COTANGENT; plain gradient only, no sensitivity outputs): demo_x / demo_u carry the cotangents gx = dL/dx [B][T+1][n], gu = dL/du [B][T][m] of
-// a caller's scalar loss L(x, u) and go into the DLX / DLU pool slots as they are - where the default forms x - x_demo, u - u_demo - so that
-// grad = sum_t gx_t' X_t + gu_t' U_t is the vector-Jacobian product of L through the OC solution, contracted in the same order into the same accumulators.
-// No loss is formed (no lsum, no misc[4] share, no hand-over of it: `loss` is not written and may be NULL) and gx[b][0] is never loaded (X_0 = 0).
-// MODE = PDP_FUSED_GN (PDP_GRAD_GAUSS_NEWTON; plain gradient only): the default unit, and in the forward sweep one more accumulator tile Gn += X_t' X_t + U_t' U_t - the
-// Gauss-Newton matrix J'J of the sum-of-squares loss, whose parameter block is rows and columns M .. M + NP - 1 of the tile.  grad is the packed row
-// [B][NP + 1 + NP NP] = gradient | loss | G row-major.  G[i][j] and G[j][i] are the same products in the same order: symmetric to the bit.
-// MODE = PDP_FUSED_MISS / PDP_FUSED_GN_MISS (PDP_GRAD_SKIP_MISSING on the plain / the Gauss-Newton unit): a NaN in demo_x / demo_u is an entry that was not observed.  No
-// change of the LDS layout: the demonstration's NaN, left in the DLX / DLU slot in place of the residual, IS the mark (the evaluator adds nothing to lsum for it), and the runner, which holds the residual
-// tiles DX, DU - the residual of a row broadcast over its columns - element-aligned with the sensitivity tiles Xc, U2, SELECTS 0.0 for both wherever the residual is NaN
-// (a compare and a select per tile register; never a product with 0: 0 inf must not appear) before it contracts them.  Both operands of every G product carry the same
-// row mask: G stays symmetric to the bit.  The terminal row goes the same way through dT / dlT.  tile_finite keeps looking at the unmasked sensitivities.
+// MODE: one of PDP_FUSED_* (pdp_chain_rule.h describes the modes and holds what they change).  Here the evaluator fills the residual slots and owns the loss sum over
+// t < T (handed over in misc[4]; PDP_FUSED_COT: no lsum, no hand-over); the runner contracts, and takes the terminal row through dT / dlT.
 template <class Mdl, int TPW = 4, int MODE = PDP_FUSED_PLAIN>
 __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, int flags, const double* __restrict__ x0, const double* __restrict__ u,
                                                             const double* __restrict__ theta, int tb, const double* __restrict__ demo_x,
@@ -117,10 +107,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
     // the wave index is uniform over the wave - said explicitly, or every pointer derived from it (trajectory, workspace, LDS slice) would be
     // carried per lane and every global access would pay 64-bit VALU address arithmetic
     static_assert(TPW == 1 || TPW == 2 || TPW == 4, "trajectories per workgroup");
-    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT || MODE == PDP_FUSED_GN || MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS,
-                  "instantiation");
-    constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT, GN = MODE == PDP_FUSED_GN || MODE == PDP_FUSED_GN_MISS;
-    constexpr bool MISS = MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS;
+    using FM = FusedMode<MODE>;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, slot = wid & (TPW - 1);
     const bool runner = wid < TPW;
     const int b = blockIdx.x * TPW + slot;
@@ -296,10 +283,10 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
             // Riccati record of a stage (RIC): P_{t+1} [NX x NX] | W_{t+1} [NX x NP] | zero sink
             constexpr int RSZ = oc_riccati_doubles<Mdl>();
             [[maybe_unused]] const BufMap mRP = f3_store_map(NX, NX, NX, 0, lane), mRW = f3_store_map(NX, NP, NP, M, lane);
-            [[maybe_unused]] const auto rsR = PDP_BUF_RSRC(RIC && riccati ? riccati + (int64_t)b * T * RSZ : ws_gain, RIC && riccati ? (int64_t)T * RSZ * 8 : 0);
+            [[maybe_unused]] const auto rsR = PDP_BUF_RSRC(FM::RIC && riccati ? riccati + (int64_t)b * T * RSZ : ws_gain, FM::RIC && riccati ? (int64_t)T * RSZ * 8 : 0);
             // packed fp32 prediction record (PredRec, pdp_model_kernels.h)
             [[maybe_unused]] const PredMaps<Mdl> pm(lane);
-            [[maybe_unused]] const bool precPW = RIC && prec && !(flags & PDP_OC_RECORD_PRIMAL);      // the P | W part of the record is wanted
+            [[maybe_unused]] const bool precPW = FM::RIC && prec && !(flags & PDP_OC_RECORD_PRIMAL);      // the P | W part of the record is wanted
             [[maybe_unused]] const auto rsPR = PDP_BUF_RSRC(precPW ? (void*)(prec + (int64_t)b * T * PredRec<Mdl>::SIZE) : (void*)ws_gain, precPW ? (int64_t)T * PredRec<Mdl>::SIZE * 4 : 0);
             constexpr int RB = 8 * BS;                           // bytes per row
             for (int g = 0; g < nchunk; ++g) {
@@ -330,7 +317,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                     if (tl > 0) { Fn = row_read(rF, imm - RB); Yn = row_read(rY, imm - RB); }
                     RiccatiGains gn;
                     d4 P_old;
-                    if constexpr (RIC) {          // (uniform branches: a store to an absent output would be dropped by its size-0 resource, but still issued - 8 to 13 per step)
+                    if constexpr (FM::RIC) {          // (uniform branches: a store to an absent output would be dropped by its size-0 resource, but still issued - 8 to 13 per step)
                         if (riccati) { buf_store(rsR, (unsigned)(t * RSZ) * 8u, mRP, P); buf_store(rsR, (unsigned)(t * RSZ + NX * NX) * 8u, mRW, W2); }
                         if (precPW) { pred_store(rsPR, (unsigned)(t * PredRec<Mdl>::SIZE) * 4u, pm.P, P); pred_store(rsPR, (unsigned)(t * PredRec<Mdl>::SIZE) * 4u, pm.W, W2); }
                     }
@@ -362,10 +349,12 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         // ---- forward sweep: sensitivities X_t = dx_t/dtheta, U_t, gradient
         double acc = 0.0;
         [[maybe_unused]] double lsum = 0.0;
-        double dT;                                              // terminal residual (COT: terminal cotangent), requested ahead of the loops that hide its latency
+        // The terminal slot value, requested ahead of the loops that hide its latency and squared behind them: the slot rule of pdp_chain_rule.h split in time and
+        // folded into the lane predicate, in this kernel's own text (through residual_value the cotangent and skip-missing instantiations compiled differently)
+        double dT;
         [[maybe_unused]] bool obsT = true;                      // MISS: the terminal entry of this lane was observed (the demonstration's entry is not NaN)
-        if constexpr (COT) dT = lane < NX ? dxb[T * NX + lane] : 0.0;
-        else if constexpr (MISS) { const double dd = lane < NX ? dxb[T * NX + lane] : 0.0; obsT = dd == dd; dT = lane < NX ? (obsT ? xb[T * NX + lane] - dd : dd) : 0.0; }
+        if constexpr (FM::COT) dT = lane < NX ? dxb[T * NX + lane] : 0.0;
+        else if constexpr (FM::MISS) { const double dd = lane < NX ? dxb[T * NX + lane] : 0.0; obsT = dd == dd; dT = lane < NX ? (obsT ? xb[T * NX + lane] - dd : dd) : 0.0; }
         else dT = lane < NX ? xb[T * NX + lane] - dxb[T * NX + lane] : 0.0;
         d4 X2 = z;
         [[maybe_unused]] d4 Gn = z;                             // GN: sum_t X_t' X_t + U_t' U_t
@@ -400,7 +389,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
             [[maybe_unused]] const auto rsSX = PDP_BUF_RSRC(dxdp ? dxdp + (int64_t)b * (T + 1) * NX * NP : ws_gain, dxdp ? (int64_t)(T + 1) * NX * NP * 8 : 0);
             [[maybe_unused]] const auto rsSU = PDP_BUF_RSRC(dudp ? dudp + (int64_t)b * T * NU * NP : ws_gain, dudp ? (int64_t)T * NU * NP * 8 : 0);
             [[maybe_unused]] const PredMaps<Mdl> pmf(lane);
-            [[maybe_unused]] const auto rsPRf = PDP_BUF_RSRC(RIC && prec ? (void*)(prec + (int64_t)b * T * PredRec<Mdl>::SIZE) : (void*)ws_gain, RIC && prec ? (int64_t)T * PredRec<Mdl>::SIZE * 4 : 0);
+            [[maybe_unused]] const auto rsPRf = PDP_BUF_RSRC(FM::RIC && prec ? (void*)(prec + (int64_t)b * T * PredRec<Mdl>::SIZE) : (void*)ws_gain, FM::RIC && prec ? (int64_t)T * PredRec<Mdl>::SIZE * 4 : 0);
             constexpr int RF = 8 * FS;
             static_assert((U & 1) == 0, "the register sets of the unrolled loops alternate: U must be even");
             for (int c = 0; c < nchunkF; ++c) {
@@ -422,18 +411,11 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                     d4 DU = row_read<1>(rDU, imm);
                     d4 U2;
                     riccati_forward(KTc, kc, FT, GT, E2, Xc, U2, Xn);
-                    if constexpr (MISS) {                          // a NaN residual marks a row that was not observed: residual and sensitivity row are selected away
-                        d4 Xm, Um = z;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) { const bool obs = DX[r] == DX[r]; Xm[r] = obs ? Xc[r] : 0.0; DX[r] = obs ? DX[r] : 0.0; }
-                        { const bool obs = DU[0] == DU[0]; Um[0] = obs ? U2[0] : 0.0; DU[0] = obs ? DU[0] : 0.0; }
-                        if constexpr (GN) { Gn = mma_tn(Xm, Xm, Gn); Gn = mma_tn_r0(Um, Um, Gn); }
-                        acc += DX[0] * Xm[0] + DX[1] * Xm[1] + DX[2] * Xm[2] + DX[3] * Xm[3] + DU[0] * Um[0];
-                    } else {
-                    if constexpr (GN) { Gn = mma_tn(Xc, Xc, Gn); Gn = mma_tn_r0(U2, U2, Gn); }
-                    acc += DX[0] * Xc[0] + DX[1] * Xc[1] + DX[2] * Xc[2] + DX[3] * Xc[3] + DU[0] * U2[0];
-                    }
-                    if constexpr (RIC) {
+                    d4 Xm = Xc, Um = U2;
+                    mask_step<FM::MISS, 4>(DX, DU, Xc, U2, Xm, Um);
+                    if constexpr (FM::GN) Gn = gram_step<false>(Xm, Um, Gn);
+                    acc += contract_step(DX, DU, Xm, Um);
+                    if constexpr (FM::RIC) {
                         if (dxdp || dudp) {
                             buf_store(rsSX, (unsigned)(t * NX * NP) * 8u, mSX, Xc);
                             buf_store<1>(rsSU, (unsigned)(t * NU * NP) * 8u, mSU, U2);
@@ -487,28 +469,18 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         wave_lds_sync();
         if (lane < NX) {
             dlT[lane] = dT;
-            if constexpr (MISS) lsum += obsT ? dT * dT : 0.0;
-            else if constexpr (!COT) lsum += dT * dT;
+            if constexpr (FM::MISS) lsum += obsT ? dT * dT : 0.0;
+            else if constexpr (!FM::COT) lsum += dT * dT;
         }
         wave_lds_sync();
         [[maybe_unused]] d4 X2m = z;                            // MISS: X_T with the rows that were not observed selected away
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int row = tile_row(lane, r);
-            if constexpr (MISS) {
-                if (row < NX) { const double d = dlT[row]; const bool obs = d == d; X2m[r] = obs ? X2[r] : 0.0; acc += (obs ? d : 0.0) * X2m[r]; }
-            } else {
-            if (row < NX) acc += dlT[row] * X2[r];
-            }
-        }
+        for (int r = 0; r < 4; ++r) { const int row = tile_row(lane, r); if (row < NX) { const double d = dlT[row]; X2m[r] = observed<FM::MISS>(d, X2[r]); acc += observed<FM::MISS>(d, d) * X2m[r]; } }
         if (dxdp) store_dense(dxdp + ((int64_t)b * (T + 1) + T) * NX * NP, NX, NP, NP, 0, M, lane, X2);
         finite = finite && tile_finite(X2);
-        if constexpr (GN) {                                     // X_T
-            if constexpr (MISS) Gn = mma_tn(X2m, X2m, Gn);
-            else Gn = mma_tn(X2, X2, Gn);
-        }
+        if constexpr (FM::GN) Gn = gram_add<false>(FM::MISS ? X2m : X2, Gn);      // X_T
         acc = sum_over_rowgroups(acc);
-        if constexpr (COT) {                                    // no loss, no packed row (PDP_E_ARG at the entry point), nothing to wait for: every chunk has been consumed
+        if constexpr (FM::COT) {                                // no loss, no packed row (PDP_E_ARG at the entry point), nothing to wait for: every chunk has been consumed
             if (lane >= M && lane < M + NP) grad[(int64_t)b * NP + (lane - M)] = acc;
         } else {
         lsum = wave_sum(lsum);
@@ -517,7 +489,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         F3_W1();
         lsum += misc[4];                                        // the evaluator's share: sum over t < T of |x - xd|^2 + |u - ud|^2
         // PDP_OC_PACKED: grad is [B][NP + 1] with the loss in the last column - the row the data-parallel iteration all-gathers
-        if constexpr (GN) {                                     // the packed row gradient | loss | G (PDP_OC_PACKED is PDP_E_ARG at the entry point)
+        if constexpr (FM::GN) {                                 // the packed row gradient | loss | G (PDP_OC_PACKED is PDP_E_ARG at the entry point)
             double* row = grad + (int64_t)b * (NP + 1 + NP * NP);
             if (lane >= M && lane < M + NP) row[lane - M] = acc;
             if (lane == 0) { loss[b] = lsum; row[NP] = lsum; }
@@ -671,16 +643,14 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
 #pragma unroll
                     for (int i = 0; i < NX; ++i) {
                         xc[i] = xb[t * NX + i];
-                        if constexpr (COT) row[DLX + i] = t > 0 ? dxb[t * NX + i] : 0.0;       // gx_0 multiplies X_0 = 0: not loaded
-                        else if constexpr (MISS) { const double dd = dxb[t * NX + i], d = xc[i] - dd; row[DLX + i] = dd == dd ? d : dd; lsum += dd == dd ? d * d : 0.0; }
-                        else { double d = xc[i] - dxb[t * NX + i]; row[DLX + i] = d; lsum += d * d; }
+                        if constexpr (FM::COT) row[DLX + i] = t > 0 ? dxb[t * NX + i] : 0.0;       // the cotangent takes the slot as it is; gx_0 multiplies X_0 = 0: not loaded
+                        else residual_slot<FM::RES>(row[DLX + i], xc[i], dxb[t * NX + i], lsum);
                     }
 #pragma unroll
                     for (int i = 0; i < NU; ++i) {
                         uc[i] = ub[t * NU + i];
-                        if constexpr (COT) row[DLU + i] = dub[t * NU + i];
-                        else if constexpr (MISS) { const double dd = dub[t * NU + i], d = uc[i] - dd; row[DLU + i] = dd == dd ? d : dd; lsum += dd == dd ? d * d : 0.0; }
-                        else { double d = uc[i] - dub[t * NU + i]; row[DLU + i] = d; lsum += d * d; }
+                        if constexpr (FM::COT) row[DLU + i] = dub[t * NU + i];
+                        else residual_slot<FM::RES>(row[DLU + i], uc[i], dub[t * NU + i], lsum);
                     }
                     PackedSink s{row};
                     Mdl::eval_fwd(xc, uc, nullptr, th, pc, s);
@@ -691,7 +661,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                 wg_signal(fl + 2, g + 1);
             }
         }
-        if constexpr (!COT) {
+        if constexpr (!FM::COT) {
         lsum = wave_sum(lsum);
         if (lane == 0) misc[4] = lsum;
         wg_signal(fl + 4, 1);

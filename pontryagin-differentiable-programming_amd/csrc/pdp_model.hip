@@ -100,6 +100,10 @@ int oc_predict_rec(int B, int T, const double* dth, int dtb, const float* rec, d
         return launch(oc_predict_rec_kernel<Mdl>, dim3((unsigned)((int64_t)B * ((T + 3) / 4))), dim3(64), 0, S(st), B, T, dth, dtb, rec, x, u, lam);
     } else { return Mdl::KIND == PDP_KIND_OC ? PDP_E_SIZE : PDP_E_MODE; }
 }
+// the instantiations of the two fused OC kernels, PDP_FUSED_PLAIN last: with_int's fallback
+template <class F>
+inline int with_fused_mode(int mode, F&& f) { return with_int<PDP_FUSED_RIC, PDP_FUSED_COT, PDP_FUSED_GN, PDP_FUSED_MISS, PDP_FUSED_GN_MISS, PDP_FUSED_PLAIN>(mode, f); }
+
 template <class Mdl>
 int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const double* th, int tb, const double* dx, const double* du, double* x,
            double* lam, double* loss, double* grad, double* dxdp, double* dudp, double* ric, float* prec, int32_t* status, void* ws, int64_t wsb, void* st) {
@@ -130,12 +134,12 @@ int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const dou
             if (variant == 3 && fused3_ok<Mdl>(T)) {
                 static const int tpw_env = env_int("PDP_FUSED_TPW", 0);          // (overrides the batch rule)
                 const int tpw = tpw_env ? tpw_env : traj_per_workgroup(B, device_cu_count(), 4);
-                return with_int<PDP_FUSED_RIC, PDP_FUSED_COT, PDP_FUSED_GN, PDP_FUSED_MISS, PDP_FUSED_GN_MISS, PDP_FUSED_PLAIN>(mode(sens), [&](auto MODE) {
+                return with_fused_mode(mode(sens), [&](auto MODE) {
                     return with_int<1, 2, 4>(tpw, [&](auto K) { return run(oc_pdp_fused3_kernel<Mdl, K(), MODE()>, (B + K() - 1) / K(), 128 * K(), K() * 40 * 1024); });
                 });
             }
         }
-        return with_int<PDP_FUSED_COT, PDP_FUSED_GN, PDP_FUSED_RIC, PDP_FUSED_MISS, PDP_FUSED_GN_MISS, PDP_FUSED_PLAIN>(mode(records), [&](auto MODE) { return run(oc_pdp_fused_kernel<Mdl, MODE()>, B, 64, lds); });
+        return with_fused_mode(mode(records), [&](auto MODE) { return run(oc_pdp_fused_kernel<Mdl, MODE()>, B, 64, lds); });
     } else { return Mdl::KIND == PDP_KIND_OC ? PDP_E_SIZE : PDP_E_MODE; }
 }
 

@@ -18,6 +18,7 @@
 #include "pdp_riccati_small.h"
 #include "pdp_policy.h"
 #include "pdp_wave.h"
+#include "pdp_chain_rule.h"
 
 namespace pdp {
 
@@ -570,23 +571,7 @@ __host__ __device__ inline size_t fused_lds_bytes(int T) {
     return sizeof(double) * (size_t)(RICCATI_SCRATCH + FusedLayout<Mdl>::NC + fused_pool_doubles<Mdl>(T) + Mdl::NX + Mdl::NP + Mdl::NPC + 8);
 }
 
-// instantiations of the fused OC unit (oc_pdp_fused_kernel here, oc_pdp_fused3_kernel in pdp_fused3_kernels.h) - a template parameter, never a run-time branch:
-//   PDP_FUSED_PLAIN  loss and gradient of the demonstration loss (the frozen default);
-//   PDP_FUSED_RIC    the same with the Riccati / prediction records (and, fused3, every sensitivity output) written;
-//   PDP_FUSED_COT    PDP_OC_COTANGENT: demo_x / demo_u carry the cotangents gx = dL/dx [B][T+1][n], gu = dL/du [B][T][m] of a caller's loss and take the place of
-//                    x - x_demo, u - u_demo in the contraction: grad = sum_t gx_t' X_t + gu_t' U_t.  No loss is formed (`loss` may be NULL); gx[b][0] is never loaded (X_0 = 0).
-//   PDP_FUSED_GN     PDP_GRAD_GAUSS_NEWTON: PDP_FUSED_PLAIN plus one accumulator tile in the forward sweep, Gn += X_t' X_t + U_t' U_t (the X_t, U_t tiles are in registers
-//                    there): the Gauss-Newton matrix G = J'J of the sum-of-squares loss.  grad is the packed row [B][p + 1 + p p] = gradient | loss | G row-major.
-//   PDP_FUSED_MISS, PDP_FUSED_GN_MISS   PDP_GRAD_SKIP_MISSING on PDP_FUSED_PLAIN / PDP_FUSED_GN: a NaN in demo_x / demo_u is an entry that was not observed.  The lane-per-step
-//                    pass leaves the NaN in the residual's pool slot (DLX / DLU) and adds nothing to the loss for it; the forward sweep selects 0.0 for the residual and for
-//                    the sensitivity row wherever the residual tile DX / DU (element-aligned with X_t / U_t) is NaN, then contracts as before.  Same LDS layout.
-#define PDP_FUSED_PLAIN 0
-#define PDP_FUSED_RIC 1
-#define PDP_FUSED_COT 2
-#define PDP_FUSED_GN 3
-#define PDP_FUSED_MISS 4
-#define PDP_FUSED_GN_MISS 5
-
+// MODE: one of PDP_FUSED_* - a template parameter, never a run-time branch (pdp_chain_rule.h describes the modes and holds what they change)
 template <class Mdl, int MODE = PDP_FUSED_PLAIN>
 __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(int B, int T, int flags, const double* __restrict__ x0, const double* __restrict__ u,
                                                            const double* __restrict__ theta, int tb, const double* __restrict__ demo_x,
@@ -595,10 +580,7 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
                                                            double* __restrict__ dudp, int32_t* __restrict__ status, double* __restrict__ ws_gain,
                                                            double* __restrict__ riccati, float* __restrict__ prec) {
     using L = FusedLayout<Mdl>;
-    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT || MODE == PDP_FUSED_GN || MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS,
-                  "instantiation");
-    constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT, GN = MODE == PDP_FUSED_GN || MODE == PDP_FUSED_GN_MISS;
-    constexpr bool MISS = MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS;
+    using FM = FusedMode<MODE>;
     constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP, CH = L::CH, M = NU;
     constexpr int GSZ = fused_gain_doubles<Mdl>();         // per step: K [NU x NX] | k [NU x NP] | zero sink
     // SMALL (n <= 4: pendulum, cart-pole, robot arm): every matrix of the recursion fits the rows-0..3 register of its tile and every
@@ -754,10 +736,10 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
         // Riccati record of a stage (RIC; see oc_pdp_fused3_kernel): P_{t+1} [NX x NX] | W_{t+1} [NX x NP] | zero sink
         constexpr int RSZ = oc_riccati_doubles<Mdl>();
         [[maybe_unused]] const TileMapBytes mRP = make_tile_map_sink(NX, NX, NX, 0, 0, lane, RSZ - 1), mRW = make_tile_map_sink(NX, NP, NP, 0, M, lane, NX * NP);
-        [[maybe_unused]] double* rw = (RIC && riccati) ? riccati + (int64_t)b * T * RSZ : nullptr;
+        [[maybe_unused]] double* rw = (FM::RIC && riccati) ? riccati + (int64_t)b * T * RSZ : nullptr;
         // prediction record (RIC, fp32, see PredRec): range-checked buffer stores, a NULL record is a resource of size 0
         [[maybe_unused]] const PredMaps<Mdl> pm(lane);
-        [[maybe_unused]] const bool precPW = RIC && prec && !(flags & PDP_OC_RECORD_PRIMAL);      // (PDP_OC_RECORD_PRIMAL: the P | W stores go to a resource of size 0)
+        [[maybe_unused]] const bool precPW = FM::RIC && prec && !(flags & PDP_OC_RECORD_PRIMAL);      // (PDP_OC_RECORD_PRIMAL: the P | W stores go to a resource of size 0)
         [[maybe_unused]] const auto rsPR = PDP_BUF_RSRC(precPW ? (void*)(prec + (int64_t)b * T * PredRec<Mdl>::SIZE) : (void*)ws_gain, precPW ? (int64_t)T * PredRec<Mdl>::SIZE * 4 : 0);
         const bool given = (flags & PDP_OC_GIVEN_TRAJ) != 0;
         // costate tile: column 0 holds lambda_{t+1}; terminal value lambda_T = h_x(x_T)
@@ -872,7 +854,7 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
                 if constexpr (SMALL) {
                     SmallGains g;
                     double Pr = P[0], Wr = W2[0];
-                    if constexpr (RIC) {                     // (P is in rep form: the first column block is P itself, the replicas must not reach the sink slot)
+                    if constexpr (FM::RIC) {                     // (P is in rep form: the first column block is P itself, the replicas must not reach the sink slot)
                         d4 Pt_ = z, Wt_ = z;
                         Pt_[0] = (lane & 12) == 0 ? Pr : 0.0; Wt_[0] = Wr;
                         if (rw) { store_all<1>(rw + t * RSZ, mRP, Pt_); store_all<1>(rw + t * RSZ + NX * NX, mRW, Wt_); }
@@ -889,7 +871,7 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
                 } else {
                 RiccatiGains g;
                 d4 P_old;
-                if constexpr (RIC) {
+                if constexpr (FM::RIC) {
                     if (rw) { store_all(rw + t * RSZ, mRP, P); store_all(rw + t * RSZ + NX * NX, mRW, W2); }
                     pred_store(rsPR, (unsigned)(t * PredRec<Mdl>::SIZE) * 4u, pm.P, P);
                     pred_store(rsPR, (unsigned)(t * PredRec<Mdl>::SIZE) * 4u, pm.W, W2);
@@ -936,7 +918,7 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
         d4 KTn = -load_all<NRT>(gw, mKT);
         d4 kn = -load_all<1>(gw + NX * NU, mIK);
         [[maybe_unused]] const PredMaps<Mdl> pmf(lane);
-        [[maybe_unused]] const auto rsPRf = PDP_BUF_RSRC(RIC && prec ? (void*)(prec + (int64_t)b * T * PredRec<Mdl>::SIZE) : (void*)ws_gain, RIC && prec ? (int64_t)T * PredRec<Mdl>::SIZE * 4 : 0);
+        [[maybe_unused]] const auto rsPRf = PDP_BUF_RSRC(FM::RIC && prec ? (void*)(prec + (int64_t)b * T * PredRec<Mdl>::SIZE) : (void*)ws_gain, FM::RIC && prec ? (int64_t)T * PredRec<Mdl>::SIZE * 4 : 0);
         const int nchunk = (T + CH - 1) / CH;
         const int ch = (T + nchunk - 1) / nchunk;      // chunks of equal length
         for (int c = 0; c < nchunk; ++c) {
@@ -951,16 +933,14 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
 #pragma unroll
                 for (int i = 0; i < NX; ++i) {
                     xc[i] = xb[t * NX + i];
-                    if constexpr (COT) row[DLX + i] = t > 0 ? dxb[t * NX + i] : 0.0;           // gx_0 multiplies X_0 = 0: not loaded
-                    else if constexpr (MISS) { const double dd = dxb[t * NX + i], d = xc[i] - dd; row[DLX + i] = dd == dd ? d : dd; lsum += dd == dd ? d * d : 0.0; }
-                    else { double d = xc[i] - dxb[t * NX + i]; row[DLX + i] = d; lsum += d * d; }
+                    if constexpr (FM::COT) row[DLX + i] = t > 0 ? dxb[t * NX + i] : 0.0;       // the cotangent takes the slot as it is; gx_0 multiplies X_0 = 0: not loaded
+                    else residual_slot<FM::RES>(row[DLX + i], xc[i], dxb[t * NX + i], lsum);
                 }
 #pragma unroll
                 for (int i = 0; i < NU; ++i) {
                     uc[i] = ub[t * NU + i];
-                    if constexpr (COT) row[DLU + i] = dub[t * NU + i];
-                    else if constexpr (MISS) { const double dd = dub[t * NU + i], d = uc[i] - dd; row[DLU + i] = dd == dd ? d : dd; lsum += dd == dd ? d * d : 0.0; }
-                    else { double d = uc[i] - dub[t * NU + i]; row[DLU + i] = d; lsum += d * d; }
+                    if constexpr (FM::COT) row[DLU + i] = dub[t * NU + i];
+                    else residual_slot<FM::RES>(row[DLU + i], uc[i], dub[t * NU + i], lsum);
                 }
                 PackedSink s{row};
                 Mdl::eval_fwd(xc, uc, nullptr, th, pc, s);
@@ -988,28 +968,13 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
                 } else
                 riccati_forward(KTc, kc, FT, GT, E2, Xc, U2, Xn);
                 PDP_FINE(10, t == 20);
-                if constexpr (MISS) {           // a NaN residual marks a row that was not observed: residual and sensitivity row are selected away (SMALL: register 0 only)
-                    d4 Xm = z, Um = z;
-#pragma unroll
-                    for (int r = 0; r < NRT; ++r) { const bool obs = DX[r] == DX[r]; Xm[r] = obs ? Xc[r] : 0.0; DX[r] = obs ? DX[r] : 0.0; }
-                    { const bool obs = DU[0] == DU[0]; Um[0] = obs ? U2[0] : 0.0; DU[0] = obs ? DU[0] : 0.0; }
-                    if constexpr (GN) {
-                        if constexpr (SMALL) Gn = mma_tn_r0(Xm, Xm, Gn);
-                        else Gn = mma_tn(Xm, Xm, Gn);
-                        Gn = mma_tn_r0(Um, Um, Gn);
-                    }
-                    acc += DX[0] * Xm[0] + DX[1] * Xm[1] + DX[2] * Xm[2] + DX[3] * Xm[3] + DU[0] * Um[0];
-                } else {
-                if constexpr (GN) {             // (SMALL: X_t and U_t live on register 0 in the ordinary column layout - parameters in columns M .. - with rows >= n / >= m zero)
-                    if constexpr (SMALL) Gn = mma_tn_r0(Xc, Xc, Gn);
-                    else Gn = mma_tn(Xc, Xc, Gn);
-                    Gn = mma_tn_r0(U2, U2, Gn);
-                }
-                acc += DX[0] * Xc[0] + DX[1] * Xc[1] + DX[2] * Xc[2] + DX[3] * Xc[3] + DU[0] * U2[0];
-                }
+                d4 Xm = Xc, Um = U2;
+                mask_step<FM::MISS, NRT>(DX, DU, Xc, U2, Xm, Um);
+                if constexpr (FM::GN) Gn = gram_step<SMALL>(Xm, Um, Gn);
+                acc += contract_step(DX, DU, Xm, Um);
                 if (dxdp) store_dense(dxdp + ((int64_t)b * (T + 1) + t) * NX * NP, NX, NP, NP, 0, M, lane, Xc);
                 if (dudp) store_dense(dudp + ((int64_t)b * T + t) * NU * NP, NU, NP, NP, 0, M, lane, U2);
-                if constexpr (RIC) {
+                if constexpr (FM::RIC) {
                     pred_store<NRT>(rsPRf, (unsigned)(t * PredRec<Mdl>::SIZE) * 4u, pmf.X, Xn);      // X_{t+1}
                     pred_store<1>(rsPRf, (unsigned)(t * PredRec<Mdl>::SIZE) * 4u, pmf.U, U2);
                 }
@@ -1026,42 +991,30 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
         // terminal term (x_T - xd_T)' X_T   (cartpole_PDP.py:74)
         wave_lds_sync();
         if (lane < NX) {
-            if constexpr (COT) dlT[lane] = dxb[T * NX + lane];
-            else if constexpr (MISS) { const double dd = dxb[T * NX + lane], d = xb[T * NX + lane] - dd; dlT[lane] = dd == dd ? d : dd; lsum += dd == dd ? d * d : 0.0; }
-            else { double d = xb[T * NX + lane] - dxb[T * NX + lane]; dlT[lane] = d; lsum += d * d; }
+            if constexpr (FM::COT) dlT[lane] = dxb[T * NX + lane];
+            else if constexpr (FM::MISS) { const double dd = dxb[T * NX + lane]; residual_slot<FM::RES>(dlT[lane], xb[T * NX + lane], dd, lsum); }      // (the demonstration's entry is asked for first, as it always was here)
+            else residual_slot<FM::RES>(dlT[lane], xb[T * NX + lane], dxb[T * NX + lane], lsum);
         }
         wave_lds_sync();
         [[maybe_unused]] d4 X2m = z;                        // MISS: X_T with the rows that were not observed selected away
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int row = tile_row(lane, r);
-            if constexpr (MISS) {
-                if (row < NX) { const double d = dlT[row]; const bool obs = d == d; X2m[r] = obs ? X2[r] : 0.0; acc += (obs ? d : 0.0) * X2m[r]; }
-            } else {
-            if (row < NX) acc += dlT[row] * X2[r];
-            }
-        }
+        for (int r = 0; r < 4; ++r) { const int row = tile_row(lane, r); if (row < NX) { const double d = dlT[row]; X2m[r] = observed<FM::MISS>(d, X2[r]); acc += observed<FM::MISS>(d, d) * X2m[r]; } }
         if (dxdp) store_dense(dxdp + ((int64_t)b * (T + 1) + T) * NX * NP, NX, NP, NP, 0, M, lane, X2);
         finite = finite && tile_finite(X2);
-        if constexpr (GN) {                                 // X_T, and the packed row's G block (gradient and loss follow below)
-            if constexpr (MISS) {
-                if constexpr (SMALL) Gn = mma_tn_r0(X2m, X2m, Gn);
-                else Gn = mma_tn(X2m, X2m, Gn);
-            } else
-            if constexpr (SMALL) Gn = mma_tn_r0(X2, X2, Gn);
-            else Gn = mma_tn(X2, X2, Gn);
+        if constexpr (FM::GN) {                             // X_T, and the packed row's G block (gradient and loss follow below)
+            Gn = gram_add<SMALL>(FM::MISS ? X2m : X2, Gn);
             store_dense(grad + (int64_t)b * (NP + 1 + NP * NP) + NP + 1, NP, NP, NP, M, M, lane, Gn);
         }
     }
     acc = sum_over_rowgroups(acc);
-    if constexpr (COT) {                                    // no loss, no packed row (PDP_E_ARG at the entry point)
+    if constexpr (FM::COT) {                                // no loss, no packed row (PDP_E_ARG at the entry point)
         if (lane >= M && lane < M + NP) grad[(int64_t)b * NP + (lane - M)] = acc;
     } else {
     lsum = wave_sum(lsum);
     // PDP_OC_PACKED: grad is [B][NP + 1] with the loss in the last column - the row the data-parallel iteration all-gathers
-    const int gstride = GN ? NP + 1 + NP * NP : ((flags & PDP_OC_PACKED) ? NP + 1 : NP);      // (GN: PDP_OC_PACKED is PDP_E_ARG at the entry point)
+    const int gstride = FM::GN ? NP + 1 + NP * NP : ((flags & PDP_OC_PACKED) ? NP + 1 : NP);      // (GN: PDP_OC_PACKED is PDP_E_ARG at the entry point)
     if (lane >= M && lane < M + NP) grad[(int64_t)b * gstride + (lane - M)] = acc;
-    if (lane == 0) { loss[b] = lsum; if (GN || (flags & PDP_OC_PACKED)) grad[(int64_t)b * gstride + NP] = lsum; }
+    if (lane == 0) { loss[b] = lsum; if (FM::GN || (flags & PDP_OC_PACKED)) grad[(int64_t)b * gstride + NP] = lsum; }
     }
     int st = 0;
     if (!__all(finite)) st |= PDP_STATUS_NONFINITE;
@@ -1785,30 +1738,16 @@ __host__ inline int sysid_rows(int B, int T, int cus) {
     const int fit = (160 * 1024 / 8 / 8 - 64 - sysid_slice<Mdl>(T, 0)) / stride;      // (64 doubles of slack for the allocation granularity)
     return fit >= 4 ? (fit < Mdl::CHUNK ? fit : Mdl::CHUNK) : Mdl::CHUNK;
 }
-// MODE of the fused SysID.step kernels (sysid_step_kernel below, sysid_step2_kernel in pdp_cp_pair_kernels.h; pdp_sysid_step_gn_batched selects 1 / 2):
-//   PDP_SYSID_PLAIN    loss and gradient: the code of pdp_sysid_step_batched, unchanged by the other two (their additions sit under `if constexpr`)
-//   PDP_SYSID_GN       plus one accumulator tile Gn += X_t' X_t beside the gradient's acc += DX . X (the X_t tile is in registers anyway; both MFMA operands are the
-//                      same tile, so G = sum_{t<=T} X_t' X_t, X_0 = 0, is symmetric to the bit).  `grad` is then ONE PACKED ROW per trajectory, grad [p] | loss | G [p][p]
-//                      (the layout of PDP_GRAD_GAUSS_NEWTON), and the rollout starts from the trailing argument x0 [B][NX] (NULL: x_obs[:, 0]); row 0 adds
-//                      |x0 - x_obs_0|^2 to the loss and - X_0 = 0 - nothing to gradient and G
-//   PDP_SYSID_GN_MISS  PDP_SYSID_GN where a NaN in x_obs is an entry that was not observed (the semantics of PDP_GRAD_SKIP_MISSING): the lane-per-step pass leaves the
-//                      NaN residual in the DLX slot and adds nothing to the loss for it; the sensitivity loop SELECTS (never multiplies by 0) the residual and the row of
-//                      X_t to 0 where the residual is NaN, for the gradient and for Gn; the recursion X_{t+1} = F X_t + E runs on the unmasked X.  An OBSERVED entry whose own
-//                      state is not finite leaves a NaN in the loss: a diverged rollout stays visible (there is no status word here)
-// Both new modes exist for one parameter tile only (NT == 1, p <= 16: what irl.lm_step solves on the host).
-#define PDP_SYSID_PLAIN 0
-#define PDP_SYSID_GN 1
-#define PDP_SYSID_GN_MISS 2
 PDP_DEV const double* sysid_ini() { return nullptr; }                     // the trailing x0 argument of the Gauss-Newton modes (PDP_SYSID_PLAIN has none)
 PDP_DEV const double* sysid_ini(const double* x0) { return x0; }
 
-// Fused SysID.step per trajectory: rollout (uniform, x kept in LDS) then X_{t+1} = F X_t + E on MFMA tiles.
+// Fused SysID.step per trajectory: rollout (uniform, x kept in LDS) then X_{t+1} = F X_t + E on MFMA tiles.  MODE: one of PDP_SYSID_* (pdp_chain_rule.h;
+// pdp_sysid_step_gn_batched selects PDP_SYSID_GN / PDP_SYSID_GN_MISS).
 template <class Mdl, int NT, bool GIVEN = false, int MODE = PDP_SYSID_PLAIN, class... Ini>
 __global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const double* __restrict__ u, const double* __restrict__ xobs,
                                                          const double* __restrict__ theta, int tb, double* __restrict__ loss, double* __restrict__ grad, int CH,
                                                          const double* __restrict__ xgiven_, Ini... ini) {
-    static_assert(MODE == PDP_SYSID_PLAIN || (NT == 1 && sizeof...(Ini) == 1 && (MODE == PDP_SYSID_GN || MODE == PDP_SYSID_GN_MISS)), "sysid_step_kernel: MODE");
-    constexpr bool GN = MODE != PDP_SYSID_PLAIN, MISS = MODE == PDP_SYSID_GN_MISS;
+    using SM = SysidMode<MODE, NT, sizeof...(Ini)>;
     const double* __restrict__ xgiven = GIVEN ? xgiven_ : nullptr;      // (a template parameter: each instantiation keeps its own register allocation)
     // xgiven [B][T+1][NX] (GIVEN): the trajectory, rolled out beforehand by sysid_integrate_kernel with ONE LANE per trajectory - the mode for batches with several
     // trajectories per SIMD: the rollout below runs one trajectory on all 64 lanes (the same value in every lane), which is the right thing while the SIMD has nothing
@@ -1841,7 +1780,7 @@ __global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const doub
         double xc[NX], xn[NX], uc[NU], un[NU];
 #pragma unroll
         for (int i = 0; i < NX; ++i) xc[i] = ob[i];                       // ini_state = batch_states[i][0] (PDP.py:1269)
-        if constexpr (GN) {
+        if constexpr (SM::GN) {
             if (const double* x0 = sysid_ini(ini...)) {
 #pragma unroll
                 for (int i = 0; i < NX; ++i) xc[i] = x0[(int64_t)b * NX + i];
@@ -1887,10 +1826,7 @@ __global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const doub
             double xc[NX], uc[NU];
             double* row = pool + lane * STRIDE;
 #pragma unroll
-            for (int i = 0; i < NX; ++i) {
-                if constexpr (!MISS) { xc[i] = xg ? xg[t * NX + i] : xs[t * NX + i]; double d = xc[i] - ob[t * NX + i]; row[DLX + i] = d; lsum += d * d; }
-                else { xc[i] = xg ? xg[t * NX + i] : xs[t * NX + i]; const double o = ob[t * NX + i], d = xc[i] - o; row[DLX + i] = d; lsum += o == o ? d * d : 0.0; }
-            }
+            for (int i = 0; i < NX; ++i) { xc[i] = xg ? xg[t * NX + i] : xs[t * NX + i]; residual_slot<SM::RES>(row[DLX + i], xc[i], ob[t * NX + i], lsum); }
 #pragma unroll
             for (int i = 0; i < NU; ++i) uc[i] = xg ? ub[t * NU + i] : us[t * NU + i];
             PackedSink s{row};
@@ -1903,42 +1839,34 @@ __global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const doub
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 d4 E = gather_tile(blk, gE[j], tl);
-                if constexpr (MISS) {
+                if constexpr (SM::MISS) {         // (pdp_chain_rule.h: mask_step, in this kernel's own text; NT == 1)
                     d4 Xm;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { const bool obs = DX[r] == DX[r]; Xm[r] = obs ? X[j][r] : 0.0; DX[r] = obs ? DX[r] : 0.0; }
-                    acc[j] += DX[0] * Xm[0] + DX[1] * Xm[1] + DX[2] * Xm[2] + DX[3] * Xm[3];
-                    Gn = mma_tn(Xm, Xm, Gn);
+                    acc[j] += contract_step(DX, Xm);
+                    Gn = gram_add<false>(Xm, Gn);
                 } else {
-                acc[j] += DX[0] * X[j][0] + DX[1] * X[j][1] + DX[2] * X[j][2] + DX[3] * X[j][3];
-                if constexpr (GN) Gn = mma_tn(X[j], X[j], Gn);
+                acc[j] += contract_step(DX, X[j]);
+                if constexpr (SM::GN) Gn = gram_add<false>(X[j], Gn);
                 }
                 X[j] = mma_tn(FT, X[j], E);
             }
         }
     }
     __syncthreads();
-    if constexpr (!MISS) {
-    if (lane < NX) { double d = (xg ? xg[T * NX + lane] : xs[T * NX + lane]) - ob[T * NX + lane]; dlT[lane] = d; lsum += d * d; }
-    } else {
-        if (lane < NX) { const double o = ob[T * NX + lane], d = (xg ? xg[T * NX + lane] : xs[T * NX + lane]) - o; dlT[lane] = d; lsum += o == o ? d * d : 0.0; }
+    if (lane < NX) {
+        if constexpr (SM::MISS) { const double o = ob[T * NX + lane]; residual_slot<SM::RES>(dlT[lane], xg ? xg[T * NX + lane] : xs[T * NX + lane], o, lsum); }      // (x_obs first, as it always was here)
+        else residual_slot<SM::RES>(dlT[lane], xg ? xg[T * NX + lane] : xs[T * NX + lane], ob[T * NX + lane], lsum);
     }
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int row = tile_row(lane, r);
-            if constexpr (MISS) {
-                if (row < NX) { const double d = dlT[row]; const bool obs = d == d; X[j][r] = obs ? X[j][r] : 0.0; acc[j] += (obs ? d : 0.0) * X[j][r]; }
-            } else {
-            if (row < NX) acc[j] += dlT[row] * X[j][r];
-            }
-        }
+        for (int r = 0; r < 4; ++r) { const int row = tile_row(lane, r); if (row < NX) { const double d = dlT[row]; X[j][r] = observed<SM::MISS>(d, X[j][r]); acc[j] += observed<SM::MISS>(d, d) * X[j][r]; } }      // (MISS: X_T masked in place)
         double a = sum_over_rowgroups(acc[j]);
-        if constexpr (GN) {
+        if constexpr (SM::GN) {
             if (lane < NP) grad[(int64_t)b * (NP + 1 + NP * NP) + lane] = a;
-            Gn = mma_tn(X[j], X[j], Gn);                   // X_T (MISS: its unobserved rows selected to 0 above)
+            Gn = gram_add<false>(X[j], Gn);                // X_T
             store_dense(grad + (int64_t)b * (NP + 1 + NP * NP) + NP + 1, NP, NP, NP, 0, 0, lane, Gn);
         } else {
         if (lane < 16 && 16 * j + lane < NP) grad[(int64_t)b * NP + 16 * j + lane] = a;
@@ -1946,7 +1874,7 @@ __global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const doub
     }
     lsum = wave_sum(lsum);
     if (lane == 0) loss[b] = lsum;
-    if constexpr (GN) { if (lane == 0) grad[(int64_t)b * (NP + 1 + NP * NP) + NP] = lsum; }
+    if constexpr (SM::GN) { if (lane == 0) grad[(int64_t)b * (NP + 1 + NP * NP) + NP] = lsum; }
 }
 
 }  // namespace pdp

@@ -61,3 +61,28 @@ def rel_per_sample(a, b):
     """max_b  max|a_b - b_b| / max|b_b|"""
     a, b = np.asarray(a), np.asarray(b)
     return max(np.abs(a[i] - b[i]).max() / np.abs(b[i]).max() for i in range(a.shape[0]))
+
+
+def run_one_wave_beyond_four_states(margins, tmp_path, worker, f3_cases, judge, judge_oracle, tag):
+    """The one-wave kernel's n > 4 branch (full tiles, not its small-system form): what a long horizon (quadrotor T >= 260) or PDP_FUSED_VARIANT=1 selects where the
+    runner / evaluator kernel runs by default.  The switch is read once per process: one child process runs the calling file's WORKER on two of its runner / evaluator
+    cases - quadrotor B = 5, T = 41, shared theta, rollout: two chunks of the one-wave kernel too, 21 + 20 steps (FusedChunk = the generated CHUNK = 33) - and rocket
+    B = 5, T = 31, given trajectory (CHUNK 28: 16 + 15).  Judged by the calling file's own checks at its own tolerance (the reference is the same process's want_sens
+    output); the oracle where that file compares it: the quadrotor case."""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    cases = [f3_cases[0], f3_cases[3]]
+    assert cases[0][:5] == ("quadrotor", 5, 41, False, False) and cases[1][:5] == ("rocket", 5, 31, False, True)
+    path = str(tmp_path / "variant1.npz")
+    r = subprocess.run([sys.executable, "-c", worker % dict(root=os.path.dirname(here), here=here, cases=cases), path], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       text=True, timeout=300, env=dict(os.environ, PDP_FUSED_VARIANT="1"))
+    assert r.returncode == 0, r.stdout[-3000:]
+    z = np.load(path)
+    for k, case in enumerate(cases):
+        res = {key.split("_", 1)[1]: z[key] for key in z.files if key.startswith("%d_" % k)}
+        judge(margins, "one-wave n > 4 " + tag(case), res)
+        if k == 0:
+            judge_oracle(margins, "one-wave n > 4 " + tag(case), make_inputs(*case[:3]), res, case[3])
+

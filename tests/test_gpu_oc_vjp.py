@@ -127,6 +127,12 @@ def test_one_wave_kernel(margins, case):
         _judge_oracle(margins, "one-wave " + _tag(case), inp, r, per_sample)
 
 
+def test_one_wave_kernel_beyond_four_states(margins, tmp_path):
+    """the one-wave kernel's n > 4 branch in the cotangent mode (oc_vjp_common.run_one_wave_beyond_four_states)"""
+    import oc_vjp_common as c
+    c.run_one_wave_beyond_four_states(margins, tmp_path, WORKER, F3_CASES, _judge, _judge_oracle, _tag)
+
+
 def test_buffers_are_reused_and_the_class_surface_forwards(margins):
     import oc_vjp_common as c
     import torch
