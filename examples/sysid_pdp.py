@@ -11,6 +11,12 @@ gradient, one launch per evaluation) - a handful of evaluations instead of thous
 t = K, 2K, ... only, --observe i,j,... only those state components; every other entry becomes NaN = not observed, and the rollouts start from the recorded initial states.
 
     python examples/sysid_pdp.py --system pendulum --method lm --every 2 --observe 0
+
+--method lm --per-trajectory: one problem PER stored trajectory, each with its own parameter estimate, all advanced in lock-step on the device
+(pdp_amd.irl.BatchedLMLoop.for_sysid: one launch of the fused kernel per evaluation of all problems, one launch that accepts or rejects, damps, solves and terminates per
+problem); prints evaluations, state and final loss per problem.
+
+    python examples/sysid_pdp.py --system pendulum --method lm --per-trajectory
 """
 import argparse
 import os
@@ -50,10 +56,13 @@ def main():
     ap.add_argument("--method", default="gd", choices=["gd", "lm"], help="gd: the reference's gradient descent; lm: Levenberg-Marquardt (at most min(--iters, 100) evaluations)")
     ap.add_argument("--every", type=int, default=1, help="--method lm: only the samples at t = K, 2K, ... are observed")
     ap.add_argument("--observe", default=None, help="--method lm: only these state components are observed (comma-separated indices)")
+    ap.add_argument("--per-trajectory", action="store_true", help="--method lm: one problem per trajectory, all in lock-step on the device (irl.BatchedLMLoop)")
     a = ap.parse_args()
     partial = a.every > 1 or a.observe is not None
     if partial and a.method != "lm":
         ap.error("--every / --observe need --method lm")
+    if a.per_trajectory and a.method != "lm":
+        ap.error("--per-trajectory needs --method lm")
     env, dt = zoo.make_env(a.system, "sysid")
     sid = PDP.SysID(a.system)
     sid.setAuxvarVariable(env.dyn_auxvar)
@@ -68,12 +77,23 @@ def main():
     loss_trace, parameter_trace = [], []
     t0 = time.time()
     if a.method == "lm":
-        from pdp_amd.irl import LMLoop
+        from pdp_amd.irl import BatchedLMLoop, LMLoop
+        masked = None
         if partial:
             comps = [int(c) for c in a.observe.split(",")] if a.observe is not None else list(range(states.shape[2]))
             masked = np.full_like(states, np.nan)
             for t in range(a.every, states.shape[1], a.every):
                 masked[:, t, comps] = states[:, t, comps]
+        if a.per_trajectory:
+            kw = dict(ini_state=states[:, 0], skip_missing=True) if partial else {}
+            r = BatchedLMLoop.for_sysid(sid.model(), inputs, masked if partial else states, theta, max_evals=min(a.iters, 100), loss_tol=1e-20, **kw).run()
+            for k in range(inputs.shape[0]):
+                print("problem %3d  %2d evaluations  %2d rejected  %-9s  loss %.6e -> %.6e  |theta - theta*| = %.2e  theta %s"
+                      % (k, r["evaluations"][k], r["rejected"][k], r["state"][k], r["loss_trace"][k][0], r["loss"][k], np.abs(r["theta"][k] - true_parameter).max(),
+                         np.array2string(r["theta"][k], precision=4)))
+            print("done: %d problems in %d launches, %.2f s; largest final loss %.4e" % (inputs.shape[0], r["launches"], time.time() - t0, np.max(r["loss"])))
+            return r
+        if partial:
             loop = LMLoop.for_sysid(sid.model(), inputs, masked, theta, ini_state=states[:, 0], skip_missing=True)
         else:
             loop = LMLoop.for_sysid(sid.model(), inputs, states, theta)

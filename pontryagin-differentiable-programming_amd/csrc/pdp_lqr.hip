@@ -2,6 +2,7 @@
 //   pdp_lqr_solve_batched            LQR.lqrSolver              (reference PDP/PDP.py:446-615)
 //   pdp_cp_aux_integrate_batched     ControlPlanning.integrateAuxSys (PDP/PDP.py:813-838)
 //   pdp_sysid_aux_integrate_batched  SysID.integrateAuxSys      (PDP/PDP.py:1241-1259)
+//   pdp_lm_update_batched            the Levenberg-Marquardt update of many independent problems (include/pdp_hip_lm.h, pdp_lm_kernels.h)
 // One wavefront (= one 64-thread workgroup) per trajectory; matrices are read from HBM straight into the
 // register tile layout, every product is a chain of v_mfma_f64_16x16x4_f64 (pdp_tile.h / pdp_riccati.h).
 #include <hip/hip_runtime.h>
@@ -9,6 +10,7 @@
 #include "../../include/pdp_hip.h"
 #include "pdp_lqr_kernels.h"
 #include "pdp_lqr_stream_kernels.h"
+#include "pdp_lm_kernels.h"
 #include "pdp_launch.h"
 
 using namespace pdp;
@@ -325,6 +327,18 @@ int pdp_sysid_aux_integrate_batched(int B, int T, int n, int p, const double* F,
     if (B <= 0 || T <= 0 || n <= 0 || p <= 0 || !F || !E || !X) return PDP_E_ARG;
     if (n > 16) return launch(sysid_aux_generic_kernel, dim3((unsigned)(((int64_t)B * p + 63) / 64)), dim3(64), 0, (hipStream_t)stream, B, T, n, p, F, E, X0, X);
     return launch(sysid_aux_kernel, dim3(B, (p + 15) / 16), dim3(64), 0, (hipStream_t)stream, B, T, n, p, F, E, X0, X);
+}
+
+// four problems per wavefront, one wavefront per workgroup: K = 1024 is 256 workgroups, one per CU
+int pdp_lm_update_batched(int K, int S, int p, const double* rows, int rows_bstride, const int32_t* bad, const pdp_lm_schedule* schedule, const pdp_lm_state* state,
+                          void* stream) {
+    if (K <= 0 || S <= 0 || p <= 0 || !rows || !schedule || !state) return PDP_E_ARG;
+    const pdp_lm_state& st = *state;
+    if (!st.theta || !st.trial || !st.lam || !st.current || !st.state || !st.evaluations || !st.rejected || !st.accepted || !st.counters) return PDP_E_ARG;
+    if (!(schedule->up > 0.0) || !(schedule->down > 0.0) || st.trace_len < 0) return PDP_E_ARG;
+    if (p > LM_PMAX) return PDP_E_SIZE;
+    if (rows_bstride < p + 1 + p * p) return PDP_E_ARG;
+    return launch(lm_update_kernel, dim3((unsigned)((K - 1) / 4 + 1)), dim3(64), 0, (hipStream_t)stream, K, S, p, rows, rows_bstride, bad, *schedule, st);
 }
 
 }  // extern "C"

@@ -16,6 +16,10 @@ the Gauss-Newton matrix G = J'J beside the gradient J'r from the sensitivity til
 gradient-descent step, and a handful of them reach what thousands of descent steps do not.  A step is accepted or rejected on the loss: this loop is driven by the host (LMLoop.for_irl reads
 the device once per evaluation: rows and health flags in one copy) and is not graph-replayed.  LMLoop.for_sysid is the same loop on SysID.step, whose loss is a sum of
 squares with no inner solve: one launch per evaluation (pdp_sysid_step_gn_batched), complete or partial (NaN) data.
+
+BatchedLMLoop: MANY independent least-squares problems - a parameter estimate per unit of a fleet, per demonstrator, per segment, per bootstrap resample - advanced in
+lock-step on the device.  The fused units take per-sample parameters and write one row per trajectory anyway; here an evaluation is one launch of the unit for all problems and
+one launch of pdp_lm_update_batched (csrc/pdp_lm_kernels.h) does for all of them what LMLoop.step does on the host.  The host reads an 8-byte counter every few iterations.
 """
 import numpy as np
 
@@ -177,7 +181,7 @@ class LMLoop:
     Schedule: the trial point theta - lm_step(g, G, lam) is accepted iff its loss is finite and strictly below the current one; then lam <- max(lam / down, lam_min), else
     lam <- lam * up.  run() ends at max_evals evaluations, at loss <= loss_tol, or when lam > lam_max - no damping the schedule may try improves the loss any more: the fp64
     floor of the problem, reported as results()["stalled"], not raised.
-    Out of scope: per-sample parameters (the fused unit serves them; the loop is the reference's shared-parameter setting) and a device-resident or graph-captured loop."""
+    One shared-parameter problem, driven by the host; many independent problems with their own parameters, decided on the device: BatchedLMLoop (below)."""
 
     def __init__(self, evaluate, theta0, lam0=1e-3, up=10.0, down=10.0, lam_min=1e-12, lam_max=1e8):
         self.evaluate = evaluate
@@ -314,3 +318,137 @@ class LMLoop:
             return float(row[p]), row[:p].copy(), row[p + 1:].reshape(p, p).copy()
 
         return cls(evaluate, theta0, **kw)
+
+
+class BatchedLMLoop:
+    """K independent Levenberg-Marquardt problems in lock-step, every decision on the device.  evaluate_rows(trial [K S, p], a CUDA tensor at a fixed address: the
+    per-sample parameters) -> (rows [K S, p + 1 + p p] = grad | loss | G per sample, bad int32 [K S] or None), device tensors, no synchronisation; problem k owns the
+    samples k S .. k S + S - 1 (S = samples_per_problem) and its loss, gradient and G are their means.  theta0 [K, p], or [p] with K given: every problem starts there.
+    The schedule is LMLoop's, per problem (runtime.lm_update / include/pdp_hip_lm.h: the exact order, and the two differences - a damped matrix that is exactly singular is
+    a rejected trial, not a least-squares solve; pivoted elimination).  A problem whose initial point cannot be evaluated is FAILED (LMLoop raises there) and the others go
+    on.  step() is one evaluation and one update launch; run() reads counters[1] - problems still START or ACTIVE, one 8-byte copy - every poll_every launches.
+    Made for many problems with few samples each; one problem with thousands of samples is LMLoop's job.  Not graph-captured; samples of one problem do not span ranks
+    (independent problems shard over ranks without any collective)."""
+
+    def __init__(self, evaluate_rows, theta0, samples_per_problem=1, lam0=1e-3, up=10.0, down=10.0, lam_min=1e-12, lam_max=1e8, max_evals=50, loss_tol=0.0, trace_len=None,
+                 K=None):
+        torch = rt.torch_cuda()
+        f64, i32 = dict(dtype=torch.float64, device="cuda"), dict(dtype=torch.int32, device="cuda")
+        th = rt.dev(theta0)
+        if th.dim() == 1:
+            th = th[None].expand(int(K) if K is not None else 1, -1)
+        self.theta = th.contiguous().clone()
+        self.K, self.p = (int(v) for v in self.theta.shape)
+        assert K is None or int(K) == self.K
+        self.S = S = int(samples_per_problem)
+        assert S >= 1 and 1 <= self.p <= 16, "p <= 16 (one 16-lane row per problem)"
+        self.evaluate_rows = evaluate_rows
+        self.schedule = dict(up=float(up), down=float(down), lam_min=float(lam_min), lam_max=float(lam_max), loss_tol=float(loss_tol), max_evals=int(max_evals))
+        L = int(max_evals) + 1 if trace_len is None else int(trace_len)
+        K, p, w = self.K, self.p, self.p + 1 + self.p * self.p
+        self.trial = self.theta.repeat_interleave(S, dim=0).contiguous()
+        self.lam = torch.full((K,), float(lam0), **f64)
+        self.current = torch.zeros((K, w), **f64)
+        self.state, self.evaluations, self.rejected, self.accepted = (torch.zeros((K,), **i32) for _ in range(4))
+        self.accepted_now = torch.zeros((K * S,), **i32)
+        self.loss_trace, self.lambda_trace, self.parameter_trace = torch.zeros((K, L), **f64), torch.zeros((K, L), **f64), torch.zeros((K, L, p), **f64)
+        self.counters = torch.tensor([0, K], dtype=torch.int64, device="cuda")
+        self.after_update = None                # called after every update launch (for_irl: keeps the accepted solutions as the next warm start, on the device)
+        self.launches = 0
+
+    def step(self):
+        """one evaluation of all trial points and one update launch; nothing is read back"""
+        rows, bad = self.evaluate_rows(self.trial)
+        rt.lm_update(rows, self.theta, self.trial, self.lam, self.current, self.state, self.evaluations, self.rejected, self.accepted, self.counters, bad=bad,
+                     accepted_now=self.accepted_now, loss_trace=self.loss_trace, lambda_trace=self.lambda_trace, parameter_trace=self.parameter_trace, **self.schedule)
+        if self.after_update is not None:
+            self.after_update()
+        self.launches += 1
+
+    def active(self):
+        """problems still START or ACTIVE: one 8-byte copy (a synchronisation)"""
+        return int(self.counters[1].item())
+
+    def run(self, max_launches=None, poll_every=4):
+        """steps until no problem is START or ACTIVE (looked at every poll_every launches), at most max_launches of them and never beyond launch max_evals + 1, after
+        which every problem has ended by its budget.  Returns results()."""
+        limit = self.schedule["max_evals"] + 1
+        todo = limit - self.launches if max_launches is None else min(int(max_launches), limit - self.launches)
+        for i in range(max(todo, 0)):
+            self.step()
+            if (i + 1) % max(1, int(poll_every)) == 0 and self.active() == 0:
+                break
+        return self.results()
+
+    def results(self):
+        """host copies (one synchronisation), per problem: loss_trace, parameter_trace, lambda_trace (lists of K arrays over the ACCEPTED points, cut at the trace length),
+        evaluations, rejected, accepted [K], state (names), theta [K, p], loss [K] (of theta; NaN for a FAILED problem); launches"""
+        acc = self.accepted.cpu().numpy()
+        n = np.minimum(acc, self.loss_trace.shape[1])
+        lt, pt, lmt = self.loss_trace.cpu().numpy(), self.parameter_trace.cpu().numpy(), self.lambda_trace.cpu().numpy()
+        state = self.state.cpu().numpy()
+        loss = np.where(acc > 0, self.current[:, self.p].cpu().numpy(), np.nan)
+        return {"loss_trace": [lt[k, :n[k]].copy() for k in range(self.K)], "parameter_trace": [pt[k, :n[k]].copy() for k in range(self.K)],
+                "lambda_trace": [lmt[k, :n[k]].copy() for k in range(self.K)], "evaluations": self.evaluations.cpu().numpy(), "rejected": self.rejected.cpu().numpy(),
+                "accepted": acc, "state": [rt.LM_STATES[v] for v in state], "theta": self.theta.cpu().numpy(), "loss": loss, "launches": self.launches}
+
+    @classmethod
+    def for_sysid(cls, mdl, inputs, states, theta0, samples_per_problem=1, ini_state=None, skip_missing=False, **kw):
+        """One SysID problem per group of samples_per_problem consecutive trajectories: inputs [K S, T, m], states [K S, T+1, n], theta0 [K, p] or [p].  An evaluation is
+        ONE launch of mdl.sysid_step(gauss_newton=True) with the trial points as per-sample parameters; a sample is bad where its row holds a non-finite entry (formed on
+        the device).  skip_missing, ini_state: as in LMLoop.for_sysid (a NaN in the initial state under skip_missing is a ValueError before any launch)."""
+        if skip_missing:                            # judged on what the caller gave (a host array is not moved to the device first)
+            first = ini_state if ini_state is not None else (states if hasattr(states, "data_ptr") else np.asarray(states, dtype=float))[:, 0]
+            if bool(first.isnan().any()) if hasattr(first, "data_ptr") else bool(np.isnan(np.asarray(first, dtype=float)).any()):
+                raise ValueError("BatchedLMLoop.for_sysid: skip_missing=True and the initial state (%s) holds a NaN: give ini_state [B, n]"
+                                 % ("states[:, 0]" if ini_state is None else "ini_state"))
+        torch = rt.torch_cuda()
+        inputs, states = rt.dev(inputs), rt.dev(states)
+        B, T, S = int(inputs.shape[0]), int(inputs.shape[1]), int(samples_per_problem)
+        assert states.shape == (B, T + 1, mdl.n) and inputs.shape == (B, T, mdl.m) and B % S == 0
+        x0 = rt.dev(ini_state).reshape(B, mdl.n).contiguous() if ini_state is not None else None
+        bufs = {}
+
+        def evaluate_rows(trial):
+            out = mdl.sysid_step(inputs, states, trial, gauss_newton=True, skip_missing=skip_missing, ini_state=x0, buffers=bufs)
+            return out["packed_gn"], (~torch.isfinite(out["packed_gn"])).any(dim=1).to(torch.int32)
+
+        return cls(evaluate_rows, theta0, samples_per_problem=S, K=B // S, **kw)
+
+    @classmethod
+    def for_irl(cls, mdl, demo_x, demo_u, theta0, samples_per_problem=1, tol=1e-10, max_iter=300, ini_state=None, skip_missing=False, **kw):
+        """One IRL problem per group of samples_per_problem consecutive demonstrations: demo_x [K S, T+1, n], demo_u [K S, T, m], theta0 [K, p] or [p].  An evaluation
+        solves every demonstration's OC problem at its problem's trial point (oc_solve_ms with per-sample parameters: the first cold, later ones warm from COPIES of the
+        last accepted solutions) and runs the fused unit once with gauss_newton=True.  A sample is bad under LMLoop.for_irl's three conditions: its solve did not
+        converge, reported trouble, or the unit set a status bit.  After the update the accepted solutions are refreshed where the launch accepted the sample's problem
+        (torch.where on accepted_now: no host decision).  skip_missing, ini_state: as in LMLoop.for_irl."""
+        if skip_missing:
+            first = ini_state if ini_state is not None else (demo_x if hasattr(demo_x, "data_ptr") else np.asarray(demo_x, dtype=float))[:, 0]
+            if bool(first.isnan().any()) if hasattr(first, "data_ptr") else bool(np.isnan(np.asarray(first, dtype=float)).any()):
+                raise ValueError("BatchedLMLoop.for_irl: skip_missing=True and the initial state (%s) holds a NaN: give ini_state [B, n]"
+                                 % ("demo_x[:, 0]" if ini_state is None else "ini_state"))
+        torch = rt.torch_cuda()
+        demo_x, demo_u = rt.dev(demo_x), rt.dev(demo_u)
+        B, T, S = int(demo_u.shape[0]), int(demo_u.shape[1]), int(samples_per_problem)
+        assert demo_x.shape == (B, T + 1, mdl.n) and demo_u.shape == (B, T, mdl.m) and B % S == 0
+        x0 = (demo_x[:, 0] if ini_state is None else rt.dev(ini_state).reshape(B, mdl.n)).contiguous()
+        bufs, sols = {}, {"accepted": None, "trial": None}
+        informational = 128 | 512 | 1024 | 2048          # PDP_MS_RESTORED, PDP_MS_PREDICT_REJECTED, PDP_MS_SOC, PDP_MS_WATCHDOG
+
+        def evaluate_rows(trial):
+            s = mdl.oc_solve_ms(x0, trial, T, tol=tol, max_iter=max_iter, warm=sols["accepted"])
+            out = mdl.oc_pdp_grad(s["control"], trial, demo_x, demo_u, x=s["state"], lam=s["costate"], gauss_newton=True, skip_missing=skip_missing, buffers=bufs)
+            sols["trial"] = (s["state"], s["control"], s["costate"])
+            bad = (s["converged_flags"] == 0) | ((s["status"] & ~informational) != 0) | (out["status"] != 0)
+            return out["packed_gn"], bad.to(torch.int32)
+
+        loop = cls(evaluate_rows, theta0, samples_per_problem=S, K=B // S, **kw)
+
+        def keep_accepted():
+            now = (loop.accepted_now != 0)[:, None, None]
+            if sols["accepted"] is None:            # the first launch: every usable problem was accepted; a FAILED one keeps the cold start's all-zero point
+                sols["accepted"] = tuple(torch.where(now, t, torch.zeros_like(t)) for t in sols["trial"])
+            else:
+                sols["accepted"] = tuple(torch.where(now, t, a) for t, a in zip(sols["trial"], sols["accepted"]))
+        loop.after_update = keep_accepted
+        return loop

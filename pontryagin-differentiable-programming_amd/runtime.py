@@ -49,6 +49,15 @@ class PdpOcSensOut(C.Structure):
     _fields_ = [("dxdp", C.c_void_p), ("dudp", C.c_void_p), ("riccati", C.c_void_p), ("predict_record", C.c_void_p)]
 
 
+class PdpLmSchedule(C.Structure):                  # include/pdp_hip_lm.h
+    _fields_ = [("up", C.c_double), ("down", C.c_double), ("lam_min", C.c_double), ("lam_max", C.c_double), ("loss_tol", C.c_double), ("max_evals", C.c_int32)]
+
+
+class PdpLmState(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("theta", "trial", "lam", "current", "state", "evaluations", "rejected", "accepted", "accepted_now", "loss_trace",
+                                          "lambda_trace", "parameter_trace")] + [("trace_len", C.c_int64), ("counters", C.c_void_p)]
+
+
 class PdpPolicy(C.Structure):
     _fields_ = [("kind", C.c_int), ("n_pivots", C.c_int), ("pivots", C.c_double * 16), ("n_layers", C.c_int), ("sizes", C.c_int * 16), ("n_basis", C.c_int),
                 ("table", C.c_void_p)]
@@ -64,6 +73,7 @@ MODEL_SYMBOLS = ["pdp_model_get_info", "pdp_oc_rollout_batched", "pdp_oc_rollout
                  "pdp_cp_integrate_batched", "pdp_cp_auxsys_batched",
                  "pdp_cp_step_workspace_bytes", "pdp_cp_step_batched", "pdp_sysid_integrate_batched", "pdp_sysid_auxsys_batched", "pdp_sysid_step_batched",
                  "pdp_sysid_step_workspace_bytes", "pdp_sysid_step_ws_batched"]
+CORE_EXT_SYMBOLS = ["pdp_lm_update_batched"]             # declared in the extension header include/pdp_hip_lm.h, exported by libpdp_hip.so
 MODEL_EXT_SYMBOLS = ["pdp_sysid_step_gn_batched"]        # declared in the extension headers (include/pdp_hip_sysid_gn.h): include/pdp_hip.h is pinned at its entry points
 
 _core = None
@@ -102,6 +112,8 @@ def load_core():
         lib.pdp_gd_update_batched.restype = C.c_int
         lib.pdp_gd_update_batched.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 4 + \
                                              [C.c_int64, C.c_void_p, C.c_void_p]
+        lib.pdp_lm_update_batched.restype = C.c_int
+        lib.pdp_lm_update_batched.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PdpLmSchedule), C.POINTER(PdpLmState), C.c_void_p]
         _core = lib
     return _core
 
@@ -125,6 +137,36 @@ def gd_update(loss, grad, lr, theta, dtheta, counters, status=None, converged=No
         assert parameter_trace.is_contiguous() and parameter_trace.shape[1] == p
     check(load_core().pdp_gd_update_batched(B, p, ptr(loss), ptr(grad), int(grad.stride(0)), ptr(status), ptr(converged), ptr(iterations), float(lr), ptr(theta), ptr(dtheta),
                                             ptr(loss_trace), ptr(parameter_trace), int(tl), ptr(counters), current_stream_ptr()), "pdp_gd_update_batched")
+
+
+LM_STATES = ["START", "ACTIVE", "CONVERGED", "STALLED", "BUDGET", "FAILED"]          # PDP_LM_* of include/pdp_hip_lm.h
+
+
+def lm_update(rows, theta, trial, lam, current, state, evaluations, rejected, accepted, counters, up=10.0, down=10.0, lam_min=1e-12, lam_max=1e8, loss_tol=0.0,
+              max_evals=50, bad=None, accepted_now=None, loss_trace=None, lambda_trace=None, parameter_trace=None):
+    """One Levenberg-Marquardt update of K independent problems, one launch (pdp_lm_update_batched, include/pdp_hip_lm.h: the semantics).  rows [K S, p + 1 + p p] =
+    grad | loss | G per sample, evaluated at `trial` (rows may be strided: a view of a wider buffer); the state at fixed device addresses, initialised by the caller:
+    theta [K, p], trial [K S, p], lam [K], current [K, p + 1 + p p] fp64; state, evaluations, rejected, accepted int32 [K]; counters int64 [2] = launches done |
+    problems still START or ACTIVE (initialised 0 | K).  Optional: bad int32 [K S], accepted_now int32 [K S], loss_trace / lambda_trace [K, L], parameter_trace [K, L, p]."""
+    torch = torch_cuda()
+    K, p = theta.shape
+    assert trial.dim() == 2 and trial.shape[1] == p and trial.shape[0] % K == 0
+    S, w = trial.shape[0] // K, p + 1 + p * p
+    assert rows.dtype == torch.float64 and rows.dim() == 2 and tuple(rows.shape) == (K * S, w) and rows.stride(1) == 1 and rows.stride(0) >= w
+    for t, shape in ((theta, (K, p)), (trial, (K * S, p)), (lam, (K,)), (current, (K, w))):
+        assert t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
+    for t in (state, evaluations, rejected, accepted):
+        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (K,)
+    for t in (bad, accepted_now):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (K * S,))
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 2
+    L = next((int(t.shape[1]) for t in (loss_trace, lambda_trace, parameter_trace) if t is not None), 0)
+    for t, shape in ((loss_trace, (K, L)), (lambda_trace, (K, L)), (parameter_trace, (K, L, p))):
+        assert t is None or (t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape)
+    sch = PdpLmSchedule(float(up), float(down), float(lam_min), float(lam_max), float(loss_tol), int(max_evals))
+    st = PdpLmState(*[t.data_ptr() if t is not None else None for t in (theta, trial, lam, current, state, evaluations, rejected, accepted, accepted_now, loss_trace,
+                                                                         lambda_trace, parameter_trace)], L, counters.data_ptr())
+    check(load_core().pdp_lm_update_batched(K, S, p, ptr(rows), int(rows.stride(0)), ptr(bad), C.byref(sch), C.byref(st), current_stream_ptr()), "pdp_lm_update_batched")
 
 
 def torch_cuda():
