@@ -17,6 +17,13 @@ t = K, 2K, ... only, --observe i,j,... only those state components; every other 
 problem); prints evaluations, state and final loss per problem.
 
     python examples/sysid_pdp.py --system pendulum --method lm --per-trajectory
+
+--method lm --estimate-ini i,j,...: these components of every recording's initial state are NOT known (an encoder without velocities does not give the initial velocity
+either) and are estimated together with the parameters, from 0: the sensitivity with respect to them is a further column of the tile the fused kernel holds anyway.
+Shared parameters with one initial state per recording (LMLoop.for_sysid(estimate_ini=)), or with --per-trajectory one parameter estimate and one initial state per
+trajectory (BatchedLMLoop.for_sysid(estimate_ini=)).
+
+    python examples/sysid_pdp.py --system cartpole --method lm --observe 0,1 --estimate-ini 2,3
 """
 import argparse
 import os
@@ -57,8 +64,11 @@ def main():
     ap.add_argument("--every", type=int, default=1, help="--method lm: only the samples at t = K, 2K, ... are observed")
     ap.add_argument("--observe", default=None, help="--method lm: only these state components are observed (comma-separated indices)")
     ap.add_argument("--per-trajectory", action="store_true", help="--method lm: one problem per trajectory, all in lock-step on the device (irl.BatchedLMLoop)")
+    ap.add_argument("--estimate-ini", default=None, help="--method lm: these components of the initial states are unknown and estimated with the parameters (comma-separated)")
     a = ap.parse_args()
     partial = a.every > 1 or a.observe is not None
+    if a.estimate_ini is not None and a.method != "lm":
+        ap.error("--estimate-ini needs --method lm")
     if partial and a.method != "lm":
         ap.error("--every / --observe need --method lm")
     if a.per_trajectory and a.method != "lm":
@@ -84,6 +94,33 @@ def main():
             masked = np.full_like(states, np.nan)
             for t in range(a.every, states.shape[1], a.every):
                 masked[:, t, comps] = states[:, t, comps]
+        if a.estimate_ini is not None:
+            idx = [int(c) for c in a.estimate_ini.split(",")]
+            ini = states[:, 0].copy()
+            ini[:, idx] = 0.0                       # not known: the estimate starts from 0
+            data = masked if partial else states.copy()
+            if not partial:
+                data[:, 0, idx] = np.nan            # (what is estimated was not recorded)
+            make = BatchedLMLoop.for_sysid if a.per_trajectory else LMLoop.for_sysid
+            loop = make(sid.model(), inputs, data, theta, ini_state=ini, skip_missing=True, estimate_ini=idx, **(dict(max_evals=min(a.iters, 100), loss_tol=1e-20)
+                                                                                                              if a.per_trajectory else {}))
+            r = loop.run() if a.per_trajectory else loop.run(max_evals=min(a.iters, 100), loss_tol=1e-20)
+            if a.per_trajectory:
+                th, x0 = loop.split(r["theta"])
+                for k in range(inputs.shape[0]):
+                    print("trajectory %3d  %2d evaluations  %2d rejected  %-9s  loss %.6e -> %.6e  |theta - theta*| = %.2e  |ini_state - x0*| = %.2e  theta %s"
+                          % (k, r["evaluations"][k], r["rejected"][k], r["state"][k], r["loss_trace"][k][0], r["loss"][k], np.abs(th[k] - true_parameter).max(),
+                             np.abs(x0[k] - states[k, 0]).max(), np.array2string(th[k], precision=4)))
+                print("done: %d problems in %d launches, %.2f s; largest final loss %.4e" % (inputs.shape[0], r["launches"], time.time() - t0, np.max(r["loss"])))
+                return r
+            for k in range(len(r["loss_trace"])):
+                print("accepted %3d  loss %.6e  lambda %.1e  theta %s" % (k, r["loss_trace"][k], r["lambda_trace"][k],
+                                                                          np.array2string(loop.split(r["parameter_trace"][k])[0], precision=4)))
+            print("%d evaluations, %d rejected%s" % (r["evaluations"], r["rejected"], ", stalled" if r["stalled"] else ""))
+            th, x0 = loop.split(r["parameter_trace"][-1])
+            print("done: %d accepted points in %.2f s; loss %.4e -> %.4e; |theta - theta*| = %.2e; |ini_state - x0*| = %.2e"
+                  % (len(r["loss_trace"]), time.time() - t0, r["loss_trace"][0], r["loss_trace"][-1], np.abs(th - true_parameter).max(), np.abs(x0 - states[:, 0]).max()))
+            return r
         if a.per_trajectory:
             kw = dict(ini_state=states[:, 0], skip_missing=True) if partial else {}
             r = BatchedLMLoop.for_sysid(sid.model(), inputs, masked if partial else states, theta, max_evals=min(a.iters, 100), loss_tol=1e-20, **kw).run()

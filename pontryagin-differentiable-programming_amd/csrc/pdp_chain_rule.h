@@ -30,6 +30,12 @@
 //   PDP_SYSID_GN_MISS   PDP_SYSID_GN with the semantics of PDP_GRAD_SKIP_MISSING.  An OBSERVED entry whose own state is not finite leaves a NaN in the loss: a
 //                    diverged rollout stays visible (there is no status word here).
 //                    Both SysID Gauss-Newton modes exist for one parameter tile only (NT == 1, p <= 16: what irl.lm_step solves on the host).
+//   PDP_SYSID_GN_INI, PDP_SYSID_GN_INI_MISS   PDP_SYSID_GN / PDP_SYSID_GN_MISS with q = popcount(ini_mask) components of x0 as further unknowns (the second
+//                    trailing argument: a bit mask over the n state components; its k-th set bit i_k, ascending, is unknown p + k).  dx_t/dx0[i_k] is one more
+//                    COLUMN of the same sensitivity tile: it starts as the unit vector e_{i_k} instead of 0 (sysid_ini_tile, per lane, no LDS) and sees a zero column of
+//                    E, which the E gather returns for every column >= p anyway - the recursion, the contraction and the Gram product are the ones of the other modes,
+//                    no MFMA and no LDS word more per step.  W = p + q <= 16 (the host checks); the row is grad [W] | loss | G [W][W].  Row 0 is no longer silent: an
+//                    observed x_obs[0][i_k] adds d_0[i_k] to grad[p + k] and 1 to G[p + k][p + k].
 #pragma once
 #include "pdp_tile.h"
 
@@ -43,6 +49,8 @@
 #define PDP_SYSID_PLAIN 0
 #define PDP_SYSID_GN 1
 #define PDP_SYSID_GN_MISS 2
+#define PDP_SYSID_GN_INI 3
+#define PDP_SYSID_GN_INI_MISS 4
 
 namespace pdp {
 
@@ -58,10 +66,11 @@ struct FusedMode {
     static constexpr bool MISS = MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS;
     static constexpr Residual RES = MISS ? RES_MISS : RES_PLAIN;          // (COT forms no residual: the cotangent takes the slot as it is)
 };
-template <int MODE, int NT, int NINI>                      // NT parameter tiles, NINI trailing kernel arguments (the x0 of the Gauss-Newton modes)
+template <int MODE, int NT, int NINI>                      // NT parameter tiles, NINI trailing kernel arguments (the x0 of the Gauss-Newton modes; INI: x0 and the mask)
 struct SysidMode {
-    static_assert(MODE == PDP_SYSID_PLAIN || (NT == 1 && NINI == 1 && (MODE == PDP_SYSID_GN || MODE == PDP_SYSID_GN_MISS)), "instantiation");
-    static constexpr bool GN = MODE != PDP_SYSID_PLAIN, MISS = MODE == PDP_SYSID_GN_MISS;
+    static constexpr bool INI = MODE == PDP_SYSID_GN_INI || MODE == PDP_SYSID_GN_INI_MISS;
+    static_assert(MODE == PDP_SYSID_PLAIN || (NT == 1 && NINI == 1 && (MODE == PDP_SYSID_GN || MODE == PDP_SYSID_GN_MISS)) || (NT == 1 && NINI == 2 && INI), "instantiation");
+    static constexpr bool GN = MODE != PDP_SYSID_PLAIN, MISS = MODE == PDP_SYSID_GN_MISS || MODE == PDP_SYSID_GN_INI_MISS;
     static constexpr Residual RES = MISS ? RES_MISS_DIFF : RES_PLAIN;
 };
 
@@ -120,5 +129,37 @@ PDP_DEV d4 gram_step(const d4 X, const d4 U, d4 Gn) { return mma_tn_r0(U, U, gra
 // this lane's share of the gradient: DX . X (+ DU . U, the same left-to-right sum)
 PDP_DEV double contract_step(const d4 DX, const d4 X) { return DX[0] * X[0] + DX[1] * X[1] + DX[2] * X[2] + DX[3] * X[3]; }
 PDP_DEV double contract_step(const d4 DX, const d4 DU, const d4 X, const d4 U) { return contract_step(DX, X) + DU[0] * U[0]; }
+
+
+// ---- PDP_SYSID_GN_INI*: the initial sensitivity tile X_0 [n][W] = zeros with X_0[i_k][p + k] = 1, and the width W = p + q of the row.  Per lane: its column minus p
+// selects the k-th set bit of the mask (a scan over the NX bits, unrolled), its four rows are compared with it.  No memory is touched.
+template <int NX, int NP>
+PDP_DEV d4 sysid_ini_tile(int lane, unsigned mask) {
+    const int k = tile_col(lane) - NP;
+    int ik = -1, seen = 0;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+        const bool set = (mask >> i) & 1u;
+        ik = (set && seen == k) ? i : ik;
+        seen += set ? 1 : 0;
+    }
+    d4 X;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) X[r] = tile_row(lane, r) == ik ? 1.0 : 0.0;
+    return X;
+}
+template <int NP>
+PDP_DEV int sysid_ini_width(unsigned mask) { return NP + __builtin_popcount(mask); }
+// G [W][W] row-major from the accumulator tile: store_dense with a RUN-TIME width, in a helper of its own.  store_dense itself must keep being called with
+// compile-time R, C, ld only: the constants are propagated into it before it is inlined, and one caller with a run-time width changed the instructions of the frozen
+// Gauss-Newton instantiations that call it with NP (profiles/sysid_ini_code_object_diff.txt).  Used by the PDP_SYSID_GN_INI* arms alone.
+PDP_DEV void sysid_ini_store(double* __restrict__ G, int W, int lane, const d4 Gn) {
+    const int col = tile_col(lane);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = tile_row(lane, r);
+        if (row < W && col < W) G[row * W + col] = Gn[r];
+    }
+}
 
 }  // namespace pdp

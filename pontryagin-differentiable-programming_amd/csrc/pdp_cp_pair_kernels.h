@@ -269,6 +269,7 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
         [[maybe_unused]] d4 Gn = z;                        // GN: sum_t X_t' X_t
 #pragma unroll
         for (int j = 0; j < NT; ++j) { X[j] = z; acc[j] = 0.0; }
+        if constexpr (SM::INI) X[0] = sysid_ini_tile<NX, NP>(lane, sysid_ini_mask(ini...));      // X_0: the unit columns of the estimated components of x0
         const int nchunk = (T + CH - 1) / CH;
         const int ch = (T + nchunk - 1) / nchunk;
         for (int c = 0; c < nchunk; ++c) {
@@ -326,7 +327,15 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
                 }
             }
             double a = sum_over_rowgroups(acc[j]);
-            if constexpr (SM::GN) {
+            if constexpr (SM::INI) {                       // the row of W = p + q unknowns: grad [W] | loss | G [W][W]
+                Gn = gram_add<false>(X[j], Gn);            // X_T
+                if (mine) {
+                    const int W = sysid_ini_width<NP>(sysid_ini_mask(ini...));
+                    double* row = grad + (int64_t)b * (W + 1 + W * W);
+                    if (lane < W) row[lane] = a;
+                    sysid_ini_store(row + W + 1, W, lane, Gn);
+                }
+            } else if constexpr (SM::GN) {
                 Gn = gram_add<false>(X[j], Gn);            // X_T
                 if (mine) {
                     if (lane < NP) grad[(int64_t)b * (NP + 1 + NP * NP) + lane] = a;
@@ -338,6 +347,8 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
         }
         lsum = wave_sum(lsum);
         if (mine && lane == 0) loss[b] = lsum;
+        if constexpr (SM::INI) { const int W = sysid_ini_width<NP>(sysid_ini_mask(ini...)); if (mine && lane == 0) grad[(int64_t)b * (W + 1 + W * W) + W] = lsum; }
+        else
         if constexpr (SM::GN) { if (mine && lane == 0) grad[(int64_t)b * (NP + 1 + NP * NP) + NP] = lsum; }
     }
 }

@@ -4,6 +4,7 @@
 #include <cstdio>
 #include "../../include/pdp_hip.h"
 #include "../../include/pdp_hip_sysid_gn.h"
+#include "../../include/pdp_hip_sysid_ini.h"
 #ifndef PDP_MODEL_HEADER
 #error "compile with -DPDP_MODEL_HEADER=\"generated/<model>.h\""
 #endif
@@ -556,12 +557,15 @@ int64_t sysid_step_ws_bytes(int B, int T) {
 }
 // MODE (PDP_SYSID_PLAIN / PDP_SYSID_GN / PDP_SYSID_GN_MISS): the instantiation of the fused kernels.  The Gauss-Newton modes write the packed row grad | loss | G through
 // `grad`, start the rollouts from x0 [B][n] (NULL: x_obs[:, 0]) - in the kernels through their trailing argument, in the pre-pass through its pointer and stride - and
-// exist for p <= 16.  Same dispatch, thresholds and switches in every mode.
+// exist for p <= 16.  PDP_SYSID_GN_INI / PDP_SYSID_GN_INI_MISS: the Gauss-Newton modes with the components of x0 that `ini_mask` names as further unknowns (the
+// kernels' second trailing argument; the row is grad | loss | G over W = p + popcount(ini_mask) <= 16 unknowns).  Same dispatch, thresholds and switches in every mode.
 template <class Mdl, int MODE = PDP_SYSID_PLAIN>
 int sysid_step(int B, int T, const double* u, const double* xobs, const double* th, int tb, double* loss, double* grad, void* ws, int64_t wsb, void* st,
-               const double* x0 = nullptr) {
-    if constexpr (Mdl::KIND == PDP_KIND_SYSID && Mdl::NX <= 16 && Mdl::NP <= (MODE == PDP_SYSID_PLAIN ? 64 : 16)) {
+               const double* x0 = nullptr, [[maybe_unused]] unsigned ini_mask = 0) {
+    constexpr bool INI = MODE == PDP_SYSID_GN_INI || MODE == PDP_SYSID_GN_INI_MISS;
+    if constexpr (Mdl::KIND == PDP_KIND_SYSID && Mdl::NX <= 16 && Mdl::NP <= (MODE == PDP_SYSID_PLAIN ? 64 : (INI ? 15 : 16))) {
         if (B <= 0 || T <= 0 || !u || !xobs || !th || !loss || !grad) return PDP_E_ARG;
+        if constexpr (INI) { if (Mdl::NP + __builtin_popcount(ini_mask) > 16) return PDP_E_SIZE; }
         const double* xgiven = nullptr;
         if (ws && sysid_prepass(B)) {           // (no workspace: the kernel rolls out itself, whatever the batch)
             if (wsb < sysid_step_ws_bytes<Mdl>(B, T)) return PDP_E_ARG;
@@ -588,6 +592,9 @@ int sysid_step(int B, int T, const double* u, const double* xobs, const double* 
                     if constexpr (MODE == PDP_SYSID_PLAIN)
                     return launch(sysid_step2_kernel<Mdl, NT, K()>, dim3((B + K() - 1) / K()), dim3(128 * K()), slice * K() * sizeof(double), S(st), B, T, u, xobs, th, tb, loss,
                                   grad, slice);
+                    else if constexpr (INI)
+                        return launch(sysid_step2_kernel<Mdl, NT, K(), MODE, const double*, unsigned>, dim3((B + K() - 1) / K()), dim3(128 * K()),
+                                      slice * K() * sizeof(double), S(st), B, T, u, xobs, th, tb, loss, grad, slice, x0, ini_mask);
                     else
                         return launch(sysid_step2_kernel<Mdl, NT, K(), MODE, const double*>, dim3((B + K() - 1) / K()), dim3(128 * K()), slice * K() * sizeof(double), S(st),
                                       B, T, u, xobs, th, tb, loss, grad, slice, x0);
@@ -596,6 +603,9 @@ int sysid_step(int B, int T, const double* u, const double* xobs, const double* 
         return with_bool(xgiven != nullptr, [&](auto GIVEN) {
             if constexpr (MODE == PDP_SYSID_PLAIN)
             return launch(sysid_step_kernel<Mdl, NT, GIVEN()>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad, rows, xgiven);
+            else if constexpr (INI)
+                return launch(sysid_step_kernel<Mdl, NT, GIVEN(), MODE, const double*, unsigned>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad, rows,
+                              xgiven, x0, ini_mask);
             else
                 return launch(sysid_step_kernel<Mdl, NT, GIVEN(), MODE, const double*>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad, rows, xgiven, x0);
         });
@@ -708,6 +718,16 @@ int pdp_sysid_step_gn_batched(int B, int T, const double* u, const double* x_obs
     if (B <= 0 || T <= 0 || !u || !x_obs || !theta || !loss || !packed || (flags & ~PDP_GRAD_SKIP_MISSING)) return PDP_E_ARG;
     return (flags & PDP_GRAD_SKIP_MISSING) ? sysid_step<PdpModel, PDP_SYSID_GN_MISS>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0)
                                            : sysid_step<PdpModel, PDP_SYSID_GN>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0);
+}
+int pdp_sysid_step_gn_ini_batched(int B, int T, const double* u, const double* x_obs, const double* x0, int ini_mask, const double* theta, int tb, int flags, double* loss,
+                                  double* packed, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (ini_mask == 0) return pdp_sysid_step_gn_batched(B, T, u, x_obs, x0, theta, tb, flags, loss, packed, workspace, workspace_bytes, stream);
+    if (B <= 0 || T <= 0 || !u || !x_obs || !theta || !loss || !packed || (flags & ~PDP_GRAD_SKIP_MISSING)) return PDP_E_ARG;
+    if (PdpModel::NX < 32 && ((unsigned)ini_mask >> PdpModel::NX) != 0) return PDP_E_ARG;       // a mask bit >= n
+    const unsigned mask = (unsigned)ini_mask;
+    return (flags & PDP_GRAD_SKIP_MISSING)
+               ? sysid_step<PdpModel, PDP_SYSID_GN_INI_MISS>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0, mask)
+               : sysid_step<PdpModel, PDP_SYSID_GN_INI>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0, mask);
 }
 
 }  // extern "C"

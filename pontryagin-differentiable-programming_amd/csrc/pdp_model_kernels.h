@@ -1740,9 +1740,11 @@ __host__ inline int sysid_rows(int B, int T, int cus) {
 }
 PDP_DEV const double* sysid_ini() { return nullptr; }                     // the trailing x0 argument of the Gauss-Newton modes (PDP_SYSID_PLAIN has none)
 PDP_DEV const double* sysid_ini(const double* x0) { return x0; }
+PDP_DEV const double* sysid_ini(const double* x0, unsigned) { return x0; }      // PDP_SYSID_GN_INI*: x0 and the mask of its estimated components
+PDP_DEV unsigned sysid_ini_mask(const double*, unsigned mask) { return mask; }
 
 // Fused SysID.step per trajectory: rollout (uniform, x kept in LDS) then X_{t+1} = F X_t + E on MFMA tiles.  MODE: one of PDP_SYSID_* (pdp_chain_rule.h;
-// pdp_sysid_step_gn_batched selects PDP_SYSID_GN / PDP_SYSID_GN_MISS).
+// pdp_sysid_step_gn_batched selects PDP_SYSID_GN / PDP_SYSID_GN_MISS, pdp_sysid_step_gn_ini_batched PDP_SYSID_GN_INI / PDP_SYSID_GN_INI_MISS).
 template <class Mdl, int NT, bool GIVEN = false, int MODE = PDP_SYSID_PLAIN, class... Ini>
 __global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const double* __restrict__ u, const double* __restrict__ xobs,
                                                          const double* __restrict__ theta, int tb, double* __restrict__ loss, double* __restrict__ grad, int CH,
@@ -1816,6 +1818,7 @@ __global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const doub
     [[maybe_unused]] d4 Gn = z;                            // GN: sum_t X_t' X_t
 #pragma unroll
     for (int j = 0; j < NT; ++j) { X[j] = z; acc[j] = 0.0; }
+    if constexpr (SM::INI) X[0] = sysid_ini_tile<NX, NP>(lane, sysid_ini_mask(ini...));      // X_0: the unit columns of the estimated components of x0
     const int nchunk = (T + CH - 1) / CH;
     const int ch = (T + nchunk - 1) / nchunk;      // chunks of equal length
     for (int c = 0; c < nchunk; ++c) {
@@ -1864,7 +1867,13 @@ __global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const doub
 #pragma unroll
         for (int r = 0; r < 4; ++r) { const int row = tile_row(lane, r); if (row < NX) { const double d = dlT[row]; X[j][r] = observed<SM::MISS>(d, X[j][r]); acc[j] += observed<SM::MISS>(d, d) * X[j][r]; } }      // (MISS: X_T masked in place)
         double a = sum_over_rowgroups(acc[j]);
-        if constexpr (SM::GN) {
+        if constexpr (SM::INI) {                           // the row of W = p + q unknowns: grad [W] | loss | G [W][W]
+            const int W = sysid_ini_width<NP>(sysid_ini_mask(ini...));
+            double* row = grad + (int64_t)b * (W + 1 + W * W);
+            if (lane < W) row[lane] = a;
+            Gn = gram_add<false>(X[j], Gn);                // X_T
+            sysid_ini_store(row + W + 1, W, lane, Gn);
+        } else if constexpr (SM::GN) {
             if (lane < NP) grad[(int64_t)b * (NP + 1 + NP * NP) + lane] = a;
             Gn = gram_add<false>(X[j], Gn);                // X_T
             store_dense(grad + (int64_t)b * (NP + 1 + NP * NP) + NP + 1, NP, NP, NP, 0, 0, lane, Gn);
@@ -1874,6 +1883,8 @@ __global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const doub
     }
     lsum = wave_sum(lsum);
     if (lane == 0) loss[b] = lsum;
+    if constexpr (SM::INI) { const int W = sysid_ini_width<NP>(sysid_ini_mask(ini...)); if (lane == 0) grad[(int64_t)b * (W + 1 + W * W) + W] = lsum; }
+    else
     if constexpr (SM::GN) { if (lane == 0) grad[(int64_t)b * (NP + 1 + NP * NP) + NP] = lsum; }
 }
 

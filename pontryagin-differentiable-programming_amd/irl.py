@@ -175,6 +175,37 @@ def lm_step(g, G, lam):
         return np.linalg.lstsq(A, g, rcond=None)[0]
 
 
+def arrow_normal_equations(rows, p, q):
+    """The normal equations of ONE shared theta [p] and one unknown initial-state part [q] per recording, from the B augmented rows grad [W] | loss | G [W][W]
+    (W = p + q) of sysid_step(estimate_ini=): the unknown vector is [theta | x0_0[idx] | ... | x0_{B-1}[idx]], N = p + B q, and with the mean over the recordings as
+    the loss the matrix is arrow-shaped - the theta block and the theta-x0_b blocks are sums over the rows / B, the block of x0_b is row b's own block / B, and two
+    different recordings share no entry.  Equal to J'J / B of the stacked dense Jacobian.  rows [B, W + 1 + W W]: a torch tensor on any device (CPU included);
+    returns ONE flat tensor grad [N] | loss | G [N][N] on the same device (what goes to the host in one copy)."""
+    import torch
+    B, W = int(rows.shape[0]), p + q
+    N = p + B * q
+    g, loss, G = rows[:, :W], rows[:, W], rows[:, W + 1:].reshape(B, W, W)
+    out = rows.new_zeros(N + 1 + N * N)
+    out[:p] = g[:, :p].sum(dim=0) / B
+    out[p:N] = (g[:, p:] / B).reshape(-1)
+    out[N] = loss.sum() / B
+    A = out[N + 1:].view(N, N)
+    A[:p, :p] = G[:, :p, :p].sum(dim=0) / B
+    A[:p, p:] = (G[:, :p, p:] / B).permute(1, 0, 2).reshape(p, B * q)
+    A[p:, :p] = (G[:, p:, :p] / B).reshape(B * q, p)
+    b = torch.arange(B, device=rows.device)
+    A[p:, p:].unflatten(0, (B, q)).unflatten(2, (B, q))[b, :, b, :] = G[:, p:, p:] / B
+    return out
+
+
+def _refuse_nan_start(who, data, ini_state, name):
+    """skip_missing: a NaN in the initial state that would be used - ini_state, else data[:, 0] - is a ValueError before any launch.  Judged on what the caller gave (a
+    host array is not moved to the device first)."""
+    first = ini_state if ini_state is not None else (data if hasattr(data, "data_ptr") else np.asarray(data, dtype=float))[:, 0]
+    if bool(first.isnan().any()) if hasattr(first, "data_ptr") else bool(np.isnan(np.asarray(first, dtype=float)).any()):
+        raise ValueError("%s: skip_missing=True and the initial state (%s) holds a NaN: give ini_state [B, n]" % (who, "%s[:, 0]" % name if ini_state is None else "ini_state"))
+
+
 class LMLoop:
     """Levenberg-Marquardt on a sum-of-squares loss.  evaluate(theta [p], numpy) -> (loss, g [p], G [p, p]) as host floats / numpy arrays with g = J'r, G = J'J in the same
     scaling (half the gradient of loss = |r|^2, as the fused unit returns them), or None where theta cannot be evaluated (a solve that did not converge, a singular stage).
@@ -264,10 +295,7 @@ class LMLoop:
         demo_x[:, 0] as the initial state of the solves - needed where the first row of a demonstration is not (fully) observed: with skip_missing a NaN in the initial
         state the solves would start from is a ValueError here, before any launch."""
         if skip_missing:                            # judged on what the caller gave (a host array is not moved to the device first)
-            first = ini_state if ini_state is not None else (demo_x if hasattr(demo_x, "data_ptr") else np.asarray(demo_x, dtype=float))[:, 0]
-            if bool(first.isnan().any()) if hasattr(first, "data_ptr") else bool(np.isnan(np.asarray(first, dtype=float)).any()):
-                raise ValueError("LMLoop.for_irl: skip_missing=True and the initial state (%s) holds a NaN: give ini_state [B, n]"
-                                 % ("demo_x[:, 0]" if ini_state is None else "ini_state"))
+            _refuse_nan_start("LMLoop.for_irl", demo_x, ini_state, "demo_x")
         from . import parallel
         demo_x, demo_u = rt.dev(demo_x), rt.dev(demo_u)
         B, T, p = int(demo_u.shape[0]), int(demo_u.shape[1]), mdl.p
@@ -293,14 +321,23 @@ class LMLoop:
         return loop
 
     @classmethod
-    def for_sysid(cls, mdl, inputs, states, theta0, n_total=None, ini_state=None, skip_missing=False, **kw):
+    def for_sysid(cls, mdl, inputs, states, theta0, n_total=None, ini_state=None, skip_missing=False, estimate_ini=None, **kw):
         """The SysID drivers' problem (Examples/SysID/*/..._PDP.py) as nonlinear least squares: mdl a runtime.ModelLib of a SysID model, inputs [B, T, m] and states
         [B, T+1, n] the recorded data (this rank's shard under torch.distributed; n_total as in parallel.allreduce_mean_packed), theta0 [p] shared by all trajectories.
         evaluate(theta) is ONE launch - sysid_step with gauss_newton=True: loss, gradient and G = J'J from the sensitivity tiles of the fused kernel - and hands the packed
         rows, with the count of rows that hold a non-finite entry (a diverged rollout: SysID has no status word), to parallel.mean_row_checked: one all-reduce when a
         process group exchanges, one copy of p + 3 + p p doubles to the host; a trial with such a row on ANY rank is None on EVERY rank.
         skip_missing: partial data - a NaN in `states` is an entry that was not observed (encoders without velocities, a sample every k steps); ini_state [B, n] replaces
-        states[:, 0] as the initial state of the rollouts, needed where the first row is not fully observed (a NaN there is a ValueError before any launch)."""
+        states[:, 0] as the initial state of the rollouts, needed where the first row is not fully observed (a NaN there is a ValueError before any launch).
+        estimate_ini (state indices or a bool mask [n], runtime.ini_indices): these q components of every recording's initial state are unknowns too - one shared theta
+        and one unknown initial-state part per recording.  The unknown vector is [theta | x0_0[idx] | ... | x0_{B-1}[idx]], N = p + B q; theta0 is [p] (the estimated
+        components start from ini_state, or states[:, 0]) or [N].  An evaluation is one launch of sysid_step(estimate_ini=) at (theta, x0); the arrow-shaped normal
+        equations are assembled from the B augmented rows on the device (arrow_normal_equations) and go to the host in one copy; a non-finite row makes the point None;
+        the solve is lm_step's, dense on the host.  loop.split(vector) -> (theta [p], ini_state [B, n]).  N > 256, n_total, or a process group of more than one rank is a
+        ValueError: many recordings, or recordings spread over ranks, are BatchedLMLoop.for_sysid(estimate_ini=)'s problems, one theta per trajectory."""
+        idx = rt.ini_indices(estimate_ini, mdl.n)[0]
+        if idx:                                     # (nothing selected is estimate_ini=None)
+            return cls._for_sysid_ini(mdl, inputs, states, theta0, n_total, ini_state, skip_missing, idx, **kw)
         from . import parallel
         torch = rt.torch_cuda()
         inputs, states = rt.dev(inputs), rt.dev(states)
@@ -318,6 +355,51 @@ class LMLoop:
             return float(row[p]), row[:p].copy(), row[p + 1:].reshape(p, p).copy()
 
         return cls(evaluate, theta0, **kw)
+
+    @classmethod
+    def _for_sysid_ini(cls, mdl, inputs, states, theta0, n_total, ini_state, skip_missing, idx, **kw):
+        if skip_missing:                            # an estimated component still needs a finite starting value
+            _refuse_nan_start("LMLoop.for_sysid", states, ini_state, "states")
+        torch = rt.torch_cuda()
+        inputs, states = rt.dev(inputs), rt.dev(states)
+        B, T, p, q = int(inputs.shape[0]), int(inputs.shape[1]), mdl.p, len(idx)
+        assert states.shape == (B, T + 1, mdl.n) and inputs.shape == (B, T, mdl.m)
+        x0 = (rt.dev(ini_state).reshape(B, mdl.n) if ini_state is not None else states[:, 0]).contiguous().clone()      # persistent: the estimated components are written into it
+        N = p + B * q
+        dist = torch.distributed
+        if n_total is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            raise ValueError("LMLoop.for_sysid(estimate_ini=): one shared theta with per-recording initial states lives on one rank (no n_total, no process group of "
+                             "more than one rank); independent problems shard over ranks with BatchedLMLoop.for_sysid(estimate_ini=)")
+        if N > 256:
+            raise ValueError("LMLoop.for_sysid(estimate_ini=): N = p + B q = %d unknowns > 256 (a dense solve on the host); one problem per trajectory is "
+                             "BatchedLMLoop.for_sysid(estimate_ini=)" % N)
+        ini0 = x0.cpu().numpy().copy()
+        th0 = np.asarray(theta0.cpu() if hasattr(theta0, "cpu") else theta0, dtype=float).reshape(-1)
+        if th0.size == p:
+            th0 = np.concatenate([th0, ini0[:, idx].reshape(-1)])
+        if th0.size != N:
+            raise ValueError("LMLoop.for_sysid(estimate_ini=): theta0 is [p] = [%d] or [p + B q] = [%d], got %d" % (p, N, th0.size))
+        cols = torch.tensor(idx, dtype=torch.int64, device="cuda")
+        bufs = {}
+
+        def evaluate(vector):
+            v = rt.dev(np.ascontiguousarray(vector, dtype=float))                         # one copy to the device: theta and the estimated components
+            x0.index_copy_(1, cols, v[p:].view(B, q))
+            out = mdl.sysid_step(inputs, states, v[:p], gauss_newton=True, skip_missing=skip_missing, ini_state=x0, buffers=bufs, estimate_ini=idx)
+            flat = arrow_normal_equations(out["packed_gn"], p, q).cpu().numpy()            # one copy to the host
+            if not np.isfinite(flat).all():         # every entry of every row is in there, summed or as it is: a non-finite row shows
+                return None
+            return float(flat[N]), flat[:N].copy(), flat[N + 1:].reshape(N, N).copy()
+
+        def split(vector):
+            v = np.asarray(vector, dtype=float).reshape(-1)
+            ini = ini0.copy()
+            ini[:, idx] = v[p:].reshape(B, q)
+            return v[:p].copy(), ini
+
+        loop = cls(evaluate, th0, **kw)
+        loop.split = split
+        return loop
 
 
 class BatchedLMLoop:
@@ -393,15 +475,20 @@ class BatchedLMLoop:
                 "accepted": acc, "state": [rt.LM_STATES[v] for v in state], "theta": self.theta.cpu().numpy(), "loss": loss, "launches": self.launches}
 
     @classmethod
-    def for_sysid(cls, mdl, inputs, states, theta0, samples_per_problem=1, ini_state=None, skip_missing=False, **kw):
+    def for_sysid(cls, mdl, inputs, states, theta0, samples_per_problem=1, ini_state=None, skip_missing=False, estimate_ini=None, **kw):
         """One SysID problem per group of samples_per_problem consecutive trajectories: inputs [K S, T, m], states [K S, T+1, n], theta0 [K, p] or [p].  An evaluation is
         ONE launch of mdl.sysid_step(gauss_newton=True) with the trial points as per-sample parameters; a sample is bad where its row holds a non-finite entry (formed on
-        the device).  skip_missing, ini_state: as in LMLoop.for_sysid (a NaN in the initial state under skip_missing is a ValueError before any launch)."""
+        the device).  skip_missing, ini_state: as in LMLoop.for_sysid (a NaN in the initial state under skip_missing is a ValueError before any launch).
+        estimate_ini (state indices or a bool mask [n]): one problem per TRAJECTORY (samples_per_problem == 1) whose vector is [theta_k | x0_k[idx]], W = p + q <= 16
+        unknowns; theta0 is [p], [K, p] (the estimated components start from ini_state, or states[:, 0]) or [K, W].  An evaluation is one launch of
+        pdp_sysid_step_gn_ini_batched: theta is read from the trial rows in place (row stride W), the estimated components are copied from the trial rows into a
+        persistent x0 buffer at a fixed address - one small device copy, no host synchronisation; the update launch is pdp_lm_update_batched's with W as its p.
+        loop.split(theta [K, W]) -> (theta [K, p], ini_state [K, n])."""
         if skip_missing:                            # judged on what the caller gave (a host array is not moved to the device first)
-            first = ini_state if ini_state is not None else (states if hasattr(states, "data_ptr") else np.asarray(states, dtype=float))[:, 0]
-            if bool(first.isnan().any()) if hasattr(first, "data_ptr") else bool(np.isnan(np.asarray(first, dtype=float)).any()):
-                raise ValueError("BatchedLMLoop.for_sysid: skip_missing=True and the initial state (%s) holds a NaN: give ini_state [B, n]"
-                                 % ("states[:, 0]" if ini_state is None else "ini_state"))
+            _refuse_nan_start("BatchedLMLoop.for_sysid", states, ini_state, "states")
+        idx, mask = rt.ini_indices(estimate_ini, mdl.n)
+        if idx:                                     # (nothing selected is estimate_ini=None; an estimated component still needs the finite starting value checked above)
+            return cls._for_sysid_ini(mdl, inputs, states, theta0, samples_per_problem, ini_state, skip_missing, idx, mask, **kw)
         torch = rt.torch_cuda()
         inputs, states = rt.dev(inputs), rt.dev(states)
         B, T, S = int(inputs.shape[0]), int(inputs.shape[1]), int(samples_per_problem)
@@ -416,6 +503,44 @@ class BatchedLMLoop:
         return cls(evaluate_rows, theta0, samples_per_problem=S, K=B // S, **kw)
 
     @classmethod
+    def _for_sysid_ini(cls, mdl, inputs, states, theta0, samples_per_problem, ini_state, skip_missing, idx, mask, **kw):
+        torch = rt.torch_cuda()
+        inputs, states = rt.dev(inputs), rt.dev(states)
+        K, T, p, q = int(inputs.shape[0]), int(inputs.shape[1]), mdl.p, len(idx)
+        W = p + q
+        assert states.shape == (K, T + 1, mdl.n) and inputs.shape == (K, T, mdl.m)
+        x0 = (rt.dev(ini_state).reshape(K, mdl.n) if ini_state is not None else states[:, 0]).contiguous().clone()      # persistent, at a fixed address
+        if int(samples_per_problem) != 1:
+            raise ValueError("BatchedLMLoop.for_sysid(estimate_ini=): one problem per trajectory (samples_per_problem == 1); one shared theta with an initial state "
+                             "per recording is LMLoop.for_sysid(estimate_ini=)")
+        if W > 16:
+            raise ValueError("BatchedLMLoop.for_sysid(estimate_ini=): p + q = %d + %d > 16 unknowns per problem" % (p, q))
+        ini0 = x0.cpu().numpy().copy()
+        cols = torch.tensor(idx, dtype=torch.int64, device="cuda")
+        th = rt.dev(theta0)
+        th = (th[None].expand(K, -1) if th.dim() == 1 else th).reshape(K, -1)
+        if th.shape[1] == p:
+            th = torch.cat([th, x0[:, cols]], dim=1)
+        if th.shape[1] != W:
+            raise ValueError("BatchedLMLoop.for_sysid(estimate_ini=): theta0 is [p], [K, p] or [K, p + q] = [%d, %d], got %s" % (K, W, tuple(th.shape)))
+        bufs = {}
+
+        def evaluate_rows(trial):                   # trial [K, W] at a fixed address: theta_k in its first p columns (read in place), x0_k[idx] behind them
+            x0.index_copy_(1, cols, trial[:, p:])
+            out = mdl._sysid_step_gn_ini(inputs, states, trial, W, True, skip_missing, x0, bufs, idx, mask)
+            return out["packed_gn"], (~torch.isfinite(out["packed_gn"])).any(dim=1).to(torch.int32)
+
+        def split(theta):
+            v = np.asarray(theta.cpu() if hasattr(theta, "cpu") else theta, dtype=float).reshape(K, W)
+            ini = ini0.copy()
+            ini[:, idx] = v[:, p:]
+            return v[:, :p].copy(), ini
+
+        loop = cls(evaluate_rows, th, samples_per_problem=1, K=K, **kw)
+        loop.split = split
+        return loop
+
+    @classmethod
     def for_irl(cls, mdl, demo_x, demo_u, theta0, samples_per_problem=1, tol=1e-10, max_iter=300, ini_state=None, skip_missing=False, **kw):
         """One IRL problem per group of samples_per_problem consecutive demonstrations: demo_x [K S, T+1, n], demo_u [K S, T, m], theta0 [K, p] or [p].  An evaluation
         solves every demonstration's OC problem at its problem's trial point (oc_solve_ms with per-sample parameters: the first cold, later ones warm from COPIES of the
@@ -423,10 +548,7 @@ class BatchedLMLoop:
         converge, reported trouble, or the unit set a status bit.  After the update the accepted solutions are refreshed where the launch accepted the sample's problem
         (torch.where on accepted_now: no host decision).  skip_missing, ini_state: as in LMLoop.for_irl."""
         if skip_missing:
-            first = ini_state if ini_state is not None else (demo_x if hasattr(demo_x, "data_ptr") else np.asarray(demo_x, dtype=float))[:, 0]
-            if bool(first.isnan().any()) if hasattr(first, "data_ptr") else bool(np.isnan(np.asarray(first, dtype=float)).any()):
-                raise ValueError("BatchedLMLoop.for_irl: skip_missing=True and the initial state (%s) holds a NaN: give ini_state [B, n]"
-                                 % ("demo_x[:, 0]" if ini_state is None else "ini_state"))
+            _refuse_nan_start("BatchedLMLoop.for_irl", demo_x, ini_state, "demo_x")
         torch = rt.torch_cuda()
         demo_x, demo_u = rt.dev(demo_x), rt.dev(demo_u)
         B, T, S = int(demo_u.shape[0]), int(demo_u.shape[1]), int(samples_per_problem)

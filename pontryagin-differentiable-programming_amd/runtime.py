@@ -76,6 +76,8 @@ MODEL_SYMBOLS = ["pdp_model_get_info", "pdp_oc_rollout_batched", "pdp_oc_rollout
 CORE_EXT_SYMBOLS = ["pdp_lm_update_batched"]             # declared in the extension header include/pdp_hip_lm.h, exported by libpdp_hip.so
 MODEL_EXT_SYMBOLS = ["pdp_sysid_step_gn_batched"]        # declared in the extension headers (include/pdp_hip_sysid_gn.h): include/pdp_hip.h is pinned at its entry points
 
+MODEL_INI_SYMBOLS = ["pdp_sysid_step_gn_ini_batched"]   # include/pdp_hip_sysid_ini.h: one list per extension header
+
 _core = None
 
 
@@ -291,6 +293,30 @@ def sysid_aux_integrate(F, E, X0=None):
     return X
 
 
+def ini_indices(estimate_ini, n):
+    """The estimated components of an initial state, normalised: estimate_ini is None, a bool mask [n] or ascending unique state indices; returns (indices as a list
+    of int, the bit mask of pdp_sysid_step_gn_ini_batched).  Duplicates, indices out of range or not ascending, and a mask of another length are a ValueError."""
+    if estimate_ini is None:
+        return [], 0
+    a = np.asarray(estimate_ini.cpu() if hasattr(estimate_ini, "cpu") else estimate_ini)
+    if a.dtype == bool:
+        if a.shape != (n,):
+            raise ValueError("estimate_ini: a bool mask has one entry per state component (%d), got shape %s" % (n, a.shape))
+        idx = [int(i) for i in np.flatnonzero(a)]
+    else:
+        a = a.reshape(-1)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("estimate_ini: state indices (integers) or a bool mask [n]")
+        idx = [int(i) for i in a]
+        if any(i < 0 or i >= n for i in idx):
+            raise ValueError("estimate_ini: state index out of range 0 .. %d: %s" % (n - 1, idx))
+        if len(set(idx)) != len(idx):
+            raise ValueError("estimate_ini: duplicate state index: %s" % idx)
+        if idx != sorted(idx):
+            raise ValueError("estimate_ini: state indices in ascending order (unknown p + k is the k-th of them): %s" % idx)
+    return idx, sum(1 << i for i in idx)
+
+
 # ------------------------------------------------------------------------------------------------------
 # per-model libraries (section B of include/pdp_hip.h)
 # ------------------------------------------------------------------------------------------------------
@@ -324,6 +350,8 @@ _MODEL_SIGS = {
     "pdp_sysid_step_ws_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I64, _VP]),
     # include/pdp_hip_sysid_gn.h
     "pdp_sysid_step_gn_batched": (_I, [_I, _I, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I64, _VP]),
+    # include/pdp_hip_sysid_ini.h
+    "pdp_sysid_step_gn_ini_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _I, _I, _VP, _VP, _VP, _I64, _VP]),
 }
 _models = {}
 
@@ -940,7 +968,7 @@ class ModelLib:
                 del cache[key]
         return ws, nbytes
 
-    def sysid_step(self, u, xobs, theta, gauss_newton=False, skip_missing=False, ini_state=None, buffers=None):
+    def sysid_step(self, u, xobs, theta, gauss_newton=False, skip_missing=False, ini_state=None, buffers=None, estimate_ini=None):
         """SysID.step per trajectory (pdp_sysid_step_ws_batched): (loss [B], grad [B, p]).  Models beyond the fused kernels' tiles (n > 16 or p > 64) take the reference's own
         route kernel by kernel - integrateDyn -> getAuxSys -> integrateAuxSys (size-generic kernels) -> the chain rule of PDP.py:1285-1291 as two tensor contractions: no size
         is refused.
@@ -949,7 +977,15 @@ class ModelLib:
         averages).  skip_missing: a NaN in xobs is an entry that was not observed (PDP_GRAD_SKIP_MISSING): loss, gradient and G over the observed entries; a NaN in the
         initial state the rollouts would start from is a ValueError before any launch.  ini_state [B, n]: the initial state of the rollouts instead of xobs[:, 0]; row 0 then
         adds |ini_state - xobs_0|^2 to the loss.  skip_missing or ini_state without gauss_newton return (loss, grad) from the same launch.  Beyond the fused kernels' tiles
-        (n > 16 or p > 16) the same row is contracted from the materialised sensitivities.  buffers: a dict the caller keeps - the output tensors are reused between calls."""
+        (n > 16 or p > 16) the same row is contracted from the materialised sensitivities.  buffers: a dict the caller keeps - the output tensors are reused between calls.
+        estimate_ini: ascending unique state indices or a bool mask [n] (ini_indices) - these q components of the initial state are unknowns beside theta
+        (pdp_sysid_step_gn_ini_batched, one launch): the evaluation point is (theta, ini_state or xobs[:, 0]), the sensitivity of x0[i_k] is column p + k of the same tile,
+        and every p above becomes W = p + q: (loss, grad [B, W]), or with gauss_newton the same dict over W plus ini_index (the list of indices).  An estimated component
+        still needs a finite starting value (the NaN check of skip_missing stays).  W > 16 or n > 16: the same row from the materialised sensitivities started at the
+        selection matrix."""
+        idx, mask = ini_indices(estimate_ini, self.n)
+        if idx:                                     # (nothing selected is estimate_ini=None: today's calls and today's rows)
+            return self._sysid_step_gn(u, xobs, theta, gauss_newton, skip_missing, ini_state, buffers, idx, mask)
         if gauss_newton or skip_missing or ini_state is not None:
             return self._sysid_step_gn(u, xobs, theta, gauss_newton, skip_missing, ini_state, buffers)
         torch = torch_cuda()
@@ -969,7 +1005,7 @@ class ModelLib:
         check(rc, "pdp_sysid_step_ws_batched")
         return loss, grad
 
-    def _sysid_step_gn(self, u, xobs, theta, gauss_newton, skip_missing, ini_state, buffers):
+    def _sysid_step_gn(self, u, xobs, theta, gauss_newton, skip_missing, ini_state, buffers, ini_index=(), ini_mask=0):
         if skip_missing:                            # judged on what the caller gave (a host array is not moved to the device first)
             first = ini_state if ini_state is not None else (xobs if hasattr(xobs, "data_ptr") else np.asarray(xobs, dtype=float))[:, 0]
             if bool(first.isnan().any()) if hasattr(first, "data_ptr") else bool(np.isnan(np.asarray(first, dtype=float)).any()):
@@ -980,6 +1016,9 @@ class ModelLib:
         B, T, n, p = u.shape[0], u.shape[1], self.n, self.p
         x0 = dev(ini_state).reshape(B, n).contiguous() if ini_state is not None else None
         th, tb = self._theta(theta, B)
+        q = len(ini_index)
+        if q:
+            return self._sysid_step_gn_ini(u, xobs, th, tb, gauss_newton, skip_missing, x0, buffers, list(ini_index), ini_mask)
         bufs = buffers if buffers is not None else {}
 
         def buf(key, shape):
@@ -1010,6 +1049,49 @@ class ModelLib:
         if not gauss_newton:
             return packed[:, p], packed[:, :p]
         return dict(packed_gn=packed, loss=packed[:, p], grad=packed[:, :p], gn=packed[:, p + 1:].view(B, p, p))
+
+    def _sysid_step_gn_ini(self, u, xobs, th, tb, gauss_newton, skip_missing, x0, buffers, ini_index, ini_mask):
+        """sysid_step with estimated components of the initial state (device tensors; th [1 or B, p], tb its row stride)"""
+        torch = torch_cuda()
+        B, T, n, p = u.shape[0], u.shape[1], self.n, self.p
+        W = p + len(ini_index)
+        bufs = buffers if buffers is not None else {}
+
+        def buf(key, shape):
+            t = bufs.get(key)
+            if t is None or tuple(t.shape) != tuple(shape):
+                t = bufs[key] = torch.empty(shape, dtype=torch.float64, device="cuda")
+            return t
+        loss, packed = buf("loss", (B,)), buf("packed_gn_ini", (B, W + 1 + W * W))
+        ws, nbytes = self._sysid_workspace(B, T)
+        rc = self.lib.pdp_sysid_step_gn_ini_batched(B, T, ptr(u), ptr(xobs), ptr(x0), ini_mask, ptr(th), tb, 32 if skip_missing else 0, ptr(loss), ptr(packed), ptr(ws),
+                                                    nbytes, current_stream_ptr())
+        if rc == -2:                                # beyond the fused kernels' tile: the same row from the materialised sensitivities, started at the selection matrix
+            if th.shape[-1] != p:                   # (parameters read in place from wider rows: theta_b | x0_b[idx])
+                th = th[:, :p].contiguous()
+            x = self.sysid_integrate(x0 if x0 is not None else xobs[:, 0].contiguous(), u, th)
+            F, E = self.sysid_auxsys(x, u, th)
+            Ew = torch.zeros((B, T, n, W), dtype=torch.float64, device="cuda")
+            Ew[..., :p] = E
+            X0 = torch.zeros((B, n, W), dtype=torch.float64, device="cuda")
+            for k, i in enumerate(ini_index):
+                X0[:, i, p + k] = 1.0
+            X = sysid_aux_integrate(F, Ew, X0)                                      # [B, T+1, n, W]
+            d = x - xobs
+            if skip_missing:                        # selects, as in the kernels: an observed entry with a non-finite state keeps its NaN in the loss
+                zero = torch.zeros((), dtype=torch.float64, device="cuda")
+                packed[:, W] = torch.where(xobs == xobs, d * d, zero).sum(dim=(1, 2))
+                obs = d == d
+                d, X = torch.where(obs, d, zero), torch.where(obs[..., None], X, zero)
+            else:
+                packed[:, W] = (d * d).sum(dim=(1, 2))
+            packed[:, :W] = torch.einsum("bti,btip->bp", d, X)
+            packed[:, W + 1:] = torch.einsum("btip,btiq->bpq", X, X).reshape(B, W * W)
+            rc = 0
+        check(rc, "pdp_sysid_step_gn_ini_batched")
+        if not gauss_newton:
+            return packed[:, W], packed[:, :W]
+        return dict(packed_gn=packed, loss=packed[:, W], grad=packed[:, :W], gn=packed[:, W + 1:].view(B, W, W), ini_index=ini_index)
 
 
 def load_model(path):
