@@ -24,6 +24,13 @@ Shared parameters with one initial state per recording (LMLoop.for_sysid(estimat
 trajectory (BatchedLMLoop.for_sysid(estimate_ini=)).
 
     python examples/sysid_pdp.py --system cartpole --method lm --observe 0,1 --estimate-ini 2,3
+
+--method lm --noise-sigma s0,s1,... --huber DELTA --outliers FRACTION: weighted and Huber-robust least squares (the weights= / huber_delta= keywords of the two loops; one
+launch per evaluation as before).  --noise-sigma adds Gaussian noise of standard deviation s_i to component i of the recorded states (t >= 1) and weights every entry of
+that component by 1 / s_i^2; --outliers moves that fraction of the recorded entries (t >= 1) by +-(0.5 .. 1.5); --huber is Huber's threshold on the standardised residual
+sqrt(w) (x - x_obs).  (--sigma is the spread of the starting parameter, as it always was.)
+
+    python examples/sysid_pdp.py --system cartpole --method lm --noise-sigma 1e-3,1e-3,1e-2,1e-2 --huber 3 --outliers 0.05
 """
 import argparse
 import os
@@ -65,6 +72,9 @@ def main():
     ap.add_argument("--observe", default=None, help="--method lm: only these state components are observed (comma-separated indices)")
     ap.add_argument("--per-trajectory", action="store_true", help="--method lm: one problem per trajectory, all in lock-step on the device (irl.BatchedLMLoop)")
     ap.add_argument("--estimate-ini", default=None, help="--method lm: these components of the initial states are unknown and estimated with the parameters (comma-separated)")
+    ap.add_argument("--noise-sigma", default=None, help="--method lm: per-component noise levels s0,s1,... added to the recorded states; the weights are 1 / s_i^2")
+    ap.add_argument("--huber", type=float, default=None, help="--method lm: Huber's threshold on the standardised residual")
+    ap.add_argument("--outliers", type=float, default=0.0, help="--method lm: this fraction of the recorded entries is moved by +-(0.5 .. 1.5)")
     a = ap.parse_args()
     partial = a.every > 1 or a.observe is not None
     if a.estimate_ini is not None and a.method != "lm":
@@ -73,6 +83,8 @@ def main():
         ap.error("--every / --observe need --method lm")
     if a.per_trajectory and a.method != "lm":
         ap.error("--per-trajectory needs --method lm")
+    if (a.noise_sigma is not None or a.huber is not None or a.outliers > 0) and a.method != "lm":
+        ap.error("--noise-sigma / --huber / --outliers need --method lm")
     env, dt = zoo.make_env(a.system, "sysid")
     sid = PDP.SysID(a.system)
     sid.setAuxvarVariable(env.dyn_auxvar)
@@ -84,6 +96,23 @@ def main():
     batch_states = [states[i] for i in range(states.shape[0])]
     rng = np.random.default_rng(a.seed)
     theta = true_parameter + a.sigma * rng.random(true_parameter.size) - a.sigma / 2
+    wls = {}
+    if a.noise_sigma is not None or a.outliers > 0:         # (row 0 stays as recorded: the rollouts start there)
+        states = states.copy()
+        if a.noise_sigma is not None:
+            sig = np.array([float(c) for c in a.noise_sigma.split(",")])
+            if sig.shape != (states.shape[2],) or not (sig > 0).all():
+                ap.error("--noise-sigma: %d positive values, one per state component" % states.shape[2])
+            states[:, 1:] += sig * rng.standard_normal(states[:, 1:].shape)
+            wls["weights"] = 1.0 / sig ** 2
+        if a.outliers > 0:
+            hit = rng.random(states.shape) < a.outliers
+            hit[:, 0] = False
+            k = int(hit.sum())
+            states[hit] += rng.choice([-1.0, 1.0], k) * (0.5 + rng.random(k))
+            print("%d of %d recorded entries are outliers" % (k, states.size))
+    if a.huber is not None:
+        wls["huber_delta"] = a.huber
     loss_trace, parameter_trace = [], []
     t0 = time.time()
     if a.method == "lm":
@@ -102,8 +131,8 @@ def main():
             if not partial:
                 data[:, 0, idx] = np.nan            # (what is estimated was not recorded)
             make = BatchedLMLoop.for_sysid if a.per_trajectory else LMLoop.for_sysid
-            loop = make(sid.model(), inputs, data, theta, ini_state=ini, skip_missing=True, estimate_ini=idx, **(dict(max_evals=min(a.iters, 100), loss_tol=1e-20)
-                                                                                                              if a.per_trajectory else {}))
+            loop = make(sid.model(), inputs, data, theta, ini_state=ini, skip_missing=True, estimate_ini=idx, **wls, **(dict(max_evals=min(a.iters, 100), loss_tol=1e-20)
+                                                                                                                     if a.per_trajectory else {}))
             r = loop.run() if a.per_trajectory else loop.run(max_evals=min(a.iters, 100), loss_tol=1e-20)
             if a.per_trajectory:
                 th, x0 = loop.split(r["theta"])
@@ -123,7 +152,7 @@ def main():
             return r
         if a.per_trajectory:
             kw = dict(ini_state=states[:, 0], skip_missing=True) if partial else {}
-            r = BatchedLMLoop.for_sysid(sid.model(), inputs, masked if partial else states, theta, max_evals=min(a.iters, 100), loss_tol=1e-20, **kw).run()
+            r = BatchedLMLoop.for_sysid(sid.model(), inputs, masked if partial else states, theta, max_evals=min(a.iters, 100), loss_tol=1e-20, **kw, **wls).run()
             for k in range(inputs.shape[0]):
                 print("problem %3d  %2d evaluations  %2d rejected  %-9s  loss %.6e -> %.6e  |theta - theta*| = %.2e  theta %s"
                       % (k, r["evaluations"][k], r["rejected"][k], r["state"][k], r["loss_trace"][k][0], r["loss"][k], np.abs(r["theta"][k] - true_parameter).max(),
@@ -131,9 +160,9 @@ def main():
             print("done: %d problems in %d launches, %.2f s; largest final loss %.4e" % (inputs.shape[0], r["launches"], time.time() - t0, np.max(r["loss"])))
             return r
         if partial:
-            loop = LMLoop.for_sysid(sid.model(), inputs, masked, theta, ini_state=states[:, 0], skip_missing=True)
+            loop = LMLoop.for_sysid(sid.model(), inputs, masked, theta, ini_state=states[:, 0], skip_missing=True, **wls)
         else:
-            loop = LMLoop.for_sysid(sid.model(), inputs, states, theta)
+            loop = LMLoop.for_sysid(sid.model(), inputs, states, theta, **wls)
         r = loop.run(max_evals=min(a.iters, 100), loss_tol=1e-20)
         loss_trace, parameter_trace = list(r["loss_trace"]), list(r["parameter_trace"])
         for k in range(len(loss_trace)):

@@ -759,12 +759,18 @@ class SysID(_CasadiFrontEnd):
         X = runtime.sysid_aux_integrate(np.stack(dynF)[None], np.stack(dynE)[None], ini_condition[None])
         return {"state_traj": [x for x in _np(X)[0]]}
 
-    def step_batch(self, batch_inputs, batch_states, auxvar_value, want_gauss_newton=False, skip_missing=False, ini_state=None, estimate_ini=None):
+    def step_batch(self, batch_inputs, batch_states, auxvar_value, want_gauss_newton=False, skip_missing=False, ini_state=None, estimate_ini=None, weights=None,
+                   huber_delta=None):
         """per-trajectory (loss [B], grad [B,p]) tensors; trajectories of equal horizon are one kernel launch.
         want_gauss_newton: a dict instead - packed_gn [B, p + 1 + p p] = grad | loss | G per trajectory with the Gauss-Newton matrix G = sum_t X_t' X_t of the loss, and
         loss, grad, gn [B,p,p] as views of it (what irl.LMLoop.for_sysid drives).  skip_missing: a NaN in batch_states is an entry that was not observed.
         ini_state [B,n]: the initial states of the rollouts instead of batch_states[:, 0] (runtime.ModelLib.sysid_step).  estimate_ini: state indices or a bool mask -
-        these components of the initial state are unknowns beside the parameters, and the gradient and G have p + q columns (runtime.ModelLib.sysid_step)."""
+        these components of the initial state are unknowns beside the parameters, and the gradient and G have p + q columns (runtime.ModelLib.sysid_step).
+        weights ([n], [T+1, n] or [B, T+1, n], >= 0, 0 = not observed), huber_delta (> 0): weighted and Huber-robust least squares; either one returns the dict
+        (runtime.ModelLib.sysid_step)."""
+        if weights is not None or huber_delta is not None:
+            return self.model().sysid_step(batch_inputs, batch_states, _vec(auxvar_value), gauss_newton=True, skip_missing=skip_missing, ini_state=ini_state,
+                                           estimate_ini=estimate_ini, weights=weights, huber_delta=huber_delta)
         if not (want_gauss_newton or skip_missing or ini_state is not None or estimate_ini is not None):
             return self.model().sysid_step(batch_inputs, batch_states, _vec(auxvar_value))
         return self.model().sysid_step(batch_inputs, batch_states, _vec(auxvar_value), gauss_newton=want_gauss_newton, skip_missing=skip_missing, ini_state=ini_state,

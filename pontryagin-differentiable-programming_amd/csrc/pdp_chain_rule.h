@@ -36,6 +36,13 @@
 //                    E, which the E gather returns for every column >= p anyway - the recursion, the contraction and the Gram product are the ones of the other modes,
 //                    no MFMA and no LDS word more per step.  W = p + q <= 16 (the host checks); the row is grad [W] | loss | G [W][W].  Row 0 is no longer silent: an
 //                    observed x_obs[0][i_k] adds d_0[i_k] to grad[p + k] and 1 to G[p + k][p + k].
+//   PDP_SYSID_GN_W, PDP_SYSID_GN_W_INI   weighted and Huber-robust least squares on PDP_SYSID_GN / PDP_SYSID_GN_INI (include/pdp_hip_sysid_wls.h).  The last trailing
+//                    argument is a SysidWls: the weights, their batch stride, Huber's delta and whether PDP_GRAD_SKIP_MISSING holds - run-time values, uniform over the
+//                    launch, NOT further template parameters.  An entry is observed iff w > 0 and (under the flag) x_obs is not NaN.  The lane-per-step pass leaves
+//                    s d in the DLX slot and s = sqrt(w psi) in a SECOND group of NX slots of the same pool row (both 0.0 where the entry is not observed, by a select)
+//                    and adds rho(e) to the loss (wls_slot: the division and the two square roots happen there, once per entry, lane-parallel); the sensitivity loop
+//                    gathers the tile S beside DX and scales the rows of X_t by a guarded product (wls_scale: S != 0 ? S X : 0.0 - 0 inf cannot appear) before it
+//                    contracts.  Both operands of every G product are the same scaled tile.  The recursion itself is never scaled.  The pool row is NX words longer.
 #pragma once
 #include "pdp_tile.h"
 
@@ -51,6 +58,8 @@
 #define PDP_SYSID_GN_MISS 2
 #define PDP_SYSID_GN_INI 3
 #define PDP_SYSID_GN_INI_MISS 4
+#define PDP_SYSID_GN_W 5
+#define PDP_SYSID_GN_W_INI 6
 
 namespace pdp {
 
@@ -68,8 +77,10 @@ struct FusedMode {
 };
 template <int MODE, int NT, int NINI>                      // NT parameter tiles, NINI trailing kernel arguments (the x0 of the Gauss-Newton modes; INI: x0 and the mask)
 struct SysidMode {
-    static constexpr bool INI = MODE == PDP_SYSID_GN_INI || MODE == PDP_SYSID_GN_INI_MISS;
-    static_assert(MODE == PDP_SYSID_PLAIN || (NT == 1 && NINI == 1 && (MODE == PDP_SYSID_GN || MODE == PDP_SYSID_GN_MISS)) || (NT == 1 && NINI == 2 && INI), "instantiation");
+    static constexpr bool WLS = MODE == PDP_SYSID_GN_W || MODE == PDP_SYSID_GN_W_INI;             // (its own observed-rule: never together with MISS)
+    static constexpr bool INI = MODE == PDP_SYSID_GN_INI || MODE == PDP_SYSID_GN_INI_MISS || MODE == PDP_SYSID_GN_W_INI;
+    static_assert(MODE == PDP_SYSID_PLAIN || (NT == 1 && NINI == 1 && (MODE == PDP_SYSID_GN || MODE == PDP_SYSID_GN_MISS)) || (NT == 1 && NINI == 2 && INI && !WLS) ||
+                      (NT == 1 && NINI == 2 && MODE == PDP_SYSID_GN_W) || (NT == 1 && NINI == 3 && MODE == PDP_SYSID_GN_W_INI), "instantiation");
     static constexpr bool GN = MODE != PDP_SYSID_PLAIN, MISS = MODE == PDP_SYSID_GN_MISS || MODE == PDP_SYSID_GN_INI_MISS;
     static constexpr Residual RES = MISS ? RES_MISS_DIFF : RES_PLAIN;
 };
@@ -160,6 +171,37 @@ PDP_DEV void sysid_ini_store(double* __restrict__ G, int W, int lane, const d4 G
         const int row = tile_row(lane, r);
         if (row < W && col < W) G[row * W + col] = Gn[r];
     }
+}
+
+
+// ---- PDP_SYSID_GN_W*: weighted / Huber least squares.  The run-time arguments of the two modes, one struct at the end of the kernels' trailing pack.  `w` is never
+// NULL: without weights the host passes x_obs (a readable block of the same shape) and has_w = 0, and the pass SELECTS 1.0 - no conditional block around the load.
+struct SysidWls {
+    const double* w;            // [B or 1][T+1][NX]
+    long long bstride;          // (T+1) NX, or 0: one block shared by the batch
+    double delta;               // Huber's threshold on the standardised residual; +inf: off
+    int has_w, skip;            // weights given; PDP_GRAD_SKIP_MISSING
+};
+// the slot rule of one entry.  v: the state; o: x_obs; wl: the word loaded through SysidWls::w.  slot_d, slot_s: the caller's two LDS elements (no address is formed
+// in here).  e = sqrt(w) d, psi = 1 (|e| <= delta) or delta / |e|, s = sqrt(w psi); rho = e^2 or 2 delta |e| - delta^2.  A NaN e takes the second branch of both and
+// stays a NaN; delta = +inf takes the first for every finite and infinite e.
+PDP_DEV void wls_slot(double& slot_d, double& slot_s, double v, double o, double wl, const SysidWls a, double& lsum) {
+    const double w = a.has_w ? wl : 1.0;
+    const double d = v - o;
+    const bool obs = (w > 0.0) && !(a.skip && o != o);
+    const double e = __builtin_sqrt(w) * d, ae = __builtin_fabs(e);
+    const bool quad = ae <= a.delta;
+    const double s = __builtin_sqrt(quad ? w : w * (a.delta / ae));
+    slot_d = obs ? s * d : 0.0;
+    slot_s = obs ? s : 0.0;
+    lsum += obs ? (quad ? e * e : 2.0 * a.delta * ae - a.delta * a.delta) : 0.0;
+}
+// the rows of X scaled by the tile S (the s of a row broadcast over its columns): a select guards the product
+PDP_DEV d4 wls_scale(const d4 S, const d4 X) {
+    d4 Xm;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Xm[r] = S[r] != 0.0 ? S[r] * X[r] : 0.0;
+    return Xm;
 }
 
 }  // namespace pdp

@@ -200,7 +200,7 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
                                                                  Ini... ini) {
     using SM = SysidMode<MODE, NT, sizeof...(Ini)>;
     constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP, CH = Mdl::CHUNK;
-    constexpr int NC = 1 + Mdl::PATH_NCONST, DLX = Mdl::PATH_NVAR, STRIDE = (Mdl::PATH_NVAR + NX) | 1;
+    constexpr int NC = 1 + Mdl::PATH_NCONST, DLX = Mdl::PATH_NVAR, STRIDE = (Mdl::PATH_NVAR + (SM::WLS ? 2 : 1) * NX) | 1;      // (WLS: s in the slots DLX + NX ..)
     static_assert(TPW == 1 || TPW == 2 || TPW == 4, "trajectories per workgroup");
     extern __shared__ __attribute__((aligned(16))) double lds_all[];
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, slot = wid & (TPW - 1);
@@ -211,12 +211,14 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
     double* blk = lds_all + (size_t)slot * slice;
     double* pool = blk + NC;
     double* xs = pool + CH * STRIDE;         // (T+1) x NX
-    double* dlT = xs + (T + 1) * NX;         // NX
-    double* us = dlT + NX + 1;               // T x NU
+    double* dlT = xs + (T + 1) * NX;         // NX   (WLS: and the NX scales of the terminal row behind them, at dlT + NX + 1)
+    double* us = dlT + NX + 1 + (SM::WLS ? NX : 0);         // T x NU
     double* dump = us + T * NU;              // 64 + NX
     int* fl = (int*)(dump + 64 + NX);        // stages rolled out so far
     const double* ub = u + (int64_t)bb * T * NU;
     const double* ob = xobs + (int64_t)bb * (T + 1) * NX;
+    [[maybe_unused]] const double* wb = nullptr;           // WLS: this trajectory's weights
+    if constexpr (SM::WLS) wb = sysid_wls(ini...).w + (int64_t)bb * sysid_wls(ini...).bstride;
     if (roller) {
         if (lane == 0) { blk[0] = 0.0; fl[0] = 0; }
         for (int i_ = lane; i_ < Mdl::PATH_NCONST; i_ += 64) blk[1 + i_] = Mdl::path_const(i_);
@@ -261,6 +263,8 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
         Gather gFT, gDX, gE[NT];
         make_gather(gFT, lane, NC, STRIDE, [](int r, int c) { return (r < NX && c < NX) ? Mdl::path_code(0, c * NX + r) : -1; });
         make_gather(gDX, lane, NC, STRIDE, [](int r, int c) { return (r < NX) ? DLX + r : -1; });
+        [[maybe_unused]] Gather gS;                        // WLS: the scales s of the rows
+        if constexpr (SM::WLS) make_gather(gS, lane, NC, STRIDE, [](int r, int c) { return (r < NX) ? DLX + NX + r : -1; });
 #pragma unroll
         for (int j = 0; j < NT; ++j)
             make_gather(gE[j], lane, NC, STRIDE, [j](int r, int c) { return (r < NX && 16 * j + c < NP) ? Mdl::path_code(1, r * NP + 16 * j + c) : -1; });
@@ -281,7 +285,11 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
                 double xc[NX], uc[NU];
                 double* row = pool + lane * STRIDE;
 #pragma unroll
-                for (int i = 0; i < NX; ++i) { xc[i] = xs[t * NX + i]; residual_slot<SM::RES>(row[DLX + i], xc[i], ob[t * NX + i], lsum); }
+                for (int i = 0; i < NX; ++i) {
+                    xc[i] = xs[t * NX + i];
+                    if constexpr (SM::WLS) wls_slot(row[DLX + i], row[DLX + NX + i], xc[i], ob[t * NX + i], wb[t * NX + i], sysid_wls(ini...), lsum);
+                    else residual_slot<SM::RES>(row[DLX + i], xc[i], ob[t * NX + i], lsum);
+                }
 #pragma unroll
                 for (int i = 0; i < NU; ++i) uc[i] = us[t * NU + i];
                 PackedSink s{row};
@@ -294,6 +302,11 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
                     d4 E = gather_tile(blk, gE[j], tl);
+                    if constexpr (SM::WLS) {          // DX carries s d, Xm = s X: grad += (s d)' (s X), G += (s X)' (s X)
+                        const d4 Xm = wls_scale(gather_tile(blk, gS, tl), X[j]);
+                        acc[j] += contract_step(DX, Xm);
+                        Gn = gram_add<false>(Xm, Gn);
+                    } else
                     if constexpr (SM::MISS) {         // (pdp_chain_rule.h: mask_step, in this kernel's own text; NT == 1)
                         d4 Xm;
 #pragma unroll
@@ -311,6 +324,8 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
         wg_wait_ge(fl, T);                                   // x_T
         wave_lds_sync();
         if (lane < NX) {
+            if constexpr (SM::WLS) wls_slot(dlT[lane], dlT[NX + 1 + lane], xs[T * NX + lane], ob[T * NX + lane], wb[T * NX + lane], sysid_wls(ini...), lsum);
+            else
             if constexpr (SM::MISS) { const double o = ob[T * NX + lane]; residual_slot<SM::RES>(dlT[lane], xs[T * NX + lane], o, lsum); }      // (x_obs first, as in sysid_step_kernel)
             else residual_slot<SM::RES>(dlT[lane], xs[T * NX + lane], ob[T * NX + lane], lsum);
         }
@@ -320,6 +335,8 @@ __global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, co
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = tile_row(lane, r);
+                if constexpr (SM::WLS) { if (row < NX) { const double sT = dlT[NX + 1 + row]; X[j][r] = sT != 0.0 ? sT * X[j][r] : 0.0; acc[j] += dlT[row] * X[j][r]; } }      // (X_T scaled in place)
+                else
                 if constexpr (SM::MISS) {              // (observed(), in this kernel's own text: through it two of the five models' instantiations lost an instruction; X_T is masked in place)
                     if (row < NX) { const double d = dlT[row]; const bool obs = d == d; X[j][r] = obs ? X[j][r] : 0.0; acc[j] += (obs ? d : 0.0) * X[j][r]; }
                 } else {

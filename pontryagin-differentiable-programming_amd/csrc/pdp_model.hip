@@ -5,6 +5,7 @@
 #include "../../include/pdp_hip.h"
 #include "../../include/pdp_hip_sysid_gn.h"
 #include "../../include/pdp_hip_sysid_ini.h"
+#include "../../include/pdp_hip_sysid_wls.h"
 #ifndef PDP_MODEL_HEADER
 #error "compile with -DPDP_MODEL_HEADER=\"generated/<model>.h\""
 #endif
@@ -558,11 +559,15 @@ int64_t sysid_step_ws_bytes(int B, int T) {
 // MODE (PDP_SYSID_PLAIN / PDP_SYSID_GN / PDP_SYSID_GN_MISS): the instantiation of the fused kernels.  The Gauss-Newton modes write the packed row grad | loss | G through
 // `grad`, start the rollouts from x0 [B][n] (NULL: x_obs[:, 0]) - in the kernels through their trailing argument, in the pre-pass through its pointer and stride - and
 // exist for p <= 16.  PDP_SYSID_GN_INI / PDP_SYSID_GN_INI_MISS: the Gauss-Newton modes with the components of x0 that `ini_mask` names as further unknowns (the
-// kernels' second trailing argument; the row is grad | loss | G over W = p + popcount(ini_mask) <= 16 unknowns).  Same dispatch, thresholds and switches in every mode.
+// kernels' second trailing argument; the row is grad | loss | G over W = p + popcount(ini_mask) <= 16 unknowns).  PDP_SYSID_GN_W / PDP_SYSID_GN_W_INI: weighted and
+// Huber-robust least squares on PDP_SYSID_GN / PDP_SYSID_GN_INI (`wls`, the kernels' last trailing argument; NX more words per pool row and behind dlT, and the
+// Gauss-Newton modes' eight workgroups per CU in the given-trajectory kernel).  Same dispatch, thresholds and switches in every mode.
 template <class Mdl, int MODE = PDP_SYSID_PLAIN>
 int sysid_step(int B, int T, const double* u, const double* xobs, const double* th, int tb, double* loss, double* grad, void* ws, int64_t wsb, void* st,
-               const double* x0 = nullptr, [[maybe_unused]] unsigned ini_mask = 0) {
-    constexpr bool INI = MODE == PDP_SYSID_GN_INI || MODE == PDP_SYSID_GN_INI_MISS;
+               const double* x0 = nullptr, [[maybe_unused]] unsigned ini_mask = 0, [[maybe_unused]] SysidWls wls = {}) {
+    constexpr bool WLS = MODE == PDP_SYSID_GN_W || MODE == PDP_SYSID_GN_W_INI;
+    constexpr bool INI = MODE == PDP_SYSID_GN_INI || MODE == PDP_SYSID_GN_INI_MISS || MODE == PDP_SYSID_GN_W_INI;
+    constexpr int EXTRA = WLS ? Mdl::NX : 0;                // further words per pool row (sysid_slice)
     if constexpr (Mdl::KIND == PDP_KIND_SYSID && Mdl::NX <= 16 && Mdl::NP <= (MODE == PDP_SYSID_PLAIN ? 64 : (INI ? 15 : 16))) {
         if (B <= 0 || T <= 0 || !u || !xobs || !th || !loss || !grad) return PDP_E_ARG;
         if constexpr (INI) { if (Mdl::NP + __builtin_popcount(ini_mask) > 16) return PDP_E_SIZE; }
@@ -578,20 +583,26 @@ int sysid_step(int B, int T, const double* u, const double* xobs, const double* 
         static const int rows_env = env_int("PDP_SYSID_ROWS", 0), wgs_env = env_int("PDP_SYSID_GIVEN_WGS", 0);
         const int cus = device_cu_count();
         const int rows = rows_env > 0 ? (rows_env < Mdl::CHUNK ? rows_env : Mdl::CHUNK)
-                         : (xgiven ? sysid_rows_given<Mdl>(T, wgs_env > 0 ? wgs_env : SYSID_GIVEN_WGS<MODE>) : sysid_rows<Mdl>(B, T, cus));
-        const size_t lds = sizeof(double) * (size_t)sysid_slice<Mdl>(T, rows, xgiven != nullptr);
+                         : (xgiven ? sysid_rows_given<Mdl>(T, wgs_env > 0 ? wgs_env : SYSID_GIVEN_WGS<MODE>, EXTRA) : sysid_rows<Mdl>(B, T, cus, EXTRA));
+        const size_t lds = sizeof(double) * (size_t)sysid_slice<Mdl>(T, rows, xgiven != nullptr, EXTRA);
         if (lds > 150 * 1024) return PDP_E_SIZE;
         // PDP_SYSID_VARIANT: 2 = rollout wave + sensitivity wave per trajectory (pdp_cp_pair_kernels.h), the default; 1 = one wavefront per trajectory
         static const int variant = env_int("PDP_SYSID_VARIANT", 2);
         // the pair pays while SIMDs would idle (B = 256, T = 200: 0.105 -> 0.072 ms); once every SIMD has a trajectory the two waves only share what one had
         // (B = 1024: 0.0667 against 0.0685 ms, profiles/r03_pair_pipeline.txt) - the one-wave kernel stays for those batches
         if (variant == 2 && B <= 2 * cus && !xgiven) {
-            const int slice = sysid_slice<Mdl>(T), tpw = traj_per_workgroup(B, cus, 2);
+            const int slice = sysid_slice<Mdl>(T, Mdl::CHUNK, false, EXTRA), tpw = traj_per_workgroup(B, cus, 2);
             if (slice * tpw * (int)sizeof(double) <= 160 * 1024)
                 return with_int<1, 2>(tpw, [&](auto K) {
                     if constexpr (MODE == PDP_SYSID_PLAIN)
                     return launch(sysid_step2_kernel<Mdl, NT, K()>, dim3((B + K() - 1) / K()), dim3(128 * K()), slice * K() * sizeof(double), S(st), B, T, u, xobs, th, tb, loss,
                                   grad, slice);
+                    else if constexpr (MODE == PDP_SYSID_GN_W)
+                        return launch(sysid_step2_kernel<Mdl, NT, K(), MODE, const double*, SysidWls>, dim3((B + K() - 1) / K()), dim3(128 * K()),
+                                      slice * K() * sizeof(double), S(st), B, T, u, xobs, th, tb, loss, grad, slice, x0, wls);
+                    else if constexpr (MODE == PDP_SYSID_GN_W_INI)
+                        return launch(sysid_step2_kernel<Mdl, NT, K(), MODE, const double*, unsigned, SysidWls>, dim3((B + K() - 1) / K()), dim3(128 * K()),
+                                      slice * K() * sizeof(double), S(st), B, T, u, xobs, th, tb, loss, grad, slice, x0, ini_mask, wls);
                     else if constexpr (INI)
                         return launch(sysid_step2_kernel<Mdl, NT, K(), MODE, const double*, unsigned>, dim3((B + K() - 1) / K()), dim3(128 * K()),
                                       slice * K() * sizeof(double), S(st), B, T, u, xobs, th, tb, loss, grad, slice, x0, ini_mask);
@@ -603,6 +614,12 @@ int sysid_step(int B, int T, const double* u, const double* xobs, const double* 
         return with_bool(xgiven != nullptr, [&](auto GIVEN) {
             if constexpr (MODE == PDP_SYSID_PLAIN)
             return launch(sysid_step_kernel<Mdl, NT, GIVEN()>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad, rows, xgiven);
+            else if constexpr (MODE == PDP_SYSID_GN_W)
+                return launch(sysid_step_kernel<Mdl, NT, GIVEN(), MODE, const double*, SysidWls>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad, rows, xgiven,
+                              x0, wls);
+            else if constexpr (MODE == PDP_SYSID_GN_W_INI)
+                return launch(sysid_step_kernel<Mdl, NT, GIVEN(), MODE, const double*, unsigned, SysidWls>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad,
+                              rows, xgiven, x0, ini_mask, wls);
             else if constexpr (INI)
                 return launch(sysid_step_kernel<Mdl, NT, GIVEN(), MODE, const double*, unsigned>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad, rows,
                               xgiven, x0, ini_mask);
@@ -728,6 +745,20 @@ int pdp_sysid_step_gn_ini_batched(int B, int T, const double* u, const double* x
     return (flags & PDP_GRAD_SKIP_MISSING)
                ? sysid_step<PdpModel, PDP_SYSID_GN_INI_MISS>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0, mask)
                : sysid_step<PdpModel, PDP_SYSID_GN_INI>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0, mask);
+}
+int pdp_sysid_step_wls_batched(int B, int T, const double* u, const double* x_obs, const double* x0, int ini_mask, const double* weights, int64_t weights_bstride,
+                               double huber_delta, const double* theta, int tb, int flags, double* loss, double* packed, void* workspace, int64_t workspace_bytes,
+                               void* stream) {
+    if (B <= 0 || T <= 0 || !u || !x_obs || !theta || !loss || !packed || (flags & ~PDP_GRAD_SKIP_MISSING)) return PDP_E_ARG;
+    if (!(huber_delta > 0.0)) return PDP_E_ARG;                                                  // (<= 0 and NaN)
+    if (weights_bstride != 0 && weights_bstride != (int64_t)(T + 1) * PdpModel::NX) return PDP_E_ARG;
+    if (PdpModel::NX < 32 && ((unsigned)ini_mask >> PdpModel::NX) != 0) return PDP_E_ARG;       // a mask bit >= n
+    const unsigned mask = (unsigned)ini_mask;
+    // without weights the kernels load x_obs in their place (a readable block of the same shape) and select 1.0
+    const SysidWls wls{weights ? weights : x_obs, weights ? (long long)weights_bstride : (long long)(T + 1) * PdpModel::NX, huber_delta, weights ? 1 : 0,
+                       (flags & PDP_GRAD_SKIP_MISSING) ? 1 : 0};
+    return mask ? sysid_step<PdpModel, PDP_SYSID_GN_W_INI>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0, mask, wls)
+                : sysid_step<PdpModel, PDP_SYSID_GN_W>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0, 0u, wls);
 }
 
 }  // extern "C"

@@ -321,7 +321,7 @@ class LMLoop:
         return loop
 
     @classmethod
-    def for_sysid(cls, mdl, inputs, states, theta0, n_total=None, ini_state=None, skip_missing=False, estimate_ini=None, **kw):
+    def for_sysid(cls, mdl, inputs, states, theta0, n_total=None, ini_state=None, skip_missing=False, estimate_ini=None, weights=None, huber_delta=None, **kw):
         """The SysID drivers' problem (Examples/SysID/*/..._PDP.py) as nonlinear least squares: mdl a runtime.ModelLib of a SysID model, inputs [B, T, m] and states
         [B, T+1, n] the recorded data (this rank's shard under torch.distributed; n_total as in parallel.allreduce_mean_packed), theta0 [p] shared by all trajectories.
         evaluate(theta) is ONE launch - sysid_step with gauss_newton=True: loss, gradient and G = J'J from the sensitivity tiles of the fused kernel - and hands the packed
@@ -334,10 +334,16 @@ class LMLoop:
         components start from ini_state, or states[:, 0]) or [N].  An evaluation is one launch of sysid_step(estimate_ini=) at (theta, x0); the arrow-shaped normal
         equations are assembled from the B augmented rows on the device (arrow_normal_equations) and go to the host in one copy; a non-finite row makes the point None;
         the solve is lm_step's, dense on the host.  loop.split(vector) -> (theta [p], ini_state [B, n]).  N > 256, n_total, or a process group of more than one rank is a
-        ValueError: many recordings, or recordings spread over ranks, are BatchedLMLoop.for_sysid(estimate_ini=)'s problems, one theta per trajectory."""
-        idx = rt.ini_indices(estimate_ini, mdl.n)[0]
+        ValueError: many recordings, or recordings spread over ranks, are BatchedLMLoop.for_sysid(estimate_ini=)'s problems, one theta per trajectory.
+        weights ([n], [T+1, n] or [B, T+1, n], >= 0, 0 = not observed), huber_delta (> 0): the row the loop minimises carries the weighted / Huber loss, its exact half
+        derivative and the Gauss-Newton matrix of iteratively reweighted least squares (ModelLib.sysid_step, pdp_sysid_step_wls_batched); the loop itself is unchanged.
+        They are checked once, here."""
+        idx, mask = rt.ini_indices(estimate_ini, mdl.n)
+        wls = _wls_keywords(mdl, inputs, weights, huber_delta)
         if idx:                                     # (nothing selected is estimate_ini=None)
-            return cls._for_sysid_ini(mdl, inputs, states, theta0, n_total, ini_state, skip_missing, idx, **kw)
+            return cls._for_sysid_ini(mdl, inputs, states, theta0, n_total, ini_state, skip_missing, idx, mask=mask, wls=wls, **kw)
+        if wls and skip_missing:
+            _refuse_nan_start("LMLoop.for_sysid", states, ini_state, "states")
         from . import parallel
         torch = rt.torch_cuda()
         inputs, states = rt.dev(inputs), rt.dev(states)
@@ -347,7 +353,10 @@ class LMLoop:
         bufs = {}
 
         def evaluate(theta):
-            out = mdl.sysid_step(inputs, states, theta, gauss_newton=True, skip_missing=skip_missing, ini_state=x0, buffers=bufs)
+            if wls:
+                out = mdl._sysid_step_wls_dev(inputs, states, *mdl._theta(theta, B), skip_missing, x0, bufs, [], 0, *wls)
+            else:
+                out = mdl.sysid_step(inputs, states, theta, gauss_newton=True, skip_missing=skip_missing, ini_state=x0, buffers=bufs)
             bad = (~torch.isfinite(out["packed_gn"])).any(dim=1)
             row = parallel.mean_row_checked(out["packed_gn"], bad, n_total)                # (a bad row makes the point None before its sums are read)
             if row is None:
@@ -357,7 +366,7 @@ class LMLoop:
         return cls(evaluate, theta0, **kw)
 
     @classmethod
-    def _for_sysid_ini(cls, mdl, inputs, states, theta0, n_total, ini_state, skip_missing, idx, **kw):
+    def _for_sysid_ini(cls, mdl, inputs, states, theta0, n_total, ini_state, skip_missing, idx, mask=0, wls=None, **kw):
         if skip_missing:                            # an estimated component still needs a finite starting value
             _refuse_nan_start("LMLoop.for_sysid", states, ini_state, "states")
         torch = rt.torch_cuda()
@@ -385,7 +394,10 @@ class LMLoop:
         def evaluate(vector):
             v = rt.dev(np.ascontiguousarray(vector, dtype=float))                         # one copy to the device: theta and the estimated components
             x0.index_copy_(1, cols, v[p:].view(B, q))
-            out = mdl.sysid_step(inputs, states, v[:p], gauss_newton=True, skip_missing=skip_missing, ini_state=x0, buffers=bufs, estimate_ini=idx)
+            if wls:
+                out = mdl._sysid_step_wls_dev(inputs, states, *mdl._theta(v[:p], B), skip_missing, x0, bufs, idx, mask, *wls)
+            else:
+                out = mdl.sysid_step(inputs, states, v[:p], gauss_newton=True, skip_missing=skip_missing, ini_state=x0, buffers=bufs, estimate_ini=idx)
             flat = arrow_normal_equations(out["packed_gn"], p, q).cpu().numpy()            # one copy to the host
             if not np.isfinite(flat).all():         # every entry of every row is in there, summed or as it is: a non-finite row shows
                 return None
@@ -400,6 +412,15 @@ class LMLoop:
         loop = cls(evaluate, th0, **kw)
         loop.split = split
         return loop
+
+
+def _wls_keywords(mdl, inputs, weights, huber_delta):
+    """The weights / huber_delta keywords of the for_sysid constructors, checked ONCE and with the weights on the device: () when neither is given, else the last three
+    arguments of ModelLib._sysid_step_wls_dev - (weights on the device or None, their batch stride, delta)."""
+    if weights is None and huber_delta is None:
+        return ()
+    w, wbs, delta = rt.wls_arguments(weights, huber_delta, int(inputs.shape[0]), int(inputs.shape[1]), mdl.n)
+    return (rt.dev(w).contiguous() if w is not None else None, wbs, delta)
 
 
 class BatchedLMLoop:
@@ -475,7 +496,8 @@ class BatchedLMLoop:
                 "accepted": acc, "state": [rt.LM_STATES[v] for v in state], "theta": self.theta.cpu().numpy(), "loss": loss, "launches": self.launches}
 
     @classmethod
-    def for_sysid(cls, mdl, inputs, states, theta0, samples_per_problem=1, ini_state=None, skip_missing=False, estimate_ini=None, **kw):
+    def for_sysid(cls, mdl, inputs, states, theta0, samples_per_problem=1, ini_state=None, skip_missing=False, estimate_ini=None, weights=None, huber_delta=None,
+                  **kw):
         """One SysID problem per group of samples_per_problem consecutive trajectories: inputs [K S, T, m], states [K S, T+1, n], theta0 [K, p] or [p].  An evaluation is
         ONE launch of mdl.sysid_step(gauss_newton=True) with the trial points as per-sample parameters; a sample is bad where its row holds a non-finite entry (formed on
         the device).  skip_missing, ini_state: as in LMLoop.for_sysid (a NaN in the initial state under skip_missing is a ValueError before any launch).
@@ -483,12 +505,14 @@ class BatchedLMLoop:
         unknowns; theta0 is [p], [K, p] (the estimated components start from ini_state, or states[:, 0]) or [K, W].  An evaluation is one launch of
         pdp_sysid_step_gn_ini_batched: theta is read from the trial rows in place (row stride W), the estimated components are copied from the trial rows into a
         persistent x0 buffer at a fixed address - one small device copy, no host synchronisation; the update launch is pdp_lm_update_batched's with W as its p.
-        loop.split(theta [K, W]) -> (theta [K, p], ini_state [K, n])."""
+        loop.split(theta [K, W]) -> (theta [K, p], ini_state [K, n]).
+        weights, huber_delta: as in LMLoop.for_sysid - checked once here, then every evaluation is one launch of pdp_sysid_step_wls_batched."""
+        wls = _wls_keywords(mdl, inputs, weights, huber_delta)
         if skip_missing:                            # judged on what the caller gave (a host array is not moved to the device first)
             _refuse_nan_start("BatchedLMLoop.for_sysid", states, ini_state, "states")
         idx, mask = rt.ini_indices(estimate_ini, mdl.n)
         if idx:                                     # (nothing selected is estimate_ini=None; an estimated component still needs the finite starting value checked above)
-            return cls._for_sysid_ini(mdl, inputs, states, theta0, samples_per_problem, ini_state, skip_missing, idx, mask, **kw)
+            return cls._for_sysid_ini(mdl, inputs, states, theta0, samples_per_problem, ini_state, skip_missing, idx, mask, wls=wls, **kw)
         torch = rt.torch_cuda()
         inputs, states = rt.dev(inputs), rt.dev(states)
         B, T, S = int(inputs.shape[0]), int(inputs.shape[1]), int(samples_per_problem)
@@ -497,13 +521,16 @@ class BatchedLMLoop:
         bufs = {}
 
         def evaluate_rows(trial):
-            out = mdl.sysid_step(inputs, states, trial, gauss_newton=True, skip_missing=skip_missing, ini_state=x0, buffers=bufs)
+            if wls:
+                out = mdl._sysid_step_wls_dev(inputs, states, *mdl._theta(trial, B), skip_missing, x0, bufs, [], 0, *wls)
+            else:
+                out = mdl.sysid_step(inputs, states, trial, gauss_newton=True, skip_missing=skip_missing, ini_state=x0, buffers=bufs)
             return out["packed_gn"], (~torch.isfinite(out["packed_gn"])).any(dim=1).to(torch.int32)
 
         return cls(evaluate_rows, theta0, samples_per_problem=S, K=B // S, **kw)
 
     @classmethod
-    def _for_sysid_ini(cls, mdl, inputs, states, theta0, samples_per_problem, ini_state, skip_missing, idx, mask, **kw):
+    def _for_sysid_ini(cls, mdl, inputs, states, theta0, samples_per_problem, ini_state, skip_missing, idx, mask, wls=None, **kw):
         torch = rt.torch_cuda()
         inputs, states = rt.dev(inputs), rt.dev(states)
         K, T, p, q = int(inputs.shape[0]), int(inputs.shape[1]), mdl.p, len(idx)
@@ -527,7 +554,10 @@ class BatchedLMLoop:
 
         def evaluate_rows(trial):                   # trial [K, W] at a fixed address: theta_k in its first p columns (read in place), x0_k[idx] behind them
             x0.index_copy_(1, cols, trial[:, p:])
-            out = mdl._sysid_step_gn_ini(inputs, states, trial, W, True, skip_missing, x0, bufs, idx, mask)
+            if wls:
+                out = mdl._sysid_step_wls_dev(inputs, states, trial, W, skip_missing, x0, bufs, idx, mask, *wls)
+            else:
+                out = mdl._sysid_step_gn_ini(inputs, states, trial, W, True, skip_missing, x0, bufs, idx, mask)
             return out["packed_gn"], (~torch.isfinite(out["packed_gn"])).any(dim=1).to(torch.int32)
 
         def split(theta):

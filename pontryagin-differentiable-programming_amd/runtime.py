@@ -77,6 +77,7 @@ CORE_EXT_SYMBOLS = ["pdp_lm_update_batched"]             # declared in the exten
 MODEL_EXT_SYMBOLS = ["pdp_sysid_step_gn_batched"]        # declared in the extension headers (include/pdp_hip_sysid_gn.h): include/pdp_hip.h is pinned at its entry points
 
 MODEL_INI_SYMBOLS = ["pdp_sysid_step_gn_ini_batched"]   # include/pdp_hip_sysid_ini.h: one list per extension header
+MODEL_WLS_SYMBOLS = ["pdp_sysid_step_wls_batched"]      # include/pdp_hip_sysid_wls.h
 
 _core = None
 
@@ -317,6 +318,35 @@ def ini_indices(estimate_ini, n):
     return idx, sum(1 << i for i in idx)
 
 
+def _refuse_nan_initial_state(xobs, ini_state):
+    """skip_missing: a NaN in the initial state the rollouts would start from - ini_state, else xobs[:, 0] - is a ValueError before any launch.  Judged on what the
+    caller gave (a host array is not moved to the device first)."""
+    first = ini_state if ini_state is not None else (xobs if hasattr(xobs, "data_ptr") else np.asarray(xobs, dtype=float))[:, 0]
+    if bool(first.isnan().any()) if hasattr(first, "data_ptr") else bool(np.isnan(np.asarray(first, dtype=float)).any()):
+        raise ValueError("sysid_step: skip_missing=True and the initial state (%s) holds a NaN: give ini_state [B, n]" % ("xobs[:, 0]" if ini_state is None else "ini_state"))
+
+
+def wls_arguments(weights, huber_delta, B, T, n):
+    """The weights and Huber's threshold of pdp_sysid_step_wls_batched, normalised and checked on what the caller gave (a host array is not moved to the device first):
+    returns (weights as given but shaped [T+1, n] or [B, T+1, n], or None; weights_bstride; delta as a float, +inf for off).  weights broadcast from [n], [T+1, n] or
+    [B, T+1, n]; a negative or non-finite weight, another shape, or a huber_delta that is not > 0 is a ValueError before any launch.  The loops of irl.py call it
+    once and evaluate many times (ModelLib._sysid_step_wls_dev)."""
+    delta = float("inf") if huber_delta is None else float(huber_delta)
+    if not delta > 0.0:
+        raise ValueError("huber_delta: a threshold > 0 (None: plain least squares), got %r" % (huber_delta,))
+    if weights is None:
+        return None, 0, delta
+    w = weights if hasattr(weights, "data_ptr") else np.asarray(weights, dtype=float)
+    shape = tuple(w.shape)
+    if shape not in ((n,), (T + 1, n), (B, T + 1, n)):
+        raise ValueError("weights: shape [n], [T+1, n] or [B, T+1, n] = (%d,), (%d, %d) or (%d, %d, %d), got %s" % (n, T + 1, n, B, T + 1, n, shape))
+    if not bool(((w >= 0) & (w < float("inf"))).all()):          # (a NaN fails the comparison)
+        raise ValueError("weights: finite and >= 0 (0: the entry is not observed)")
+    if len(shape) == 1:
+        w = w.expand(T + 1, n) if hasattr(w, "data_ptr") else np.broadcast_to(w, (T + 1, n))
+    return w, (0 if len(w.shape) == 2 else (T + 1) * n), delta
+
+
 # ------------------------------------------------------------------------------------------------------
 # per-model libraries (section B of include/pdp_hip.h)
 # ------------------------------------------------------------------------------------------------------
@@ -352,6 +382,8 @@ _MODEL_SIGS = {
     "pdp_sysid_step_gn_batched": (_I, [_I, _I, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I64, _VP]),
     # include/pdp_hip_sysid_ini.h
     "pdp_sysid_step_gn_ini_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _I, _I, _VP, _VP, _VP, _I64, _VP]),
+    # include/pdp_hip_sysid_wls.h
+    "pdp_sysid_step_wls_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _I64, C.c_double, _VP, _I, _I, _VP, _VP, _VP, _I64, _VP]),
 }
 _models = {}
 
@@ -968,7 +1000,7 @@ class ModelLib:
                 del cache[key]
         return ws, nbytes
 
-    def sysid_step(self, u, xobs, theta, gauss_newton=False, skip_missing=False, ini_state=None, buffers=None, estimate_ini=None):
+    def sysid_step(self, u, xobs, theta, gauss_newton=False, skip_missing=False, ini_state=None, buffers=None, estimate_ini=None, weights=None, huber_delta=None):
         """SysID.step per trajectory (pdp_sysid_step_ws_batched): (loss [B], grad [B, p]).  Models beyond the fused kernels' tiles (n > 16 or p > 64) take the reference's own
         route kernel by kernel - integrateDyn -> getAuxSys -> integrateAuxSys (size-generic kernels) -> the chain rule of PDP.py:1285-1291 as two tensor contractions: no size
         is refused.
@@ -982,8 +1014,15 @@ class ModelLib:
         (pdp_sysid_step_gn_ini_batched, one launch): the evaluation point is (theta, ini_state or xobs[:, 0]), the sensitivity of x0[i_k] is column p + k of the same tile,
         and every p above becomes W = p + q: (loss, grad [B, W]), or with gauss_newton the same dict over W plus ini_index (the list of indices).  An estimated component
         still needs a finite starting value (the NaN check of skip_missing stays).  W > 16 or n > 16: the same row from the materialised sensitivities started at the
-        selection matrix."""
+        selection matrix.
+        weights, huber_delta: weighted and Huber-robust least squares (pdp_sysid_step_wls_batched, one launch; either keyword implies the packed dict, like
+        gauss_newton=True).  weights broadcast from [n], [T+1, n] (one block shared by the batch) or [B, T+1, n], finite and >= 0: w = 1 / sigma^2 per entry, 0 = not
+        observed (xobs may hold anything there).  huber_delta > 0 acts on the standardised residual e = sqrt(w) (x - xobs): rho = e^2 up to delta, 2 delta |e| - delta^2
+        beyond; loss = sum rho, grad its exact half derivative, gn the Gauss-Newton matrix of iteratively reweighted least squares (include/pdp_hip_sysid_wls.h).  They
+        combine with skip_missing, ini_state and estimate_ini; W > 16 or n > 16: the same row from scaled residuals and row-scaled materialised sensitivities."""
         idx, mask = ini_indices(estimate_ini, self.n)
+        if weights is not None or huber_delta is not None:
+            return self._sysid_step_wls(u, xobs, theta, skip_missing, ini_state, buffers, idx, mask, weights, huber_delta)
         if idx:                                     # (nothing selected is estimate_ini=None: today's calls and today's rows)
             return self._sysid_step_gn(u, xobs, theta, gauss_newton, skip_missing, ini_state, buffers, idx, mask)
         if gauss_newton or skip_missing or ini_state is not None:
@@ -1005,12 +1044,29 @@ class ModelLib:
         check(rc, "pdp_sysid_step_ws_batched")
         return loss, grad
 
+    def _sysid_materialised(self, u, xobs, th, x0, ini_index=()):
+        """(x [B, T+1, n], X [B, T+1, n, W]) from the size-generic kernels - sysid_integrate, sysid_auxsys, sysid_aux_integrate: the rollout from x0 (None: xobs[:, 0])
+        and its sensitivities with respect to theta and the components ini_index of x0 (X_0 = the selection matrix; W = p + len(ini_index)).  What the Gauss-Newton
+        entry points' rows are contracted from beyond the fused kernels' tile (PDP_E_SIZE).  Device tensors; th [1 or B, >= p]."""
+        torch = torch_cuda()
+        B, T, n, p = u.shape[0], u.shape[1], self.n, self.p
+        if th.shape[-1] != p:                       # (parameters read in place from wider rows: theta_b | x0_b[idx])
+            th = th[:, :p].contiguous()
+        x = self.sysid_integrate(x0 if x0 is not None else xobs[:, 0].contiguous(), u, th)
+        F, E = self.sysid_auxsys(x, u, th)
+        if not ini_index:
+            return x, sysid_aux_integrate(F, E)
+        W = p + len(ini_index)
+        Ew = torch.zeros((B, T, n, W), dtype=torch.float64, device="cuda")
+        Ew[..., :p] = E
+        X0 = torch.zeros((B, n, W), dtype=torch.float64, device="cuda")
+        for k, i in enumerate(ini_index):
+            X0[:, i, p + k] = 1.0
+        return x, sysid_aux_integrate(F, Ew, X0)
+
     def _sysid_step_gn(self, u, xobs, theta, gauss_newton, skip_missing, ini_state, buffers, ini_index=(), ini_mask=0):
-        if skip_missing:                            # judged on what the caller gave (a host array is not moved to the device first)
-            first = ini_state if ini_state is not None else (xobs if hasattr(xobs, "data_ptr") else np.asarray(xobs, dtype=float))[:, 0]
-            if bool(first.isnan().any()) if hasattr(first, "data_ptr") else bool(np.isnan(np.asarray(first, dtype=float)).any()):
-                raise ValueError("sysid_step: skip_missing=True and the initial state (%s) holds a NaN: give ini_state [B, n]"
-                                 % ("xobs[:, 0]" if ini_state is None else "ini_state"))
+        if skip_missing:
+            _refuse_nan_initial_state(xobs, ini_state)
         torch = torch_cuda()
         u, xobs = dev(u), dev(xobs)
         B, T, n, p = u.shape[0], u.shape[1], self.n, self.p
@@ -1031,9 +1087,7 @@ class ModelLib:
         rc = self.lib.pdp_sysid_step_gn_batched(B, T, ptr(u), ptr(xobs), ptr(x0), ptr(th), tb, 32 if skip_missing else 0, ptr(loss), ptr(packed), ptr(ws), nbytes,
                                                 current_stream_ptr())
         if rc == -2:                                # beyond the fused kernels' tiles: the same row from the materialised sensitivities
-            x = self.sysid_integrate(x0 if x0 is not None else xobs[:, 0].contiguous(), u, th)
-            F, E = self.sysid_auxsys(x, u, th)
-            X = sysid_aux_integrate(F, E)                                           # [B, T+1, n, p]
+            x, X = self._sysid_materialised(u, xobs, th, x0)                        # X [B, T+1, n, p]
             d = x - xobs
             if skip_missing:                        # selects, as in the kernels: an observed entry with a non-finite state keeps its NaN in the loss
                 zero = torch.zeros((), dtype=torch.float64, device="cuda")
@@ -1067,16 +1121,7 @@ class ModelLib:
         rc = self.lib.pdp_sysid_step_gn_ini_batched(B, T, ptr(u), ptr(xobs), ptr(x0), ini_mask, ptr(th), tb, 32 if skip_missing else 0, ptr(loss), ptr(packed), ptr(ws),
                                                     nbytes, current_stream_ptr())
         if rc == -2:                                # beyond the fused kernels' tile: the same row from the materialised sensitivities, started at the selection matrix
-            if th.shape[-1] != p:                   # (parameters read in place from wider rows: theta_b | x0_b[idx])
-                th = th[:, :p].contiguous()
-            x = self.sysid_integrate(x0 if x0 is not None else xobs[:, 0].contiguous(), u, th)
-            F, E = self.sysid_auxsys(x, u, th)
-            Ew = torch.zeros((B, T, n, W), dtype=torch.float64, device="cuda")
-            Ew[..., :p] = E
-            X0 = torch.zeros((B, n, W), dtype=torch.float64, device="cuda")
-            for k, i in enumerate(ini_index):
-                X0[:, i, p + k] = 1.0
-            X = sysid_aux_integrate(F, Ew, X0)                                      # [B, T+1, n, W]
+            x, X = self._sysid_materialised(u, xobs, th, x0, ini_index)             # X [B, T+1, n, W]
             d = x - xobs
             if skip_missing:                        # selects, as in the kernels: an observed entry with a non-finite state keeps its NaN in the loss
                 zero = torch.zeros((), dtype=torch.float64, device="cuda")
@@ -1092,6 +1137,57 @@ class ModelLib:
         if not gauss_newton:
             return packed[:, W], packed[:, :W]
         return dict(packed_gn=packed, loss=packed[:, W], grad=packed[:, :W], gn=packed[:, W + 1:].view(B, W, W), ini_index=ini_index)
+
+    def _sysid_step_wls(self, u, xobs, theta, skip_missing, ini_state, buffers, ini_index, ini_mask, weights, huber_delta):
+        """sysid_step with weights and / or Huber's loss: the arguments are checked and moved to the device here, the call is _sysid_step_wls_dev's"""
+        w, wbs, delta = wls_arguments(weights, huber_delta, int(u.shape[0]), int(u.shape[1]), self.n)
+        if skip_missing:
+            _refuse_nan_initial_state(xobs, ini_state)
+        u, xobs = dev(u), dev(xobs)
+        B = u.shape[0]
+        x0 = dev(ini_state).reshape(B, self.n).contiguous() if ini_state is not None else None
+        th, tb = self._theta(theta, B)
+        return self._sysid_step_wls_dev(u, xobs, th, tb, skip_missing, x0, buffers, ini_index, ini_mask, dev(w).contiguous() if w is not None else None, wbs, delta)
+
+    def _sysid_step_wls_dev(self, u, xobs, th, tb, skip_missing, x0, buffers, ini_index, ini_mask, wd, wbs, delta):
+        """pdp_sysid_step_wls_batched on device tensors and normalised arguments (wls_arguments: wd [T+1, n] or [B, T+1, n] or None, wbs its batch stride, delta a
+        float), no check and no host synchronisation: what the loops of irl.py call per evaluation.  th [1 or B, >= p] with row stride tb; always the packed dict over
+        W = p + q."""
+        torch = torch_cuda()
+        B, T, n, p = u.shape[0], u.shape[1], self.n, self.p
+        W = p + len(ini_index)
+        bufs = buffers if buffers is not None else {}
+
+        def buf(key, shape):
+            t = bufs.get(key)
+            if t is None or tuple(t.shape) != tuple(shape):
+                t = bufs[key] = torch.empty(shape, dtype=torch.float64, device="cuda")
+            return t
+        loss, packed = buf("loss", (B,)), buf("packed_gn_wls", (B, W + 1 + W * W))
+        ws, nbytes = self._sysid_workspace(B, T)
+        rc = self.lib.pdp_sysid_step_wls_batched(B, T, ptr(u), ptr(xobs), ptr(x0), ini_mask, ptr(wd), wbs, delta, ptr(th), tb, 32 if skip_missing else 0, ptr(loss),
+                                                 ptr(packed), ptr(ws), nbytes, current_stream_ptr())
+        if rc == -2:                                # beyond the fused kernels' tile: the same row from scaled residuals and row-scaled materialised sensitivities
+            x, X = self._sysid_materialised(u, xobs, th, x0, ini_index)             # X [B, T+1, n, W]
+            zero = torch.zeros((), dtype=torch.float64, device="cuda")
+            wf = (wd if wd is not None else torch.ones((), dtype=torch.float64, device="cuda")).expand(B, T + 1, n)
+            d = x - xobs
+            obs = (wf > 0) & (xobs == xobs) if skip_missing else wf > 0
+            e = wf.sqrt() * d
+            ae = e.abs()
+            quad = ae <= delta
+            s = torch.where(quad, wf, wf * (delta / ae)).sqrt()
+            packed[:, W] = torch.where(obs, torch.where(quad, e * e, 2.0 * delta * ae - delta * delta), zero).sum(dim=(1, 2))
+            sd = torch.where(obs, s * d, zero)                                      # selects, as in the kernels: never a product with 0
+            sX = torch.where((obs & (s != 0))[..., None], s[..., None] * X, zero)
+            packed[:, :W] = torch.einsum("bti,btip->bp", sd, sX)
+            packed[:, W + 1:] = torch.einsum("btip,btiq->bpq", sX, sX).reshape(B, W * W)
+            rc = 0
+        check(rc, "pdp_sysid_step_wls_batched")
+        out = dict(packed_gn=packed, loss=packed[:, W], grad=packed[:, :W], gn=packed[:, W + 1:].view(B, W, W))
+        if ini_index:
+            out["ini_index"] = list(ini_index)
+        return out
 
 
 def load_model(path):
