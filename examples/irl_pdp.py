@@ -23,6 +23,13 @@ Demonstrations with gaps (--method lm): --every K keeps the states at t = K, 2K,
 other entry becomes NaN = not observed (PDP_GRAD_SKIP_MISSING), and the solves start from the demonstrations' own first states:
 
     python examples/irl_pdp.py --system cartpole --method lm --every 10 --observe 0,1 --no-controls
+
+Noisy and corrupted demonstrations (--method lm): weighted and Huber-robust least squares (the weights_state= / weights_control= / huber_delta= keywords of the loops,
+pdp_oc_pdp_grad_wls_batched).  --noise-sigma s0,s1,... (one value per state component, then one per control component) adds Gaussian noise of that standard deviation
+to the demonstrations (states at t >= 1, every control) and weights every entry of a component by 1 / s_i^2; --outliers moves that fraction of the entries (states at
+t >= 1, every control) by +-(0.5 .. 1.5); --huber is Huber's threshold on the standardised residual sqrt(w) d, which keeps such entries from steering the fit:
+
+    python examples/irl_pdp.py --system cartpole --method lm --huber 0.01 --outliers 0.05
 """
 import argparse
 import os
@@ -72,9 +79,41 @@ def mask_demos(demo_x, demo_u, every=None, observe=None, no_controls=False):
     return mx, (np.full(demo_u.shape, np.nan) if no_controls else demo_u.copy())
 
 
+def disturb_demos(demo_x, demo_u, noise_sigma=None, outliers=0.0, seed=0):
+    """(demo_x, demo_u, weights_state or None, weights_control or None, number of outliers): Gaussian noise of standard deviation noise_sigma[i] on component i (n state
+    components, then m control components) with the weights 1 / s_i^2, and `outliers` of the entries moved by +-(0.5 .. 1.5).  Row 0 of the states stays as recorded:
+    the solves start there."""
+    n, m = demo_x.shape[2], demo_u.shape[2]
+    rng = np.random.default_rng(seed)
+    demo_x, demo_u, wx, wu, k = demo_x.copy(), demo_u.copy(), None, None, 0
+    if noise_sigma is not None:
+        sig = np.asarray(noise_sigma, dtype=float)
+        assert sig.shape == (n + m,) and (sig > 0).all(), "--noise-sigma: %d positive values, one per state component, then one per control component" % (n + m)
+        demo_x[:, 1:] += sig[:n] * rng.standard_normal(demo_x[:, 1:].shape)
+        demo_u += sig[n:] * rng.standard_normal(demo_u.shape)
+        wx, wu = 1.0 / sig[:n] ** 2, 1.0 / sig[n:] ** 2
+    if outliers > 0:
+        for a_, first in ((demo_x, 1), (demo_u, 0)):
+            hit = rng.random(a_.shape) < outliers
+            hit[:, :first] = False
+            a_[hit] += (rng.choice([-1.0, 1.0], a_.shape) * rng.uniform(0.5, 1.5, a_.shape))[hit]
+            k += int(hit.sum())
+    return demo_x, demo_u, wx, wu, k
+
+
 def run_lm(a, oc, demo_x, demo_u, theta, true_parameter):
     from pdp_amd.irl import LMLoop
     t0 = time.time()
+    wls = {}
+    if a.noise_sigma is not None or a.outliers > 0:
+        sig = None if a.noise_sigma is None else [float(v) for v in a.noise_sigma.split(",")]
+        demo_x, demo_u, wx, wu, k = disturb_demos(demo_x, demo_u, sig, a.outliers, a.seed)
+        if wx is not None:
+            wls.update(weights_state=wx, weights_control=wu)
+        if a.outliers > 0:
+            print("%d of %d demonstration entries are outliers" % (k, demo_x.size + demo_u.size))
+    if a.huber is not None:
+        wls["huber_delta"] = a.huber
     sparse = a.every is not None or a.observe is not None or a.no_controls
     if sparse:
         assert a.every is None or a.every >= 1, "--every: a positive number of steps"
@@ -84,9 +123,9 @@ def run_lm(a, oc, demo_x, demo_u, theta, true_parameter):
         demo_x, demo_u = mask_demos(demo_x, demo_u, a.every, observe, a.no_controls)
         print("observed: %d of %d state entries, %d of %d control entries per demonstration" % (
             int((~np.isnan(demo_x[0])).sum()), demo_x[0].size, int((~np.isnan(demo_u[0])).sum()), demo_u[0].size))
-        loop = LMLoop.for_irl(oc.model(), demo_x, demo_u, theta, ini_state=ini_state, skip_missing=True)
+        loop = LMLoop.for_irl(oc.model(), demo_x, demo_u, theta, ini_state=ini_state, skip_missing=True, **wls)
     else:
-        loop = LMLoop.for_irl(oc.model(), demo_x, demo_u, theta)
+        loop = LMLoop.for_irl(oc.model(), demo_x, demo_u, theta, **wls)
     r = loop.run(max_evals=a.iters, loss_tol=a.loss_tol)
     for k, (loss, th, lam) in enumerate(zip(r["loss_trace"], r["parameter_trace"], r["lambda_trace"])):
         print("accepted %3d  loss %.6e  |theta - theta*| %.4e  next damping %.1e" % (k, loss, np.abs(th - true_parameter).max(), lam))
@@ -123,8 +162,14 @@ def main():
     ap.add_argument("--every", type=int, default=None, help="--method lm: only the states at t = K, 2K, ... <= T are observed (default: every step)")
     ap.add_argument("--observe", default=None, help="--method lm: comma-separated state components that are observed (default: all)")
     ap.add_argument("--no-controls", action="store_true", help="--method lm: no control is observed")
+    ap.add_argument("--noise-sigma", default=None, help="--method lm: noise levels s0,s1,... added to the demonstrations, one per state component, then one per control "
+                                                        "component; the weights are 1 / s_i^2")
+    ap.add_argument("--huber", type=float, default=None, help="--method lm: Huber's threshold on the standardised residual")
+    ap.add_argument("--outliers", type=float, default=0.0, help="--method lm: this fraction of the demonstration entries is moved by +-(0.5 .. 1.5)")
     ap.add_argument("--demos", default=None, help="<name>_demos.mat in the reference's schema (default: the stored demos of --system)")
     a = ap.parse_args()
+    if (a.noise_sigma is not None or a.huber is not None or a.outliers > 0) and a.method != "lm":
+        ap.error("--noise-sigma / --huber / --outliers need --method lm")
 
     env, dt = zoo.make_env(a.system, "irl")
     oc = PDP.OCSys(a.system)

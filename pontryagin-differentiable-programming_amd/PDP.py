@@ -184,7 +184,8 @@ class OCSys(_CasadiFrontEnd):
         return self.model().oc_auxsys(state_traj, u, costate_traj, self._theta(auxvar_value, u.shape[0]))
 
     def pdp_grad_batch(self, control_traj, auxvar_value, demo_state, demo_control, ini_state=None, state_traj=None, costate_traj=None,
-                       want_sens=False, buffers=None, want_riccati=False, want_predict_record=False, want_gauss_newton=False, skip_missing=False):
+                       want_sens=False, buffers=None, want_riccati=False, want_predict_record=False, want_gauss_newton=False, skip_missing=False, weights_state=None,
+                       weights_control=None, huber_delta=None):
         """Fused forward + Riccati + PDP gradient for a batch (the body of the IRL drivers' demo loop,
         Examples/IRL/cartpole/cartpole_PDP.py:45-74): returns dict(loss [B], grad [B,p], x, lam, status[, dxdp, dudp][, riccati]).
         want_predict_record (or want_sens + want_riccati, the same in fp64): everything the next OC solve's predicted start needs
@@ -192,7 +193,16 @@ class OCSys(_CasadiFrontEnd):
         want_gauss_newton (plain gradient only): also out["gn"] [B,p,p], the Gauss-Newton matrix J'J of the sum-of-squares loss, and out["packed_gn"] [B, p+1+p*p] =
         gradient | loss | G, the row irl.LMLoop and parallel.mean_loss_grad_gn reduce (PDP_GRAD_GAUSS_NEWTON, include/pdp_hip.h).
         skip_missing (with the plain gradient or want_gauss_newton): a NaN in demo_state / demo_control is an entry that was not observed and is left out of loss,
-        gradient and G (PDP_GRAD_SKIP_MISSING); demo_state[:, 0] may be all NaN when ini_state is given."""
+        gradient and G (PDP_GRAD_SKIP_MISSING); demo_state[:, 0] may be all NaN when ini_state is given.
+        weights_state ([n], [T+1, n] or [B, T+1, n]), weights_control ([m], [T, m] or [B, T, m]), huber_delta (> 0): a weight per demonstration entry (>= 0, 0 = not
+        observed, 1 / sigma^2 the usual choice) and Huber's loss on the standardised residual (include/pdp_hip_oc_wls.h).  Any of the three implies the packed
+        Gauss-Newton dict of the weighted / robust loss; not together with want_sens, want_riccati or want_predict_record (ValueError)."""
+        if weights_state is not None or weights_control is not None or huber_delta is not None:
+            for name, on in (("want_sens", want_sens), ("want_riccati", want_riccati), ("want_predict_record", want_predict_record)):
+                if on:
+                    raise ValueError("pdp_grad_batch: weights_state, weights_control and huber_delta give the packed Gauss-Newton row only - not together with %s" % name)
+            runtime.oc_wls_arguments(weights_state, weights_control, huber_delta, int(np.shape(control_traj)[0]), int(np.shape(control_traj)[1]), self.n_state,
+                                     self.n_control)
         if skip_missing and (want_sens or want_riccati or want_predict_record):
             raise ValueError("pdp_grad_batch: skip_missing goes with the plain gradient or want_gauss_newton only")
         if want_gauss_newton and (want_sens or want_riccati or want_predict_record):
@@ -200,7 +210,8 @@ class OCSys(_CasadiFrontEnd):
         u = runtime.dev(control_traj)
         return self.model().oc_pdp_grad(u, self._theta(auxvar_value, u.shape[0]), demo_state, demo_control, x0=ini_state, x=state_traj,
                                         lam=costate_traj, want_sens=want_sens, buffers=buffers, want_riccati=want_riccati, want_predict_record=want_predict_record,
-                                        gauss_newton=want_gauss_newton, skip_missing=skip_missing)
+                                        gauss_newton=want_gauss_newton, skip_missing=skip_missing, weights_x=weights_state, weights_u=weights_control,
+                                        huber_delta=huber_delta)
 
     def pdp_vjp_batch(self, control_traj, auxvar_value, grad_state, grad_control, ini_state=None, state_traj=None, costate_traj=None, buffers=None):
         """The gradient of ANY scalar loss L(state, control) through the OC solution, for a batch: grad_state [B,T+1,n] = dL/dstate and grad_control [B,T,m] = dL/dcontrol

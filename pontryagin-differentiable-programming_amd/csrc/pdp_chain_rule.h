@@ -43,6 +43,12 @@
 //                    and adds rho(e) to the loss (wls_slot: the division and the two square roots happen there, once per entry, lane-parallel); the sensitivity loop
 //                    gathers the tile S beside DX and scales the rows of X_t by a guarded product (wls_scale: S != 0 ? S X : 0.0 - 0 inf cannot appear) before it
 //                    contracts.  Both operands of every G product are the same scaled tile.  The recursion itself is never scaled.  The pool row is NX words longer.
+//   PDP_FUSED_GN_W   the same on the two OC units (include/pdp_hip_oc_wls.h): always Gauss-Newton, weights on states AND controls.  The kernels' trailing pack holds one
+//                    OcWls - the OC twin of SysidWls, split into one SysidWls per side (oc_wls_x, oc_wls_u) for wls_slot.  The lane-per-step pass leaves s d in the
+//                    DLX / DLU slots and s in a SECOND group of NX + NU slots of the same forward pool row; the sensitivity loop gathers the tiles SX, SU beside DX, DU,
+//                    forms Xm = wls_scale(SX, X_t), Um = wls_scale(SU, U_t) (register 0) and then does what the MISS arm does with them.  The terminal row goes through
+//                    dlT, followed by NX more words for its s.  The forward row is NX + NU words longer and dlT NX words - in this mode only (the extra-words argument
+//                    of the layouts); the Riccati recursion, the forward sweep and tile_finite see the unscaled tiles.
 #pragma once
 #include "pdp_tile.h"
 
@@ -52,6 +58,7 @@
 #define PDP_FUSED_GN 3
 #define PDP_FUSED_MISS 4
 #define PDP_FUSED_GN_MISS 5
+#define PDP_FUSED_GN_W 6
 
 #define PDP_SYSID_PLAIN 0
 #define PDP_SYSID_GN 1
@@ -69,9 +76,11 @@ enum Residual { RES_PLAIN, RES_MISS, RES_MISS_DIFF };
 
 template <int MODE>
 struct FusedMode {
-    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT || MODE == PDP_FUSED_GN || MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS,
+    static_assert(MODE == PDP_FUSED_PLAIN || MODE == PDP_FUSED_RIC || MODE == PDP_FUSED_COT || MODE == PDP_FUSED_GN || MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS ||
+                      MODE == PDP_FUSED_GN_W,
                   "instantiation");
-    static constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT, GN = MODE == PDP_FUSED_GN || MODE == PDP_FUSED_GN_MISS;
+    static constexpr bool RIC = MODE == PDP_FUSED_RIC, COT = MODE == PDP_FUSED_COT, WLS = MODE == PDP_FUSED_GN_W;      // (WLS: its own observed-rule, never together with MISS)
+    static constexpr bool GN = MODE == PDP_FUSED_GN || MODE == PDP_FUSED_GN_MISS || WLS;
     static constexpr bool MISS = MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS;
     static constexpr Residual RES = MISS ? RES_MISS : RES_PLAIN;          // (COT forms no residual: the cotangent takes the slot as it is)
 };
@@ -203,5 +212,19 @@ PDP_DEV d4 wls_scale(const d4 S, const d4 X) {
     for (int r = 0; r < 4; ++r) Xm[r] = S[r] != 0.0 ? S[r] * X[r] : 0.0;
     return Xm;
 }
+
+
+// ---- PDP_FUSED_GN_W: the run-time arguments of the OC units' weighted mode, one struct at the end of the kernels' argument list.  Neither pointer is ever NULL: without
+// weights the host passes demo_x / demo_u (readable blocks of the same shape) and clears the bit of has_w, and the pass selects 1.0.
+struct OcWls {
+    const double* wx;           // [B or 1][T+1][NX]
+    const double* wu;           // [B or 1][T][NU]
+    long long bsx, bsu;         // (T+1) NX / T NU, or 0: one block shared by the batch
+    double delta;               // Huber's threshold on the standardised residual; +inf: off
+    int has_w, skip;            // bit 0: weights_x given, bit 1: weights_u given; PDP_GRAD_SKIP_MISSING
+};
+PDP_DEV SysidWls oc_wls_x(const OcWls a) { return SysidWls{a.wx, a.bsx, a.delta, a.has_w & 1, a.skip}; }
+PDP_DEV SysidWls oc_wls_u(const OcWls a) { return SysidWls{a.wu, a.bsu, a.delta, (a.has_w >> 1) & 1, a.skip}; }
+PDP_DEV OcWls oc_wls(const OcWls a) { return a; }              // the one element of the kernels' trailing pack
 
 }  // namespace pdp

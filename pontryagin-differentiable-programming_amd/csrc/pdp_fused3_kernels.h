@@ -35,7 +35,8 @@ namespace pdp {
 __device__ long long g_rb_stamp[16];      // cycle stamps inside the last backward step of trajectory 0 (PDP_RB_T in pdp_riccati.h)
 #endif
 
-template <class Mdl>
+// XW: extra words of a forward row behind the residual slots (PDP_FUSED_GN_W: the NX + NU scales s); with them dlT is NX words longer.  0: every other mode.
+template <class Mdl, int XW = 0>
 struct Fused3Layout {
     using L = FusedLayout<Mdl>;
     static constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP;
@@ -48,13 +49,13 @@ struct Fused3Layout {
     static constexpr int NA = Mdl::PATHA_NVAR, NB = Mdl::PATHB_NVAR > 16 ? Mdl::PATHB_NVAR : 16;      // (16: the costate tile's column 0 is stored whole)
     static constexpr int CB0 = NA + NB;                                          // slot of the row's 0.0; the constants follow
     static constexpr int BSTRIDE = (CB0 + NCB) | 1;
-    static constexpr int CF0 = Mdl::FWD_NVAR + NX + NU;                          // forward row: [fwd | x - x_demo | u - u_demo | 0.0 | constants]
+    static constexpr int CF0 = Mdl::FWD_NVAR + NX + NU + XW;                     // forward row: [fwd | x - x_demo | u - u_demo | (XW scales) | 0.0 | constants]
     static constexpr int FSTRIDE = (CF0 + NCF) | 1;
     // offsets (doubles) inside a trajectory's slice
     static constexpr int FIN = RICCATI_SCRATCH;                 // [0.0 | terminal constants | terminal entries]   (behind the Riccati scratch; runner only)
     static constexpr int PAR = FIN + NCFIN + Mdl::FIN_NVAR;      // theta (NP) | theta-only precomputed values (NPC)
     static constexpr int DLT = PAR + NP + Mdl::NPC;              // NX: lambda_T staging (evaluator, start) / x_T - xdemo_T (runner, end)
-    static constexpr int MISC = DLT + NX;                        // 8 doubles: ints 0..7 = counters | [4] evaluator's loss sum | [5] dead slot
+    static constexpr int MISC = DLT + NX + (XW ? NX : 0);        // 8 doubles: ints 0..7 = counters | [4] evaluator's loss sum | [5] dead slot
     static constexpr int POOL = MISC + 8;                        // two buffers of BUF doubles
     static constexpr int SLICE = 160 * 1024 / 8 / 4;
     static constexpr int BUF = (SLICE - POOL) / 2;
@@ -63,9 +64,9 @@ struct Fused3Layout {
 };
 
 // the kernel applies when the rollout staging fits the pool area and a chunk holds a useful number of steps
-template <class Mdl>
+template <class Mdl, int XW = 0>
 __host__ __device__ constexpr bool fused3_ok(int T) {
-    using F3 = Fused3Layout<Mdl>;
+    using F3 = Fused3Layout<Mdl, XW>;
     return Mdl::NX > 4 && F3::ROWS >= 4 && F3::ROWSF >= 4 && (T + 1) * Mdl::NX + T * Mdl::NU <= 2 * F3::BUF;
 }
 
@@ -91,14 +92,17 @@ PDP_DEV BufMap f3_store_map(int R, int C, int ld, int coff, int lane) {
 // buffer stores (an output that is NULL is a resource of size 0).  A template parameter, not a run-time branch: the default kernel keeps its instruction stream.
 // MODE: one of PDP_FUSED_* (pdp_chain_rule.h describes the modes and holds what they change).  Here the evaluator fills the residual slots and owns the loss sum over
 // t < T (handed over in misc[4]; PDP_FUSED_COT: no lsum, no hand-over); the runner contracts, and takes the terminal row through dT / dlT.
-template <class Mdl, int TPW = 4, int MODE = PDP_FUSED_PLAIN>
+// Wls: empty, or - PDP_FUSED_GN_W - one OcWls (pdp_chain_rule.h) at the end of the argument list.
+template <class Mdl, int TPW = 4, int MODE = PDP_FUSED_PLAIN, class... Wls>
 __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, int flags, const double* __restrict__ x0, const double* __restrict__ u,
                                                             const double* __restrict__ theta, int tb, const double* __restrict__ demo_x,
                                                             const double* __restrict__ demo_u, double* __restrict__ x, double* __restrict__ lam,
                                                             double* __restrict__ loss, double* __restrict__ grad, double* __restrict__ dxdp,
                                                             double* __restrict__ dudp, int32_t* __restrict__ status, double* __restrict__ ws_gain,
-                                                            double* __restrict__ riccati, float* __restrict__ prec) {
-    using F3 = Fused3Layout<Mdl>;
+                                                            double* __restrict__ riccati, float* __restrict__ prec, Wls... wls) {
+    using FM = FusedMode<MODE>;
+    static_assert(sizeof...(Wls) == (FM::WLS ? 1 : 0), "instantiation");
+    using F3 = Fused3Layout<Mdl, FM::WLS ? Mdl::NX + Mdl::NU : 0>;
     constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP, M = NU;
     constexpr int GSZ = fused_gain_doubles<Mdl>(), GSZ0 = fused_gain0_doubles<Mdl>();
     constexpr int BS = F3::BSTRIDE, FS = F3::FSTRIDE;
@@ -107,7 +111,6 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
     // the wave index is uniform over the wave - said explicitly, or every pointer derived from it (trajectory, workspace, LDS slice) would be
     // carried per lane and every global access would pay 64-bit VALU address arithmetic
     static_assert(TPW == 1 || TPW == 2 || TPW == 4, "trajectories per workgroup");
-    using FM = FusedMode<MODE>;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, slot = wid & (TPW - 1);
     const bool runner = wid < TPW;
     const int b = blockIdx.x * TPW + slot;
@@ -133,6 +136,8 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
     const double* ub = u + (int64_t)b * T * NU;
     const double* dxb = demo_x + (int64_t)b * (T + 1) * NX;
     const double* dub = demo_u + (int64_t)b * T * NU;
+    [[maybe_unused]] const double *wxb = nullptr, *wub = nullptr;      // WLS: this trajectory's weights
+    if constexpr (FM::WLS) { wxb = oc_wls(wls...).wx + (int64_t)b * oc_wls(wls...).bsx; wub = oc_wls(wls...).wu + (int64_t)b * oc_wls(wls...).bsu; }
     double* gw = ws_gain + (int64_t)b * T * GSZ;
     const bool given = (flags & PDP_OC_GIVEN_TRAJ) != 0;
     // backward chunks, last time steps first, of equal length.  (A short first chunk - the runner idles until the first chunk is ready - was
@@ -353,14 +358,22 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         // folded into the lane predicate, in this kernel's own text (through residual_value the cotangent and skip-missing instantiations compiled differently)
         double dT;
         [[maybe_unused]] bool obsT = true;                      // MISS: the terminal entry of this lane was observed (the demonstration's entry is not NaN)
-        if constexpr (FM::COT) dT = lane < NX ? dxb[T * NX + lane] : 0.0;
+        [[maybe_unused]] double sT = 0.0, rhoT = 0.0;           // WLS: the terminal entry's scale and its share of the loss (dT: s d)
+        if constexpr (FM::WLS) { const int li = lane < NX ? lane : 0; wls_slot(dT, sT, xb[T * NX + li], dxb[T * NX + li], wxb[T * NX + li], oc_wls_x(oc_wls(wls...)), rhoT); }
+        else if constexpr (FM::COT) dT = lane < NX ? dxb[T * NX + lane] : 0.0;
         else if constexpr (FM::MISS) { const double dd = lane < NX ? dxb[T * NX + lane] : 0.0; obsT = dd == dd; dT = lane < NX ? (obsT ? xb[T * NX + lane] - dd : dd) : 0.0; }
         else dT = lane < NX ? xb[T * NX + lane] - dxb[T * NX + lane] : 0.0;
         d4 X2 = z;
         [[maybe_unused]] d4 Gn = z;                             // GN: sum_t X_t' X_t + U_t' U_t
         {
             constexpr int DLX = Mdl::FWD_NVAR, DLU = Mdl::FWD_NVAR + NX;      // pool slots of x - x_demo, u - u_demo
+            [[maybe_unused]] constexpr int DSX = DLU + NU, DSU = DSX + NX;    // WLS: pool slots of the scales s of the state / control rows
             RowGather gFT, gGT, gE, gDX, gDU;
+            [[maybe_unused]] RowGather gSX, gSU;
+            if constexpr (FM::WLS) {
+                make_row_gather(gSX, lane, F3::CF0, [](int r, int c) { return (r < NX) ? DSX + r : -1; });
+                make_row_gather(gSU, lane, F3::CF0, [](int r, int c) { return (r < M) ? DSU + r : -1; });
+            }
             make_row_gather(gFT, lane, F3::CF0, [](int r, int c) { return (r < NX && c < NX) ? Mdl::fwd_code(0, c * NX + r) : -1; });
             make_row_gather(gGT, lane, F3::CF0, [](int r, int c) { return (r < M && c < NX) ? Mdl::fwd_code(1, c * NU + r) : -1; });
             make_row_gather(gE, lane, F3::CF0, [](int r, int c) { return (r < NX && c >= M && c < M + NP) ? Mdl::fwd_code(2, r * NP + (c - M)) : -1; });
@@ -399,7 +412,12 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                 wg_wait_ge(fl + 2, g + 1);
                 F3_W1();
                 RowRun rFT = row_run_at(gFT, pb), rGT = row_run_at(gGT, pb), rE = row_run_at(gE, pb), rDX = row_run_at(gDX, pb), rDU = row_run_at(gDU, pb);
-                auto move_all = [&](int bytes) { row_move(rFT, bytes); row_move<1>(rGT, bytes); row_move(rE, bytes); row_move(rDX, bytes); row_move<1>(rDU, bytes); };
+                [[maybe_unused]] RowRun rSX, rSU;
+                if constexpr (FM::WLS) { rSX = row_run_at(gSX, pb); rSU = row_run_at(gSU, pb); }
+                auto move_all = [&](int bytes) {
+                    row_move(rFT, bytes); row_move<1>(rGT, bytes); row_move(rE, bytes); row_move(rDX, bytes); row_move<1>(rDU, bytes);
+                    if constexpr (FM::WLS) { row_move(rSX, bytes); row_move<1>(rSU, bytes); }
+                };
                 auto fstep = [&](int tl, unsigned imm, const d4 Xc, d4& Xn, const d4 KTc, const d4 kc, d4& KTnx, d4& knx) {
                     const int t = t0 + tl, tnx = (t + PDP_F3_GAIN_AHEAD < T) ? t + PDP_F3_GAIN_AHEAD : T - 1;
                     KTnx = -load_all<4>(gw + tnx * GSZ, mKT);
@@ -412,6 +430,11 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                     d4 U2;
                     riccati_forward(KTc, kc, FT, GT, E2, Xc, U2, Xn);
                     d4 Xm = Xc, Um = U2;
+                    if constexpr (FM::WLS) {          // DX, DU carry s d; the rows of X_t, U_t scaled by the same s (U_t: register 0)
+                        const d4 SX = row_read(rSX, imm), SU = row_read<1>(rSU, imm);
+                        Xm = wls_scale(SX, Xc);
+                        Um = zero4(); Um[0] = wls_scale(SU, U2)[0];
+                    } else
                     mask_step<FM::MISS, 4>(DX, DU, Xc, U2, Xm, Um);
                     if constexpr (FM::GN) Gn = gram_step<false>(Xm, Um, Gn);
                     acc += contract_step(DX, DU, Xm, Um);
@@ -469,16 +492,22 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         wave_lds_sync();
         if (lane < NX) {
             dlT[lane] = dT;
-            if constexpr (FM::MISS) lsum += obsT ? dT * dT : 0.0;
+            if constexpr (FM::WLS) { dlT[NX + lane] = sT; lsum += rhoT; }
+            else if constexpr (FM::MISS) lsum += obsT ? dT * dT : 0.0;
             else if constexpr (!FM::COT) lsum += dT * dT;
         }
         wave_lds_sync();
         [[maybe_unused]] d4 X2m = z;                            // MISS: X_T with the rows that were not observed selected away
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { const int row = tile_row(lane, r); if (row < NX) { const double d = dlT[row]; X2m[r] = observed<FM::MISS>(d, X2[r]); acc += observed<FM::MISS>(d, d) * X2m[r]; } }
+        for (int r = 0; r < 4; ++r) {
+            const int row = tile_row(lane, r);
+            if constexpr (FM::WLS) { if (row < NX) { const double s = dlT[NX + row]; X2m[r] = s != 0.0 ? s * X2[r] : 0.0; acc += dlT[row] * X2m[r]; } }
+            else
+            if (row < NX) { const double d = dlT[row]; X2m[r] = observed<FM::MISS>(d, X2[r]); acc += observed<FM::MISS>(d, d) * X2m[r]; }
+        }
         if (dxdp) store_dense(dxdp + ((int64_t)b * (T + 1) + T) * NX * NP, NX, NP, NP, 0, M, lane, X2);
         finite = finite && tile_finite(X2);
-        if constexpr (FM::GN) Gn = gram_add<false>(FM::MISS ? X2m : X2, Gn);      // X_T
+        if constexpr (FM::GN) Gn = gram_add<false>(FM::MISS || FM::WLS ? X2m : X2, Gn);      // X_T
         acc = sum_over_rowgroups(acc);
         if constexpr (FM::COT) {                                // no loss, no packed row (PDP_E_ARG at the entry point), nothing to wait for: every chunk has been consumed
             if (lane >= M && lane < M + NP) grad[(int64_t)b * NP + (lane - M)] = acc;
@@ -630,6 +659,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
         [[maybe_unused]] double lsum = 0.0;
         {
             constexpr int DLX = Mdl::FWD_NVAR, DLU = Mdl::FWD_NVAR + NX;
+            [[maybe_unused]] constexpr int DSX = DLU + NU, DSU = DSX + NX;
             for (int c = 0; c < nchunkF; ++c) {
                 const int g = nchunk + c, t0 = c * chF, cnt = min(chF, T - t0), bo = (g & 1) * F3::BUF;
                 F3_W0();
@@ -644,12 +674,14 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                     for (int i = 0; i < NX; ++i) {
                         xc[i] = xb[t * NX + i];
                         if constexpr (FM::COT) row[DLX + i] = t > 0 ? dxb[t * NX + i] : 0.0;       // the cotangent takes the slot as it is; gx_0 multiplies X_0 = 0: not loaded
+                        else if constexpr (FM::WLS) wls_slot(row[DLX + i], row[DSX + i], xc[i], dxb[t * NX + i], wxb[t * NX + i], oc_wls_x(oc_wls(wls...)), lsum);
                         else residual_slot<FM::RES>(row[DLX + i], xc[i], dxb[t * NX + i], lsum);
                     }
 #pragma unroll
                     for (int i = 0; i < NU; ++i) {
                         uc[i] = ub[t * NU + i];
                         if constexpr (FM::COT) row[DLU + i] = dub[t * NU + i];
+                        else if constexpr (FM::WLS) wls_slot(row[DLU + i], row[DSU + i], uc[i], dub[t * NU + i], wub[t * NU + i], oc_wls_u(oc_wls(wls...)), lsum);
                         else residual_slot<FM::RES>(row[DLU + i], uc[i], dub[t * NU + i], lsum);
                     }
                     PackedSink s{row};

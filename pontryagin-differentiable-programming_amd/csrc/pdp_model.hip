@@ -6,6 +6,7 @@
 #include "../../include/pdp_hip_sysid_gn.h"
 #include "../../include/pdp_hip_sysid_ini.h"
 #include "../../include/pdp_hip_sysid_wls.h"
+#include "../../include/pdp_hip_oc_wls.h"
 #ifndef PDP_MODEL_HEADER
 #error "compile with -DPDP_MODEL_HEADER=\"generated/<model>.h\""
 #endif
@@ -142,6 +143,46 @@ int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const dou
             }
         }
         return with_fused_mode(mode(records), [&](auto MODE) { return run(oc_pdp_fused_kernel<Mdl, MODE()>, B, 64, lds); });
+    } else { return Mdl::KIND == PDP_KIND_OC ? PDP_E_SIZE : PDP_E_MODE; }
+}
+
+// pdp_oc_pdp_grad_wls_batched (include/pdp_hip_oc_wls.h): the PDP_FUSED_GN_W instantiations, chosen as oc_pdp chooses - same variant, PDP_FUSED_TPW and fused3_ok logic,
+// the last two evaluated with the mode's own (longer) layout.  The checks come in the order of the header.
+template <class Mdl>
+int oc_pdp_wls(int B, int T, int flags, const double* x0, const double* u, const double* th, int tb, const double* dx, const double* du, const double* wx, int64_t wxs,
+               const double* wu, int64_t wus, double delta, double* x, double* lam, double* loss, double* packed, int32_t* status, void* ws, int64_t wsb, void* st) {
+    if constexpr (fused_oc_ok<Mdl>()) {
+        constexpr int XW = Mdl::NX + Mdl::NU;                // the forward row's extra words
+        if (flags & ~(PDP_OC_GIVEN_TRAJ | PDP_GRAD_SKIP_MISSING)) return PDP_E_ARG;
+        if (!(delta > 0.0)) return PDP_E_ARG;                // (<= 0 and NaN)
+        if (wxs != 0 && wxs != (int64_t)(T + 1) * Mdl::NX) return PDP_E_ARG;
+        if (wus != 0 && wus != (int64_t)T * Mdl::NU) return PDP_E_ARG;
+        if (!u || !th || !dx || !du || !x || !lam || !loss || !packed || !status || !ws) return PDP_E_ARG;
+        if (!(flags & PDP_OC_GIVEN_TRAJ) && !x0) return PDP_E_ARG;
+        if (B <= 0 || T <= 0) return PDP_E_ARG;
+        if (wsb < oc_ws_bytes<Mdl>(B, T)) return PDP_E_ARG;
+        const size_t lds = fused_lds_bytes<Mdl, XW>(T);
+        if (lds > 160 * 1024) return PDP_E_SIZE;
+        // without weights the kernels load the demonstrations in their place (readable blocks of the same shape) and select 1.0
+        const OcWls a{wx ? wx : dx, wu ? wu : du, wx ? (long long)wxs : (long long)(T + 1) * Mdl::NX, wu ? (long long)wus : (long long)T * Mdl::NU, delta,
+                      (wx ? 1 : 0) | (wu ? 2 : 0), (flags & PDP_GRAD_SKIP_MISSING) ? 1 : 0};
+        double* const no_sens = nullptr;
+        float* const no_rec = nullptr;
+        auto run = [&](auto kern, int wgs, int threads, size_t lds_bytes) {
+            return launch(kern, dim3(wgs), dim3(threads), lds_bytes, S(st), B, T, flags, x0, u, th, tb, dx, du, x, lam, loss, packed, no_sens, no_sens, status, (double*)ws,
+                          no_sens, no_rec, a);
+        };
+        static const int variant = env_int("PDP_FUSED_VARIANT", PDP_FUSED_DEFAULT_VARIANT);
+        if constexpr (Mdl::NX > 4) {
+            if (variant == 3 && fused3_ok<Mdl, XW>(T)) {
+                static const int tpw_env = env_int("PDP_FUSED_TPW", 0);          // (overrides the batch rule)
+                const int tpw = tpw_env ? tpw_env : traj_per_workgroup(B, device_cu_count(), 4);
+                return with_int<1, 2, 4>(tpw, [&](auto K) {
+                    return run(oc_pdp_fused3_kernel<Mdl, K(), PDP_FUSED_GN_W, OcWls>, (B + K() - 1) / K(), 128 * K(), K() * 40 * 1024);
+                });
+            }
+        }
+        return run(oc_pdp_fused_kernel<Mdl, PDP_FUSED_GN_W, OcWls>, B, 64, lds);
     } else { return Mdl::KIND == PDP_KIND_OC ? PDP_E_SIZE : PDP_E_MODE; }
 }
 
@@ -759,6 +800,13 @@ int pdp_sysid_step_wls_batched(int B, int T, const double* u, const double* x_ob
                        (flags & PDP_GRAD_SKIP_MISSING) ? 1 : 0};
     return mask ? sysid_step<PdpModel, PDP_SYSID_GN_W_INI>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0, mask, wls)
                 : sysid_step<PdpModel, PDP_SYSID_GN_W>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0, 0u, wls);
+}
+int pdp_oc_pdp_grad_wls_batched(int B, int T, int flags, const double* x0, const double* u, const double* theta, int theta_bstride, const double* demo_x,
+                                const double* demo_u, const double* weights_x, int64_t weights_x_bstride, const double* weights_u, int64_t weights_u_bstride,
+                                double huber_delta, double* x, double* lam, double* loss, double* packed, int32_t* status, void* workspace, int64_t workspace_bytes,
+                                void* stream) {
+    return oc_pdp_wls<PdpModel>(B, T, flags, x0, u, theta, theta_bstride, demo_x, demo_u, weights_x, weights_x_bstride, weights_u, weights_u_bstride, huber_delta, x, lam,
+                                loss, packed, status, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

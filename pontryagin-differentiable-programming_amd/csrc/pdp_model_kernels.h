@@ -546,7 +546,8 @@ template <class Mdl> struct FusedChunk { static constexpr int value = Mdl::CHUNK
 #define PDP_FUSED_OCCUPANCY
 #endif
 
-template <class Mdl>
+// XW: extra words of a forward row behind the residual slots (PDP_FUSED_GN_W: the NX + NU scales s); with them dlT is NX words longer.  0: every other mode.
+template <class Mdl, int XW = 0>
 struct FusedLayout {
     static constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP, CH = FusedChunk<Mdl>::value;
     static constexpr int NCB = Mdl::PATHA_NCONST + Mdl::PATHB_NCONST;          // constants of the two backward groups, A first
@@ -555,32 +556,36 @@ struct FusedLayout {
     static constexpr int NA = Mdl::PATHA_NVAR, NB = Mdl::PATHB_NVAR;           // backward pool row: [patha | pathb | lambda_{t+1} (NX)]
     static constexpr int LAM = NA + NB;
     static constexpr int BSTRIDE = (NA + NB + NX) | 1;                         // odd -> conflict-free
-    static constexpr int FEXTRA = NX + NU;                                      // x - x_demo, u - u_demo per step
+    static constexpr int FEXTRA = NX + NU + XW;                                 // x - x_demo, u - u_demo per step (and the XW scales)
+    static constexpr int TEXTRA = XW ? NX : 0;                                  // words of dlT behind its NX
     static constexpr int FSTRIDE = (Mdl::FWD_NVAR + FEXTRA) | 1;
     static constexpr int POOL = CH * (BSTRIDE > FSTRIDE ? BSTRIDE : FSTRIDE) > Mdl::FIN_NVAR + 1 ? CH * (BSTRIDE > FSTRIDE ? BSTRIDE : FSTRIDE) : Mdl::FIN_NVAR + 1;
 };
 
 // pool size in doubles: the aux-matrix pool, or the x/u staging of the rollout phase, whichever is larger
-template <class Mdl>
+template <class Mdl, int XW = 0>
 __host__ __device__ inline int fused_pool_doubles(int T) {
     const int stage = (T + 1) * Mdl::NX + T * Mdl::NU;
-    return FusedLayout<Mdl>::POOL > stage ? FusedLayout<Mdl>::POOL : stage;
+    return FusedLayout<Mdl, XW>::POOL > stage ? FusedLayout<Mdl, XW>::POOL : stage;
 }
-template <class Mdl>
+template <class Mdl, int XW = 0>
 __host__ __device__ inline size_t fused_lds_bytes(int T) {
-    return sizeof(double) * (size_t)(RICCATI_SCRATCH + FusedLayout<Mdl>::NC + fused_pool_doubles<Mdl>(T) + Mdl::NX + Mdl::NP + Mdl::NPC + 8);
+    return sizeof(double) * (size_t)(RICCATI_SCRATCH + FusedLayout<Mdl, XW>::NC + fused_pool_doubles<Mdl, XW>(T) + Mdl::NX + FusedLayout<Mdl, XW>::TEXTRA + Mdl::NP + Mdl::NPC + 8);
 }
 
 // MODE: one of PDP_FUSED_* - a template parameter, never a run-time branch (pdp_chain_rule.h describes the modes and holds what they change)
-template <class Mdl, int MODE = PDP_FUSED_PLAIN>
+// Wls: empty, or - PDP_FUSED_GN_W - one OcWls (pdp_chain_rule.h) at the end of the argument list.
+template <class Mdl, int MODE = PDP_FUSED_PLAIN, class... Wls>
 __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(int B, int T, int flags, const double* __restrict__ x0, const double* __restrict__ u,
                                                            const double* __restrict__ theta, int tb, const double* __restrict__ demo_x,
                                                            const double* __restrict__ demo_u, double* __restrict__ x, double* __restrict__ lam,
                                                            double* __restrict__ loss, double* __restrict__ grad, double* __restrict__ dxdp,
                                                            double* __restrict__ dudp, int32_t* __restrict__ status, double* __restrict__ ws_gain,
-                                                           double* __restrict__ riccati, float* __restrict__ prec) {
-    using L = FusedLayout<Mdl>;
+                                                           double* __restrict__ riccati, float* __restrict__ prec, Wls... wls) {
     using FM = FusedMode<MODE>;
+    static_assert(sizeof...(Wls) == (FM::WLS ? 1 : 0), "instantiation");
+    constexpr int XW = FM::WLS ? Mdl::NX + Mdl::NU : 0;
+    using L = FusedLayout<Mdl, XW>;
     constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP, CH = L::CH, M = NU;
     constexpr int GSZ = fused_gain_doubles<Mdl>();         // per step: K [NU x NX] | k [NU x NP] | zero sink
     // SMALL (n <= 4: pendulum, cart-pole, robot arm): every matrix of the recursion fits the rows-0..3 register of its tile and every
@@ -593,13 +598,13 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
     double* scratch = lds;                              // RICCATI_SCRATCH
     double* blk = lds + RICCATI_SCRATCH;                // [cpool (NC) | pool]
     double* pool = blk + L::NC;
-    double* dlT = pool + fused_pool_doubles<Mdl>(T);    // x_T - xdemo_T (NX)
+    double* dlT = pool + fused_pool_doubles<Mdl, XW>(T);    // x_T - xdemo_T (NX; WLS: and the NX scales of the terminal row behind them)
     const int b = blockIdx.x, lane = threadIdx.x;
     const int tlane = small_transpose_lane(lane);
     const d4 z = zero4();
     // theta and the theta-only precomputed values are parked in LDS and re-read inside every block of generated scalar code:
     // kept in registers they would occupy 2 (NP + NPC) VGPRs for the whole kernel, which sits at the 256-VGPR ceiling
-    double* par = dlT + NX;                             // [theta (NP) | pc (NPC)]
+    double* par = dlT + NX + L::TEXTRA;                 // [theta (NP) | pc (NPC)]
     {
         double th0[NP], pc0[Mdl::NPC];
         load_theta<Mdl>(theta, b, tb, th0);
@@ -900,7 +905,13 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
         wave_lds_sync();
         for (int i_ = lane; i_ < Mdl::FWD_NCONST; i_ += 64) blk[1 + i_] = Mdl::fwd_const(i_);
         constexpr int DLX = Mdl::FWD_NVAR, DLU = Mdl::FWD_NVAR + NX;      // pool slots of x - x_demo, u - u_demo
+        [[maybe_unused]] constexpr int DSX = DLU + NU, DSU = DSX + NX;    // WLS: pool slots of the scales s of the state / control rows
         Gather gFT, gGT, gE, gDX, gDU;
+        [[maybe_unused]] Gather gSX, gSU;
+        if constexpr (FM::WLS) {
+            make_gather(gSX, lane, L::NC, L::FSTRIDE, [](int r, int c) { return (r < NX) ? DSX + r : -1; });
+            make_gather(gSU, lane, L::NC, L::FSTRIDE, [](int r, int c) { return (r < M) ? DSU + r : -1; });
+        }
         make_gather(gFT, lane, L::NC, L::FSTRIDE, [](int r, int c) { return SMALL ? ((r < NX && (c & 3) < NX) ? Mdl::fwd_code(0, (c & 3) * NX + r) : -1)
                                                                                : ((r < NX && c < NX) ? Mdl::fwd_code(0, c * NX + r) : -1); });
         make_gather(gGT, lane, L::NC, L::FSTRIDE, [](int r, int c) { return SMALL ? ((r < M && (c & 3) < NX) ? Mdl::fwd_code(1, (c & 3) * NU + r) : -1)
@@ -910,6 +921,8 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
         make_gather(gDU, lane, L::NC, L::FSTRIDE, [](int r, int c) { return (r < M) ? DLU + r : -1; });
         const double* dxb = demo_x + (int64_t)b * (T + 1) * NX;
         const double* dub = demo_u + (int64_t)b * T * NU;
+        [[maybe_unused]] const double *wxb = nullptr, *wub = nullptr;      // WLS: this trajectory's weights
+        if constexpr (FM::WLS) { wxb = oc_wls(wls...).wx + (int64_t)b * oc_wls(wls...).bsx; wub = oc_wls(wls...).wu + (int64_t)b * oc_wls(wls...).bsu; }
         d4 X2 = z;
         [[maybe_unused]] d4 Gn = z;                         // GN: sum_t X_t' X_t + U_t' U_t; parameter block = rows and columns M .. M + NP - 1
         // feedback gains of step t are fetched one step ahead (each lane re-reads exactly what it stored)
@@ -934,12 +947,14 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
                 for (int i = 0; i < NX; ++i) {
                     xc[i] = xb[t * NX + i];
                     if constexpr (FM::COT) row[DLX + i] = t > 0 ? dxb[t * NX + i] : 0.0;       // the cotangent takes the slot as it is; gx_0 multiplies X_0 = 0: not loaded
+                    else if constexpr (FM::WLS) wls_slot(row[DLX + i], row[DSX + i], xc[i], dxb[t * NX + i], wxb[t * NX + i], oc_wls_x(oc_wls(wls...)), lsum);
                     else residual_slot<FM::RES>(row[DLX + i], xc[i], dxb[t * NX + i], lsum);
                 }
 #pragma unroll
                 for (int i = 0; i < NU; ++i) {
                     uc[i] = ub[t * NU + i];
                     if constexpr (FM::COT) row[DLU + i] = dub[t * NU + i];
+                    else if constexpr (FM::WLS) wls_slot(row[DLU + i], row[DSU + i], uc[i], dub[t * NU + i], wub[t * NU + i], oc_wls_u(oc_wls(wls...)), lsum);
                     else residual_slot<FM::RES>(row[DLU + i], uc[i], dub[t * NU + i], lsum);
                 }
                 PackedSink s{row};
@@ -948,6 +963,8 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
             wave_lds_sync();
             PDP_ACC(4);
             GatherRun rFT = gather_at(gFT, 0, blk), rGT = gather_at(gGT, 0, blk), rE = gather_at(gE, 0, blk), rDX = gather_at(gDX, 0, blk), rDU = gather_at(gDU, 0, blk);
+            [[maybe_unused]] GatherRun rSX, rSU;
+            if constexpr (FM::WLS) { rSX = gather_at(gSX, 0, blk); rSU = gather_at(gSU, 0, blk); }
             auto fstep = [&](int tl, const d4 Xc, d4& Xn, const d4 KTc, const d4 kc, d4& KTnx, d4& knx) {
                 const int t = t0 + tl, tnx = (t + 1 < T) ? t + 1 : t;
                 PDP_FINE(8, t == 20);
@@ -969,6 +986,11 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
                 riccati_forward(KTc, kc, FT, GT, E2, Xc, U2, Xn);
                 PDP_FINE(10, t == 20);
                 d4 Xm = Xc, Um = U2;
+                if constexpr (FM::WLS) {              // DX, DU carry s d; the rows of X_t, U_t scaled by the same s (U_t: register 0)
+                    const d4 SX = gather_run<NRT>(rSX, 1), SU = gather_run<1>(rSU, 1);
+                    Xm = wls_scale(SX, Xc);
+                    Um = zero4(); Um[0] = wls_scale(SU, U2)[0];
+                } else
                 mask_step<FM::MISS, NRT>(DX, DU, Xc, U2, Xm, Um);
                 if constexpr (FM::GN) Gn = gram_step<SMALL>(Xm, Um, Gn);
                 acc += contract_step(DX, DU, Xm, Um);
@@ -992,17 +1014,23 @@ __global__ void __launch_bounds__(64) PDP_FUSED_OCCUPANCY oc_pdp_fused_kernel(in
         wave_lds_sync();
         if (lane < NX) {
             if constexpr (FM::COT) dlT[lane] = dxb[T * NX + lane];
+            else if constexpr (FM::WLS) wls_slot(dlT[lane], dlT[NX + lane], xb[T * NX + lane], dxb[T * NX + lane], wxb[T * NX + lane], oc_wls_x(oc_wls(wls...)), lsum);
             else if constexpr (FM::MISS) { const double dd = dxb[T * NX + lane]; residual_slot<FM::RES>(dlT[lane], xb[T * NX + lane], dd, lsum); }      // (the demonstration's entry is asked for first, as it always was here)
             else residual_slot<FM::RES>(dlT[lane], xb[T * NX + lane], dxb[T * NX + lane], lsum);
         }
         wave_lds_sync();
         [[maybe_unused]] d4 X2m = z;                        // MISS: X_T with the rows that were not observed selected away
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { const int row = tile_row(lane, r); if (row < NX) { const double d = dlT[row]; X2m[r] = observed<FM::MISS>(d, X2[r]); acc += observed<FM::MISS>(d, d) * X2m[r]; } }
+        for (int r = 0; r < 4; ++r) {
+            const int row = tile_row(lane, r);
+            if constexpr (FM::WLS) { if (row < NX) { const double s = dlT[NX + row]; X2m[r] = s != 0.0 ? s * X2[r] : 0.0; acc += dlT[row] * X2m[r]; } }
+            else
+            if (row < NX) { const double d = dlT[row]; X2m[r] = observed<FM::MISS>(d, X2[r]); acc += observed<FM::MISS>(d, d) * X2m[r]; }
+        }
         if (dxdp) store_dense(dxdp + ((int64_t)b * (T + 1) + T) * NX * NP, NX, NP, NP, 0, M, lane, X2);
         finite = finite && tile_finite(X2);
         if constexpr (FM::GN) {                             // X_T, and the packed row's G block (gradient and loss follow below)
-            Gn = gram_add<SMALL>(FM::MISS ? X2m : X2, Gn);
+            Gn = gram_add<SMALL>(FM::MISS || FM::WLS ? X2m : X2, Gn);
             store_dense(grad + (int64_t)b * (NP + 1 + NP * NP) + NP + 1, NP, NP, NP, M, M, lane, Gn);
         }
     }

@@ -283,7 +283,8 @@ class LMLoop:
                 "iterations": len(self.loss_trace)}
 
     @classmethod
-    def for_irl(cls, mdl, demo_x, demo_u, theta0, tol=1e-10, max_iter=300, n_total=None, ini_state=None, skip_missing=False, **kw):
+    def for_irl(cls, mdl, demo_x, demo_u, theta0, tol=1e-10, max_iter=300, n_total=None, ini_state=None, skip_missing=False, weights_state=None, weights_control=None,
+                huber_delta=None, **kw):
         """The IRL drivers' problem: mdl a runtime.ModelLib of an OC model, demo_x [B, T+1, n], demo_u [B, T, m] the demonstrations (this rank's shard under
         torch.distributed; n_total as in parallel.allreduce_mean_packed), theta0 [p] shared by all of them.  evaluate(theta) solves every demonstration's OC problem
         (oc_solve_ms: the first cold, later ones warm from COPIES of the last accepted solution, so that a rejected trial cannot damage it), runs the fused unit once with
@@ -293,9 +294,13 @@ class LMLoop:
         skip_missing: demonstrations with gaps - a NaN in demo_x / demo_u is an entry that was not observed (PDP_GRAD_SKIP_MISSING: a keyframe every k steps, positions
         without velocities, no recorded controls = demo_u all NaN); loss, gradient and G are formed over the observed entries only.  ini_state [B, n] replaces
         demo_x[:, 0] as the initial state of the solves - needed where the first row of a demonstration is not (fully) observed: with skip_missing a NaN in the initial
-        state the solves would start from is a ValueError here, before any launch."""
+        state the solves would start from is a ValueError here, before any launch.
+        weights_state ([n], [T+1, n] or [B, T+1, n]), weights_control ([m], [T, m] or [B, T, m]), both >= 0 with 0 = not observed, huber_delta (> 0): the row the loop
+        minimises carries the weighted / Huber loss, its exact half derivative and the Gauss-Newton matrix of iteratively reweighted least squares
+        (pdp_oc_pdp_grad_wls_batched); the loop itself is unchanged.  They are checked once, here, and the weights stay on the device."""
         if skip_missing:                            # judged on what the caller gave (a host array is not moved to the device first)
             _refuse_nan_start("LMLoop.for_irl", demo_x, ini_state, "demo_x")
+        wls = _oc_wls_keywords(mdl, demo_u, weights_state, weights_control, huber_delta)
         from . import parallel
         demo_x, demo_u = rt.dev(demo_x), rt.dev(demo_u)
         B, T, p = int(demo_u.shape[0]), int(demo_u.shape[1]), mdl.p
@@ -308,7 +313,10 @@ class LMLoop:
             # no decision on this rank's own flags: solve and unit always run, the flags are counted on the device and travel with the rows, so that every rank issues
             # the same collective and takes the same decision (parallel.mean_row_checked) - and the host reads the device once
             s = mdl.oc_solve_ms(x0, theta, T, tol=tol, max_iter=max_iter, warm=state["accepted"])
-            out = mdl.oc_pdp_grad(s["control"], theta, demo_x, demo_u, x=s["state"], lam=s["costate"], gauss_newton=True, skip_missing=skip_missing, buffers=bufs)
+            if wls:
+                out = mdl._oc_pdp_wls_dev(s["control"], *mdl._theta(theta, B), demo_x, demo_u, None, s["state"], s["costate"], bufs, skip_missing, *wls)
+            else:
+                out = mdl.oc_pdp_grad(s["control"], theta, demo_x, demo_u, x=s["state"], lam=s["costate"], gauss_newton=True, skip_missing=skip_missing, buffers=bufs)
             bad = (s["converged_flags"] == 0) | ((s["status"] & ~informational) != 0) | (out["status"] != 0)
             row = parallel.mean_row_checked(out["packed_gn"], bad, n_total)
             if row is None:
@@ -412,6 +420,16 @@ class LMLoop:
         loop = cls(evaluate, th0, **kw)
         loop.split = split
         return loop
+
+
+def _oc_wls_keywords(mdl, demo_u, weights_state, weights_control, huber_delta):
+    """The weights_state / weights_control / huber_delta keywords of the for_irl constructors, checked ONCE and with the weights on the device: () when none is given,
+    else the last five arguments of ModelLib._oc_pdp_wls_dev."""
+    if weights_state is None and weights_control is None and huber_delta is None:
+        return ()
+    shape = tuple(np.shape(demo_u))
+    wx, wxs, wu, wus, delta = rt.oc_wls_arguments(weights_state, weights_control, huber_delta, int(shape[0]), int(shape[1]), mdl.n, mdl.m)
+    return (rt.dev(wx).contiguous() if wx is not None else None, wxs, rt.dev(wu).contiguous() if wu is not None else None, wus, delta)
 
 
 def _wls_keywords(mdl, inputs, weights, huber_delta):
@@ -571,14 +589,17 @@ class BatchedLMLoop:
         return loop
 
     @classmethod
-    def for_irl(cls, mdl, demo_x, demo_u, theta0, samples_per_problem=1, tol=1e-10, max_iter=300, ini_state=None, skip_missing=False, **kw):
+    def for_irl(cls, mdl, demo_x, demo_u, theta0, samples_per_problem=1, tol=1e-10, max_iter=300, ini_state=None, skip_missing=False, weights_state=None,
+                weights_control=None, huber_delta=None, **kw):
         """One IRL problem per group of samples_per_problem consecutive demonstrations: demo_x [K S, T+1, n], demo_u [K S, T, m], theta0 [K, p] or [p].  An evaluation
         solves every demonstration's OC problem at its problem's trial point (oc_solve_ms with per-sample parameters: the first cold, later ones warm from COPIES of the
         last accepted solutions) and runs the fused unit once with gauss_newton=True.  A sample is bad under LMLoop.for_irl's three conditions: its solve did not
         converge, reported trouble, or the unit set a status bit.  After the update the accepted solutions are refreshed where the launch accepted the sample's problem
-        (torch.where on accepted_now: no host decision).  skip_missing, ini_state: as in LMLoop.for_irl."""
+        (torch.where on accepted_now: no host decision).  skip_missing, ini_state: as in LMLoop.for_irl.
+        weights_state, weights_control, huber_delta: as in LMLoop.for_irl - checked once here, then every evaluation's unit is one launch of pdp_oc_pdp_grad_wls_batched."""
         if skip_missing:
             _refuse_nan_start("BatchedLMLoop.for_irl", demo_x, ini_state, "demo_x")
+        wls = _oc_wls_keywords(mdl, demo_u, weights_state, weights_control, huber_delta)
         torch = rt.torch_cuda()
         demo_x, demo_u = rt.dev(demo_x), rt.dev(demo_u)
         B, T, S = int(demo_u.shape[0]), int(demo_u.shape[1]), int(samples_per_problem)
@@ -589,7 +610,10 @@ class BatchedLMLoop:
 
         def evaluate_rows(trial):
             s = mdl.oc_solve_ms(x0, trial, T, tol=tol, max_iter=max_iter, warm=sols["accepted"])
-            out = mdl.oc_pdp_grad(s["control"], trial, demo_x, demo_u, x=s["state"], lam=s["costate"], gauss_newton=True, skip_missing=skip_missing, buffers=bufs)
+            if wls:
+                out = mdl._oc_pdp_wls_dev(s["control"], *mdl._theta(trial, B), demo_x, demo_u, None, s["state"], s["costate"], bufs, skip_missing, *wls)
+            else:
+                out = mdl.oc_pdp_grad(s["control"], trial, demo_x, demo_u, x=s["state"], lam=s["costate"], gauss_newton=True, skip_missing=skip_missing, buffers=bufs)
             sols["trial"] = (s["state"], s["control"], s["costate"])
             bad = (s["converged_flags"] == 0) | ((s["status"] & ~informational) != 0) | (out["status"] != 0)
             return out["packed_gn"], bad.to(torch.int32)

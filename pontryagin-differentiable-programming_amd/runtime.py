@@ -78,6 +78,7 @@ MODEL_EXT_SYMBOLS = ["pdp_sysid_step_gn_batched"]        # declared in the exten
 
 MODEL_INI_SYMBOLS = ["pdp_sysid_step_gn_ini_batched"]   # include/pdp_hip_sysid_ini.h: one list per extension header
 MODEL_WLS_SYMBOLS = ["pdp_sysid_step_wls_batched"]      # include/pdp_hip_sysid_wls.h
+MODEL_OC_WLS_SYMBOLS = ["pdp_oc_pdp_grad_wls_batched"]  # include/pdp_hip_oc_wls.h
 
 _core = None
 
@@ -347,6 +348,33 @@ def wls_arguments(weights, huber_delta, B, T, n):
     return w, (0 if len(w.shape) == 2 else (T + 1) * n), delta
 
 
+def oc_wls_arguments(weights_x, weights_u, huber_delta, B, T, n, m):
+    """The weights and Huber's threshold of pdp_oc_pdp_grad_wls_batched, normalised and checked on what the caller gave, in the spirit of wls_arguments: returns
+    (weights_x shaped [T+1, n] or [B, T+1, n], or None; its batch stride; weights_u shaped [T, m] or [B, T, m], or None; its batch stride; delta as a float, +inf for
+    off).  weights_x broadcasts from [n], [T+1, n] or [B, T+1, n], weights_u from [m], [T, m] or [B, T, m]; a negative or non-finite weight, another shape, or a
+    huber_delta that is not > 0 is a ValueError before any launch.  The loops of irl.py call it once and evaluate many times (ModelLib._oc_pdp_wls_dev)."""
+    delta = float("inf") if huber_delta is None else float(huber_delta)
+    if not delta > 0.0:
+        raise ValueError("huber_delta: a threshold > 0 (None: plain least squares), got %r" % (huber_delta,))
+
+    def one(w, name, rows, k, letter):
+        if w is None:
+            return None, 0
+        w = w if hasattr(w, "data_ptr") else np.asarray(w, dtype=float)
+        shape = tuple(w.shape)
+        if shape not in ((k,), (rows, k), (B, rows, k)):
+            raise ValueError("%s: shape [%s], [%s, %s] or [B, %s, %s] = (%d,), (%d, %d) or (%d, %d, %d), got %s"
+                             % (name, letter, "T+1" if rows == T + 1 else "T", letter, "T+1" if rows == T + 1 else "T", letter, k, rows, k, B, rows, k, shape))
+        if not bool(((w >= 0) & (w < float("inf"))).all()):          # (a NaN fails the comparison)
+            raise ValueError("%s: finite and >= 0 (0: the entry is not observed)" % name)
+        if len(shape) == 1:
+            w = w.expand(rows, k) if hasattr(w, "data_ptr") else np.broadcast_to(w, (rows, k))
+        return w, (0 if len(w.shape) == 2 else rows * k)
+    wx, wxs = one(weights_x, "weights_x", T + 1, n, "n")
+    wu, wus = one(weights_u, "weights_u", T, m, "m")
+    return wx, wxs, wu, wus, delta
+
+
 # ------------------------------------------------------------------------------------------------------
 # per-model libraries (section B of include/pdp_hip.h)
 # ------------------------------------------------------------------------------------------------------
@@ -384,6 +412,8 @@ _MODEL_SIGS = {
     "pdp_sysid_step_gn_ini_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _I, _I, _VP, _VP, _VP, _I64, _VP]),
     # include/pdp_hip_sysid_wls.h
     "pdp_sysid_step_wls_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _I64, C.c_double, _VP, _I, _I, _VP, _VP, _VP, _I64, _VP]),
+    # include/pdp_hip_oc_wls.h
+    "pdp_oc_pdp_grad_wls_batched": (_I, [_I, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I64, _VP, _I64, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
 }
 _models = {}
 
@@ -600,7 +630,7 @@ class ModelLib:
         return out
 
     def oc_pdp_grad(self, u, theta, demo_x, demo_u, x0=None, x=None, lam=None, want_sens=False, buffers=None, packed=False, want_riccati=False,
-                    want_predict_record=False, gauss_newton=False, skip_missing=False):
+                    want_predict_record=False, gauss_newton=False, skip_missing=False, weights_x=None, weights_u=None, huber_delta=None):
         """Fused forward + Riccati + PDP gradient.  Give (x, lam) to use an optimal trajectory (PDP_OC_GIVEN_TRAJ),
         else x0 and the kernel integrates u and the costates itself.  Returns dict(loss, grad, x, lam, status[, dxdp, dudp][, riccati]).
         packed: the kernel writes gradient and loss as one [B, p+1] tensor (PDP_OC_PACKED; out["packed"], out["grad"] is a view of it).
@@ -616,7 +646,17 @@ class ModelLib:
         skip_missing (PDP_GRAD_SKIP_MISSING): a NaN in demo_x / demo_u marks an entry that was not observed - its residual is left out of the loss, its term out of the
         gradient and, with gauss_newton, its Jacobian row out of G (only NaN: an inf propagates as always).  demo_x[:, 0] may be all NaN when x0 is given.  Alone, with
         packed or with gauss_newton; with want_sens, want_riccati or want_predict_record: ValueError (and oc_pdp_vjp has no such switch: a NaN cotangent is an error).
-        Beyond the fused kernels' limits the same rows come from the materialised sensitivities, masked and contracted with torch.einsum."""
+        Beyond the fused kernels' limits the same rows come from the materialised sensitivities, masked and contracted with torch.einsum.
+        weights_x [n], [T+1, n] or [B, T+1, n], weights_u [m], [T, m] or [B, T, m], huber_delta (pdp_oc_pdp_grad_wls_batched, include/pdp_hip_oc_wls.h: the semantics):
+        a weight per demonstration entry (0: not observed) and Huber's loss on the standardised residual.  Any of the three implies the packed Gauss-Newton dict
+        (packed_gn, grad, loss, gn as views) of the weighted / robust loss; they combine with skip_missing, x0, a given (x, lam) and buffers={"packed_gn": ...}; with
+        want_sens, want_riccati, want_predict_record or packed: ValueError.  Beyond the fused kernels' limits the same row comes from scaled residuals and row-scaled
+        materialised sensitivities."""
+        if weights_x is not None or weights_u is not None or huber_delta is not None:
+            for name, on in (("want_sens", want_sens), ("want_riccati", want_riccati), ("want_predict_record", want_predict_record), ("packed", packed)):
+                if on:
+                    raise ValueError("oc_pdp_grad: weights_x, weights_u and huber_delta give the packed Gauss-Newton row only - not together with %s" % name)
+            return self._oc_pdp_wls(u, theta, demo_x, demo_u, x0, x, lam, buffers, skip_missing, weights_x, weights_u, huber_delta)
         if skip_missing and (want_sens or want_riccati or want_predict_record):
             raise ValueError("oc_pdp_grad: skip_missing=True goes with the gradient, packed or gauss_newton rows only - not with want_sens, want_riccati or "
                              "want_predict_record")
@@ -711,6 +751,78 @@ class ModelLib:
         if want_predict_record:
             out["predict_record"] = prec
         return out
+
+    def _oc_pdp_wls(self, u, theta, demo_x, demo_u, x0, x, lam, buffers, skip_missing, weights_x, weights_u, huber_delta):
+        """oc_pdp_grad with weights and / or Huber's loss: the arguments are checked and moved to the device here, the call is _oc_pdp_wls_dev's"""
+        u_shape = tuple(np.shape(u))
+        if len(u_shape) != 3 or u_shape[2] != self.m:
+            raise ValueError("oc_pdp_grad: u must be [B, T, %d], got %s" % (self.m, u_shape))
+        B, T = int(u_shape[0]), int(u_shape[1])
+        wx, wxs, wu, wus, delta = oc_wls_arguments(weights_x, weights_u, huber_delta, B, T, self.n, self.m)
+        if x is not None and lam is None:
+            raise ValueError("oc_pdp_grad: a given trajectory needs x and lam")
+        if x is None and x0 is None:
+            raise ValueError("oc_pdp_grad: x0 [B, %d] is needed unless (x, lam) are given" % self.n)
+        u, demo_x, demo_u = dev(u), dev(demo_x), dev(demo_u)
+        th, tb = self._theta(theta, B)
+        if x is not None:
+            x, lam, x0 = dev(x), dev(lam), None
+        else:
+            x0 = dev(x0).reshape(B, self.n)
+        return self._oc_pdp_wls_dev(u, th, tb, demo_x, demo_u, x0, x, lam, buffers, skip_missing, dev(wx) if wx is not None else None, wxs,
+                                    dev(wu) if wu is not None else None, wus, delta)
+
+    def _oc_pdp_wls_dev(self, u, th, tb, demo_x, demo_u, x0, x, lam, buffers, skip_missing, wxd, wxs, wud, wus, delta):
+        """pdp_oc_pdp_grad_wls_batched on device tensors and normalised arguments (oc_wls_arguments: wxd [T+1, n] or [B, T+1, n] or None, wud [T, m] or [B, T, m] or
+        None, their batch strides, delta a float), no check and no host synchronisation: what the loops of irl.py call per evaluation.  th [1 or B, p] with row stride
+        tb; (x, lam) given (PDP_OC_GIVEN_TRAJ) or x0 [B, n].  Always the packed Gauss-Newton dict."""
+        torch = torch_cuda()
+        B, T, n, m, p = u.shape[0], u.shape[1], self.n, self.m, self.p
+        bufs = buffers if buffers is not None else {}
+
+        def buf(key, shape, dtype=torch.float64):
+            t = bufs.get(key)
+            if t is None or tuple(t.shape) != tuple(shape):
+                t = bufs[key] = torch.empty(shape, dtype=dtype, device="cuda")
+            return t
+        flags = 32 if skip_missing else 0
+        if x is not None:
+            flags |= 1
+        else:
+            x, lam = buf("x", (B, T + 1, n)), buf("lam", (B, T, n))
+        loss, pk, status = buf("loss", (B,)), buf("packed_gn", (B, p + 1 + p * p)), buf("status", (B,), torch.int32)
+        nbytes = self.lib.pdp_oc_pdp_workspace_bytes(B, T)
+        ws = buf("ws", (max(nbytes, 8) // 8,))
+        rc = self.lib.pdp_oc_pdp_grad_wls_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(demo_x), ptr(demo_u), ptr(wxd), wxs, ptr(wud), wus, delta, ptr(x),
+                                                  ptr(lam), ptr(loss), ptr(pk), ptr(status), ptr(ws), nbytes, current_stream_ptr())
+        if rc == -2:
+            # beyond the fused kernels' limits: the want_sens launch of the kernel-by-kernel route on zero-filled demonstrations gives x, lam, status and the
+            # sensitivities; the row is formed here from scaled residuals and row-scaled sensitivities (selects, as in the kernels: never a product with 0)
+            self._warn_materialised(T)
+            zero, one = torch.zeros((), dtype=torch.float64, device="cuda"), torch.ones((), dtype=torch.float64, device="cuda")
+            dxdp, dudp = torch.empty((B, T + 1, n, p), dtype=torch.float64, device="cuda"), torch.empty((B, T, m, p), dtype=torch.float64, device="cuda")
+            self._oc_pdp_grad_materialised(u, th, torch.where(torch.isnan(demo_x), zero, demo_x), torch.where(torch.isnan(demo_u), zero, demo_u), x0, x, lam, flags & 1,
+                                           loss, pk[:, :p], status, dxdp, dudp)
+
+            def side(v, demo, w, S):
+                wf = (w if w is not None else one).expand(*demo.shape)
+                d = v - demo
+                obs = (wf > 0) & (demo == demo) if skip_missing else wf > 0
+                e = wf.sqrt() * d
+                ae = e.abs()
+                quad = ae <= delta
+                s = torch.where(quad, wf, wf * (delta / ae)).sqrt()
+                rho = torch.where(obs, torch.where(quad, e * e, 2.0 * delta * ae - delta * delta), zero).sum(dim=(1, 2))
+                return rho, torch.where(obs, s * d, zero), torch.where((obs & (s != 0))[..., None], s[..., None] * S, zero)
+            lx, sdx, sX = side(x, demo_x, wxd, dxdp)
+            lu, sdu, sU = side(u, demo_u, wud, dudp)
+            loss.copy_(lx + lu)
+            pk[:, p].copy_(loss)
+            pk[:, :p].copy_(torch.einsum("bti,btip->bp", sdx, sX) + torch.einsum("bti,btip->bp", sdu, sU))
+            pk[:, p + 1:].copy_((torch.einsum("btip,btiq->bpq", sX, sX) + torch.einsum("btip,btiq->bpq", sU, sU)).reshape(B, p * p))
+            rc = 0
+        check(rc, "pdp_oc_pdp_grad_wls_batched")
+        return dict(packed_gn=pk, loss=pk[:, p], grad=pk[:, :p], gn=pk[:, p + 1:].view(B, p, p), x=x, lam=lam, status=status)
 
     def oc_pdp_vjp(self, u, theta, gx, gu, x0=None, x=None, lam=None, buffers=None):
         """The fused unit as a vector-Jacobian product of the OC solution (PDP_OC_COTANGENT, include/pdp_hip.h): gx [B, T+1, n] = dL/dx and gu [B, T, m] = dL/du are the
