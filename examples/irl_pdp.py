@@ -30,6 +30,12 @@ to the demonstrations (states at t >= 1, every control) and weights every entry 
 t >= 1, every control) by +-(0.5 .. 1.5); --huber is Huber's threshold on the standardised residual sqrt(w) d, which keeps such entries from steering the fit:
 
     python examples/irl_pdp.py --system cartpole --method lm --huber 0.01 --outliers 0.05
+
+A prior and error bars (--method lm): --prior-sigma S puts a Gaussian prior of standard deviation S around the starting parameter (the prior_mean= / prior_precision=
+keywords of the loops), --covariance prints theta +- std_err and the pivot ratio of the covariance solve (loop.covariance()).  Keyframes without controls leave the scale
+of the cost weights unidentified: the pivot ratio shows it, the prior makes the problem well posed:
+
+    python examples/irl_pdp.py --system cartpole --method lm --every 10 --observe 0,1 --no-controls --prior-sigma 0.5 --covariance
 """
 import argparse
 import os
@@ -114,6 +120,9 @@ def run_lm(a, oc, demo_x, demo_u, theta, true_parameter):
             print("%d of %d demonstration entries are outliers" % (k, demo_x.size + demo_u.size))
     if a.huber is not None:
         wls["huber_delta"] = a.huber
+    if a.prior_sigma is not None:
+        assert a.prior_sigma > 0, "--prior-sigma: a positive number"
+        wls.update(prior_mean=np.array(theta, dtype=float), prior_precision=np.full(np.size(theta), 1.0 / a.prior_sigma ** 2))
     sparse = a.every is not None or a.observe is not None or a.no_controls
     if sparse:
         assert a.every is None or a.every >= 1, "--every: a positive number of steps"
@@ -129,6 +138,11 @@ def run_lm(a, oc, demo_x, demo_u, theta, true_parameter):
     r = loop.run(max_evals=a.iters, loss_tol=a.loss_tol)
     for k, (loss, th, lam) in enumerate(zip(r["loss_trace"], r["parameter_trace"], r["lambda_trace"])):
         print("accepted %3d  loss %.6e  |theta - theta*| %.4e  next damping %.1e" % (k, loss, np.abs(th - true_parameter).max(), lam))
+    if a.covariance:
+        noise = "known" if (a.noise_sigma is not None or a.prior_sigma is not None) else "estimated"
+        c = loop.covariance(noise)
+        print("theta %s  (noise %s, sigma^2 %.3e)  pivot_ratio %.2e%s" % ("  ".join("%.5f +- %.1e" % (v, e) for v, e in zip(r["parameter_trace"][-1], c["std_err"])), noise,
+                                                                           c["sigma2"], c["pivot_ratio"], "" if c["status"] == 0 else "  (singular)"))
     save = {"trail_no": 0, "loss_trace": r["loss_trace"], "parameter_trace": r["parameter_trace"], "learning_rate": 0.0, "time_passed": time.time() - t0}
     if a.out:
         sio.savemat(a.out, {"results": save})
@@ -166,10 +180,14 @@ def main():
                                                         "component; the weights are 1 / s_i^2")
     ap.add_argument("--huber", type=float, default=None, help="--method lm: Huber's threshold on the standardised residual")
     ap.add_argument("--outliers", type=float, default=0.0, help="--method lm: this fraction of the demonstration entries is moved by +-(0.5 .. 1.5)")
+    ap.add_argument("--prior-sigma", type=float, default=None, help="--method lm: a Gaussian prior of this standard deviation around the starting parameter")
+    ap.add_argument("--covariance", action="store_true", help="--method lm: print theta +- std_err and the pivot ratio of the covariance solve")
     ap.add_argument("--demos", default=None, help="<name>_demos.mat in the reference's schema (default: the stored demos of --system)")
     a = ap.parse_args()
     if (a.noise_sigma is not None or a.huber is not None or a.outliers > 0) and a.method != "lm":
         ap.error("--noise-sigma / --huber / --outliers need --method lm")
+    if (a.prior_sigma is not None or a.covariance) and a.method != "lm":
+        ap.error("--prior-sigma / --covariance need --method lm")
 
     env, dt = zoo.make_env(a.system, "irl")
     oc = PDP.OCSys(a.system)

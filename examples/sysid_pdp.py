@@ -31,6 +31,12 @@ that component by 1 / s_i^2; --outliers moves that fraction of the recorded entr
 sqrt(w) (x - x_obs).  (--sigma is the spread of the starting parameter, as it always was.)
 
     python examples/sysid_pdp.py --system cartpole --method lm --noise-sigma 1e-3,1e-3,1e-2,1e-2 --huber 3 --outliers 0.05
+
+--method lm --prior-sigma S --covariance: a Gaussian prior of standard deviation S around the starting parameter (the prior_mean= / prior_precision= keywords of the two
+loops: a partially identifiable problem becomes well posed) and the error bars of the estimate (loop.covariance(): theta +- std_err and the pivot ratio of the solve, the
+diagnosis of a parameter the data do not pin).  The noise level is taken as known where --noise-sigma gives the weights or a prior is set, else estimated from the loss:
+
+    python examples/sysid_pdp.py --system pendulum --method lm --per-trajectory --prior-sigma 0.5 --covariance
 """
 import argparse
 import os
@@ -75,8 +81,14 @@ def main():
     ap.add_argument("--noise-sigma", default=None, help="--method lm: per-component noise levels s0,s1,... added to the recorded states; the weights are 1 / s_i^2")
     ap.add_argument("--huber", type=float, default=None, help="--method lm: Huber's threshold on the standardised residual")
     ap.add_argument("--outliers", type=float, default=0.0, help="--method lm: this fraction of the recorded entries is moved by +-(0.5 .. 1.5)")
+    ap.add_argument("--prior-sigma", type=float, default=None, help="--method lm: a Gaussian prior of this standard deviation around the starting parameter")
+    ap.add_argument("--covariance", action="store_true", help="--method lm: print theta +- std_err and the pivot ratio of the covariance solve")
     a = ap.parse_args()
     partial = a.every > 1 or a.observe is not None
+    if (a.prior_sigma is not None or a.covariance) and a.method != "lm":
+        ap.error("--prior-sigma / --covariance need --method lm")
+    if a.prior_sigma is not None and not a.prior_sigma > 0:
+        ap.error("--prior-sigma: a positive number")
     if a.estimate_ini is not None and a.method != "lm":
         ap.error("--estimate-ini needs --method lm")
     if partial and a.method != "lm":
@@ -113,6 +125,11 @@ def main():
             print("%d of %d recorded entries are outliers" % (k, states.size))
     if a.huber is not None:
         wls["huber_delta"] = a.huber
+    if a.prior_sigma is not None:
+        wls["prior_mean"], wls["prior_precision"] = theta.copy(), np.full(theta.size, 1.0 / a.prior_sigma ** 2)
+        if a.estimate_ini is not None:              # the same prior on the estimated components of the initial states, around their start (0)
+            wls["prior_ini_precision"] = np.full(len(a.estimate_ini.split(",")), 1.0 / a.prior_sigma ** 2)
+    noise = "known" if (a.noise_sigma is not None or a.prior_sigma is not None) else "estimated"
     loss_trace, parameter_trace = [], []
     t0 = time.time()
     if a.method == "lm":
@@ -134,6 +151,12 @@ def main():
             loop = make(sid.model(), inputs, data, theta, ini_state=ini, skip_missing=True, estimate_ini=idx, **wls, **(dict(max_evals=min(a.iters, 100), loss_tol=1e-20)
                                                                                                                      if a.per_trajectory else {}))
             r = loop.run() if a.per_trajectory else loop.run(max_evals=min(a.iters, 100), loss_tol=1e-20)
+            if a.covariance:                        # over the whole vector of unknowns: theta, then the estimated components of the initial state(s)
+                c = loop.covariance(noise)
+                for k in (range(inputs.shape[0]) if a.per_trajectory else [None]):
+                    v, e = (r["theta"][k], c["std_err"][k]) if a.per_trajectory else (r["parameter_trace"][-1], c["std_err"])
+                    print("%s [theta | ini_state%s] %s  (noise %s)  pivot_ratio %.2e" % ("problem %3d " % k if a.per_trajectory else "", idx,
+                          "  ".join("%.5f +- %.1e" % (vi, ei) for vi, ei in zip(v, e)), noise, c["pivot_ratio"][k] if a.per_trajectory else c["pivot_ratio"]))
             if a.per_trajectory:
                 th, x0 = loop.split(r["theta"])
                 for k in range(inputs.shape[0]):
@@ -152,11 +175,18 @@ def main():
             return r
         if a.per_trajectory:
             kw = dict(ini_state=states[:, 0], skip_missing=True) if partial else {}
-            r = BatchedLMLoop.for_sysid(sid.model(), inputs, masked if partial else states, theta, max_evals=min(a.iters, 100), loss_tol=1e-20, **kw, **wls).run()
+            loop = BatchedLMLoop.for_sysid(sid.model(), inputs, masked if partial else states, theta, max_evals=min(a.iters, 100), loss_tol=1e-20, **kw, **wls)
+            r = loop.run()
             for k in range(inputs.shape[0]):
                 print("problem %3d  %2d evaluations  %2d rejected  %-9s  loss %.6e -> %.6e  |theta - theta*| = %.2e  theta %s"
                       % (k, r["evaluations"][k], r["rejected"][k], r["state"][k], r["loss_trace"][k][0], r["loss"][k], np.abs(r["theta"][k] - true_parameter).max(),
                          np.array2string(r["theta"][k], precision=4)))
+            if a.covariance:
+                c = loop.covariance(noise)
+                for k in range(inputs.shape[0]):
+                    print("problem %3d  theta %s  (noise %s, sigma^2 %.3e)  pivot_ratio %.2e%s"
+                          % (k, "  ".join("%.5f +- %.1e" % (v, e) for v, e in zip(r["theta"][k], c["std_err"][k])), noise, c["sigma2"][k], c["pivot_ratio"][k],
+                             "" if c["status"][k] == 0 else "  (singular)"))
             print("done: %d problems in %d launches, %.2f s; largest final loss %.4e" % (inputs.shape[0], r["launches"], time.time() - t0, np.max(r["loss"])))
             return r
         if partial:
@@ -168,6 +198,10 @@ def main():
         for k in range(len(loss_trace)):
             print("accepted %3d  loss %.6e  lambda %.1e  theta %s" % (k, loss_trace[k], r["lambda_trace"][k], np.array2string(parameter_trace[k], precision=4)))
         print("%d evaluations, %d rejected%s" % (r["evaluations"], r["rejected"], ", stalled" if r["stalled"] else ""))
+        if a.covariance:
+            c = loop.covariance(noise)
+            print("theta %s  (noise %s, sigma^2 %.3e)  pivot_ratio %.2e" % ("  ".join("%.5f +- %.1e" % (v, e) for v, e in zip(parameter_trace[-1], c["std_err"])), noise,
+                                                                            c["sigma2"], c["pivot_ratio"]))
         theta, a.iters = parameter_trace[-1], len(loss_trace)
     elif a.graph:
         from pdp_amd import runtime as rt

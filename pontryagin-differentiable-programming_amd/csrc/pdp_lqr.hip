@@ -3,6 +3,8 @@
 //   pdp_cp_aux_integrate_batched     ControlPlanning.integrateAuxSys (PDP/PDP.py:813-838)
 //   pdp_sysid_aux_integrate_batched  SysID.integrateAuxSys      (PDP/PDP.py:1241-1259)
 //   pdp_lm_update_batched            the Levenberg-Marquardt update of many independent problems (include/pdp_hip_lm.h, pdp_lm_kernels.h)
+//   pdp_lm_update_prior_batched      the same with a Gaussian prior on the unknowns (include/pdp_hip_lm_prior.h, pdp_lm_kernels.h)
+//   pdp_lm_covariance_batched        the covariance of those estimates: scale (J'J)^-1 per problem
 // One wavefront (= one 64-thread workgroup) per trajectory; matrices are read from HBM straight into the
 // register tile layout, every product is a chain of v_mfma_f64_16x16x4_f64 (pdp_tile.h / pdp_riccati.h).
 #include <hip/hip_runtime.h>
@@ -338,7 +340,28 @@ int pdp_lm_update_batched(int K, int S, int p, const double* rows, int rows_bstr
     if (!(schedule->up > 0.0) || !(schedule->down > 0.0) || st.trace_len < 0) return PDP_E_ARG;
     if (p > LM_PMAX) return PDP_E_SIZE;
     if (rows_bstride < p + 1 + p * p) return PDP_E_ARG;
-    return launch(lm_update_kernel, dim3((unsigned)((K - 1) / 4 + 1)), dim3(64), 0, (hipStream_t)stream, K, S, p, rows, rows_bstride, bad, *schedule, st);
+    return launch(lm_update_kernel<>, dim3((unsigned)((K - 1) / 4 + 1)), dim3(64), 0, (hipStream_t)stream, K, S, p, rows, rows_bstride, bad, *schedule, st);
+}
+
+int pdp_lm_update_prior_batched(int K, int S, int p, const double* rows, int rows_bstride, const int32_t* bad, const pdp_lm_schedule* schedule, const pdp_lm_state* state,
+                                const pdp_lm_prior* prior, void* stream) {
+    if (!prior) return pdp_lm_update_batched(K, S, p, rows, rows_bstride, bad, schedule, state, stream);
+    if (K <= 0 || S <= 0 || p <= 0 || !rows || !schedule || !state) return PDP_E_ARG;
+    const pdp_lm_state& st = *state;
+    if (!st.theta || !st.trial || !st.lam || !st.current || !st.state || !st.evaluations || !st.rejected || !st.accepted || !st.counters) return PDP_E_ARG;
+    if (!(schedule->up > 0.0) || !(schedule->down > 0.0) || st.trace_len < 0) return PDP_E_ARG;
+    if (!prior->mean || !prior->precision || (prior->kind != 0 && prior->kind != 1) || prior->mean_kstride < 0 || prior->precision_kstride < 0) return PDP_E_ARG;
+    if (p > LM_PMAX) return PDP_E_SIZE;
+    if (rows_bstride < p + 1 + p * p) return PDP_E_ARG;
+    return launch(lm_update_kernel<pdp_lm_prior>, dim3((unsigned)((K - 1) / 4 + 1)), dim3(64), 0, (hipStream_t)stream, K, S, p, rows, rows_bstride, bad, *schedule, st, *prior);
+}
+
+int pdp_lm_covariance_batched(int K, int p, const double* rows, int rows_bstride, const double* scale, double* cov, double* std_err, double* pivot_ratio, int32_t* status,
+                              void* stream) {
+    if (K <= 0 || p <= 0 || !rows || !cov || !status) return PDP_E_ARG;
+    if (p > LM_PMAX) return PDP_E_SIZE;
+    if (rows_bstride < p + 1 + p * p) return PDP_E_ARG;
+    return launch(lm_covariance_kernel, dim3((unsigned)((K - 1) / 4 + 1)), dim3(64), 0, (hipStream_t)stream, K, p, rows, rows_bstride, scale, cov, std_err, pivot_ratio, status);
 }
 
 }  // extern "C"

@@ -206,17 +206,173 @@ def _refuse_nan_start(who, data, ini_state, name):
         raise ValueError("%s: skip_missing=True and the initial state (%s) holds a NaN: give ini_state [B, n]" % (who, "%s[:, 0]" % name if ini_state is None else "ini_state"))
 
 
+def _host(a):
+    return np.asarray(a.detach().cpu() if hasattr(a, "detach") else a, dtype=float)
+
+
+def prior_layout(who, mean_shape, precision_shape, p, K=None, prior_kind=None):
+    """0 (the precision is a diagonal) or 1 (a full matrix) from the shapes of a prior: mean [p] (or [K, p] where K is given); precision [p] or [p, p], with K also
+    [K, p] and [K, p, p].  Where K == p the shape [p, p] says nothing - a shared full matrix or one diagonal per problem: prior_kind ("diagonal" or "full") decides,
+    and without it the shape is refused rather than guessed.  A shape that is none of these, or one that contradicts prior_kind, is a ValueError."""
+    if prior_kind not in (None, "diagonal", "full"):
+        raise ValueError("%s: prior_kind is 'diagonal' or 'full'" % who)
+    ps = tuple(int(v) for v in precision_shape)
+    if K is not None and K == p and ps == (p, p) and prior_kind is None:
+        raise ValueError("%s: with K == p = %d a prior_precision of shape [%d, %d] is a shared full matrix or one diagonal per problem: say prior_kind='full' or "
+                         "prior_kind='diagonal'" % (who, p, p, p))
+    try:
+        kind = rt.lm_prior_shapes(mean_shape, ps, K if K is not None else -1, p, diagonal_per_problem=prior_kind == "diagonal")[0]
+    except ValueError as e:
+        raise ValueError("%s: %s" % (who, e)) from None
+    if prior_kind is not None and kind != (0 if prior_kind == "diagonal" else 1):
+        raise ValueError("%s: prior_precision of shape %s is not a %s precision" % (who, list(ps), prior_kind))
+    return kind
+
+
+def check_prior(who, prior_mean, prior_precision, p, K=None, prior_kind=None):
+    """The prior_mean / prior_precision keywords of the least-squares loops, checked on the host before any launch: (mean, precision) as fp64 numpy arrays, or (None,
+    None) when neither is given.  Shapes and prior_kind: prior_layout; a non-finite entry, a negative diagonal entry or an asymmetric matrix is a ValueError."""
+    if prior_mean is None and prior_precision is None:
+        return None, None
+    if prior_mean is None or prior_precision is None:
+        raise ValueError("%s: prior_mean and prior_precision go together" % who)
+    mean, prec = _host(prior_mean), _host(prior_precision)
+    kind = prior_layout(who, mean.shape, prec.shape, p, K, prior_kind)
+    if not (np.isfinite(mean).all() and np.isfinite(prec).all()):
+        raise ValueError("%s: prior_mean / prior_precision hold a non-finite entry" % who)
+    if kind == 1 and not np.array_equal(prec, np.swapaxes(prec, -1, -2)):
+        raise ValueError("%s: prior_precision is not symmetric" % who)
+    if ((np.diagonal(prec, axis1=-2, axis2=-1) if kind == 1 else prec) < 0).any():
+        raise ValueError("%s: prior_precision has a negative diagonal entry" % who)
+    return mean, prec
+
+
+def _prior_with_ini(who, mean, prec, prior_ini_precision, p, q, start, K=None, prior_kind=None):
+    """the prior of [theta | estimated initial-state components]: the theta part (checked by check_prior; None: no prior on theta) extended by a diagonal prior
+    prior_ini_precision [q] on the components, centred on their starting values `start` - [K, q] with K given (one vector [p + q] per problem), else [B, q] (one vector
+    [p + B q]).  Returns (mean, precision, prior_kind of the result) in check_prior's shapes, or (None, None, None)."""
+    if prior_ini_precision is None:
+        return mean, prec, prior_kind
+    pi = _host(prior_ini_precision).reshape(-1)
+    if pi.size != q or not np.isfinite(pi).all() or (pi < 0).any():
+        raise ValueError("%s: prior_ini_precision is [q] = [%d], finite and >= 0" % (who, q))
+    start = np.asarray(start, dtype=float)
+    n = start.shape[0]
+    if mean is None:
+        mean, prec = np.zeros(p), np.zeros(p)
+    kind = prior_layout(who, mean.shape, prec.shape, p, K, prior_kind)
+    if K is not None:                               # one vector per problem: [K, p + q], the layout named explicitly (K may equal p + q)
+        mean_w = np.concatenate([np.broadcast_to(mean, (K, p)), start], axis=1)
+        if kind == 0:
+            return mean_w, np.concatenate([np.broadcast_to(prec, (K, p)), np.broadcast_to(pi, (K, q))], axis=1), "diagonal"
+        full = np.zeros((K, p + q, p + q))
+        full[:, :p, :p] = prec
+        full[:, np.arange(p, p + q), np.arange(p, p + q)] = pi
+        return mean_w, full, "full"
+    mean_w = np.concatenate([mean, start.reshape(-1)])
+    if kind == 0:
+        return mean_w, np.concatenate([prec, np.tile(pi, n)]), "diagonal"
+    full = np.zeros((p + n * q, p + n * q))
+    full[:p, :p] = prec
+    i = np.arange(p, p + n * q)
+    full[i, i] = np.tile(pi, n)
+    return mean_w, full, "full"
+
+
+def _sample_count(who, B, n_total, has_prior):
+    """the number of samples the loss of a for_* host loop is a mean over: n_total, else B on one rank; under a process group of more than one rank without n_total it
+    is only known after the exchange - None, and with a prior (whose precision has to be divided by it before the first evaluation) a ValueError"""
+    import torch
+    dist = torch.distributed
+    multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    if n_total is not None:
+        return float(n_total), multi
+    if multi and has_prior:
+        raise ValueError("%s: a prior under a process group needs n_total (the precision is divided by the total sample count; no collective is issued for it)" % who)
+    return (None if multi else float(B)), multi
+
+
+def _first_row(ini_state, mask_or_idx, n):
+    """count_observed's first_row for the states of a rollout: all of row 0 where ini_state was given, the estimated components where some are, else none"""
+    if ini_state is not None:
+        return True
+    if mask_or_idx:
+        keep = np.zeros(n, dtype=bool)
+        keep[list(mask_or_idx)] = True
+        return keep
+    return False
+
+
+def inverse_pivoted(A):
+    """(A^-1, ok, pivot_ratio) by the elimination of the device (pdp_lm_covariance_batched): [A | I] reduced with partial pivoting - the largest magnitude of the
+    remaining rows, ties to the lowest row, a NaN counting as the largest -, back-substituted per column; ok is False where a pivot is not > 1e-300 in magnitude;
+    pivot_ratio is the smallest over the largest pivot magnitude"""
+    A = np.array(A, dtype=float)
+    n = A.shape[0]
+    B, ok, small, large = np.eye(n), True, np.inf, 0.0
+    with np.errstate(all="ignore"):
+        for c in range(n):
+            mag = np.abs(A[c:, c])
+            j = c + int(np.argmax(np.where(np.isnan(mag), np.inf, mag)))
+            if j != c:
+                A[[c, j]], B[[c, j]] = A[[j, c]], B[[j, c]]
+            piv = A[c, c]
+            ok = ok and bool(abs(piv) > 1e-300)
+            small, large = (abs(piv) if abs(piv) < small else small), (abs(piv) if abs(piv) > large else large)
+            f = A[c + 1:, c] / piv
+            A[c + 1:, c + 1:] = A[c + 1:, c + 1:] - f[:, None] * A[c, c + 1:]
+            B[c + 1:] = B[c + 1:] - f[:, None] * B[c]
+        for c in range(n - 1, -1, -1):
+            B[c] = B[c] / A[c, c]
+            B[:c] = B[:c] - A[:c, c][:, None] * B[c]
+        return B, ok, float(small / large)
+
+
+def _covariance_host(G, loss, scale_count, noise, n_observed, p, has_prior, who):
+    """Cov of one estimate from its mean-row G (the loss is a sum over scale_count samples divided by it), by the device's rules: cov = scale G^-1 with scale =
+    sigma^2 / scale_count from inverse_pivoted; status 1, NaN and pivot_ratio 0 where a pivot fails or an entry of G or of the result is not finite.
+    dict(cov, std_err, pivot_ratio, status, sigma2) as numpy"""
+    if noise not in ("known", "estimated"):
+        raise ValueError("%s.covariance: noise is 'known' or 'estimated'" % who)
+    sigma2 = 1.0
+    if noise == "estimated":
+        if has_prior:
+            raise ValueError("%s.covariance: noise='estimated' with a prior - the loss of the row contains the prior's share; give the weights as 1 / sigma^2 and "
+                             "use noise='known'" % who)
+        N = float(n_observed)
+        sigma2 = scale_count * loss / (N - p) if N > p else np.nan
+    G = np.asarray(G, dtype=float)
+    inv, ok, ratio = inverse_pivoted(G)
+    with np.errstate(all="ignore"):
+        cov = (sigma2 / scale_count) * inv
+        status = 0 if (ok and np.isfinite(G).all() and np.isfinite(cov).all()) else 1
+        if status:
+            ratio, cov = 0.0, np.full_like(G, np.nan)
+        cov = 0.5 * (cov + cov.T)
+        d = np.diag(cov)
+        std = np.where(d < 0, np.nan, np.sqrt(np.abs(d)))
+    return dict(cov=cov, std_err=std, pivot_ratio=ratio, status=status, sigma2=sigma2)
+
+
 class LMLoop:
     """Levenberg-Marquardt on a sum-of-squares loss.  evaluate(theta [p], numpy) -> (loss, g [p], G [p, p]) as host floats / numpy arrays with g = J'r, G = J'J in the same
     scaling (half the gradient of loss = |r|^2, as the fused unit returns them), or None where theta cannot be evaluated (a solve that did not converge, a singular stage).
     Schedule: the trial point theta - lm_step(g, G, lam) is accepted iff its loss is finite and strictly below the current one; then lam <- max(lam / down, lam_min), else
     lam <- lam * up.  run() ends at max_evals evaluations, at loss <= loss_tol, or when lam > lam_max - no damping the schedule may try improves the loss any more: the fp64
     floor of the problem, reported as results()["stalled"], not raised.
+    prior_mean [p], prior_precision [p] (the diagonal) or [p, p]: a Gaussian prior - (theta - mean)' P (theta - mean) is added to the loss, P (theta - mean) to g and P
+    to G after every evaluation (hence after an all-reduce inside evaluate, identically on every rank); P is taken as given, in the scale of evaluate's loss (the for_*
+    constructors, whose loss is a mean over the samples, divide the natural-unit precision by the sample count).  results()["prior_loss"] is the prior's share of the
+    loss at the accepted point.  covariance(): the error bar of the estimate.
     One shared-parameter problem, driven by the host; many independent problems with their own parameters, decided on the device: BatchedLMLoop (below)."""
 
-    def __init__(self, evaluate, theta0, lam0=1e-3, up=10.0, down=10.0, lam_min=1e-12, lam_max=1e8):
+    def __init__(self, evaluate, theta0, lam0=1e-3, up=10.0, down=10.0, lam_min=1e-12, lam_max=1e8, prior_mean=None, prior_precision=None):
         self.evaluate = evaluate
-        self.theta = np.array(theta0, dtype=float).reshape(-1)
+        self.theta = np.array(_host(theta0), dtype=float).reshape(-1)
+        self.prior_mean, self.prior_precision = check_prior("LMLoop", prior_mean, prior_precision, self.theta.size)
+        self.prior_loss = None                  # the prior's share of the loss at self.theta
+        self.sample_count = 1.0                 # the loss of evaluate is the natural-unit objective divided by this (the for_* constructors set it)
+        self.n_observed = None                  # entries that enter the loss (the for_* constructors set it where it is known without a collective)
         self.lam, self.up, self.down, self.lam_min, self.lam_max = float(lam0), float(up), float(down), float(lam_min), float(lam_max)
         self.current = None                     # (loss, g, G) at self.theta
         self.evaluations = self.rejected = 0
@@ -225,20 +381,30 @@ class LMLoop:
         self.loss_trace, self.parameter_trace, self.lambda_trace = [], [], []
 
     def _eval(self, theta):
+        """((loss, g, G) with the prior added, the prior's share of the loss or None), or None where theta cannot be evaluated"""
         self.evaluations += 1
         r = self.evaluate(theta)
         if r is None:
             return None
-        loss, g, G = float(r[0]), np.asarray(r[1], dtype=float).reshape(-1), np.asarray(r[2], dtype=float)
+        loss, g, G, q = float(r[0]), np.asarray(r[1], dtype=float).reshape(-1), np.asarray(r[2], dtype=float), None
         if not np.isfinite(loss):
             return None
-        return loss, g, G
+        if self.prior_mean is not None:
+            d = np.asarray(theta, dtype=float).reshape(-1) - self.prior_mean
+            P = self.prior_precision
+            Pd = P * d if P.ndim == 1 else P @ d
+            q = float(d @ Pd)
+            loss, g, G = loss + q, g + Pd, G + (np.diag(P) if P.ndim == 1 else P)
+            if not np.isfinite(loss):
+                return None
+        return (loss, g, G), q
 
     def start(self):
         """the evaluation at theta0 (the first accepted point)"""
-        self.current = self._eval(self.theta)
-        if self.current is None:
+        r = self._eval(self.theta)
+        if r is None:
             raise RuntimeError("LMLoop: the initial parameter could not be evaluated")
+        self.current, self.prior_loss = r
         self._record()
 
     def _record(self):
@@ -256,8 +422,8 @@ class LMLoop:
             r = self._eval(trial)
         else:
             r, self.evaluations = None, self.evaluations + 1        # (a trial that cannot be formed still counts against the budget)
-        if r is not None and r[0] < loss:
-            self.theta, self.current = trial, r
+        if r is not None and r[0][0] < loss:
+            self.theta, (self.current, self.prior_loss) = trial, r
             self.lam = max(self.lam / self.down, self.lam_min)
             self._record()
             return True
@@ -278,13 +444,33 @@ class LMLoop:
     def results(self):
         """the reference's result fields over the ACCEPTED points (loss_trace, parameter_trace) + evaluations, rejected, lambda_trace (the damping after each accepted point),
         stalled"""
-        return {"loss_trace": np.array(self.loss_trace), "parameter_trace": np.array(self.parameter_trace).reshape(len(self.parameter_trace), self.theta.size),
-                "lambda_trace": np.array(self.lambda_trace), "evaluations": self.evaluations, "rejected": self.rejected, "stalled": self.stalled,
-                "iterations": len(self.loss_trace)}
+        r = {"loss_trace": np.array(self.loss_trace), "parameter_trace": np.array(self.parameter_trace).reshape(len(self.parameter_trace), self.theta.size),
+             "lambda_trace": np.array(self.lambda_trace), "evaluations": self.evaluations, "rejected": self.rejected, "stalled": self.stalled,
+             "iterations": len(self.loss_trace)}
+        if self.prior_mean is not None:
+            r["prior_loss"] = self.prior_loss
+        return r
+
+    def covariance(self, noise="known", n_observed=None):
+        """The covariance of the estimate at the accepted point, from G = J'J there (with a prior: J'J + P, the posterior precision): dict(cov [p, p] symmetrised, std_err
+        [p], pivot_ratio, status, sigma2) by the rules of the device (inverse_pivoted: the same elimination, pivot rule and threshold; status 1 with NaN and pivot_ratio 0).  noise="known": the weights are 1 / sigma^2,
+        Cov = (count G)^-1 with count the sample count the loss is a mean over (1 for a plain LMLoop(evaluate)).  noise="estimated": sigma^2 = count loss / (N - p) scales
+        it, N = n_observed (the for_* constructors know it on one rank; under a process group it has to be given: NotImplementedError otherwise - no collective is
+        issued here); N <= p gives NaN; with a prior it is a ValueError (the loss contains the prior's share).  Under Huber weights this is the covariance of the final
+        reweighted least-squares problem, not the sandwich estimator."""
+        if self.current is None:
+            raise RuntimeError("LMLoop.covariance: nothing evaluated yet (run() or start() first)")
+        if self.sample_count is None:
+            raise NotImplementedError("LMLoop.covariance: the total sample count is only known to the exchange (a process group without n_total): give n_total")
+        N = n_observed if n_observed is not None else self.n_observed
+        if noise == "estimated" and self.prior_mean is None and N is None:
+            raise NotImplementedError("LMLoop.covariance(noise='estimated'): the number of observed entries is not known here (a plain evaluate, or samples spread over "
+                                      "a process group): give n_observed")
+        return _covariance_host(self.current[2], self.current[0], self.sample_count, noise, N, self.theta.size, self.prior_mean is not None, "LMLoop")
 
     @classmethod
     def for_irl(cls, mdl, demo_x, demo_u, theta0, tol=1e-10, max_iter=300, n_total=None, ini_state=None, skip_missing=False, weights_state=None, weights_control=None,
-                huber_delta=None, **kw):
+                huber_delta=None, prior_mean=None, prior_precision=None, **kw):
         """The IRL drivers' problem: mdl a runtime.ModelLib of an OC model, demo_x [B, T+1, n], demo_u [B, T, m] the demonstrations (this rank's shard under
         torch.distributed; n_total as in parallel.allreduce_mean_packed), theta0 [p] shared by all of them.  evaluate(theta) solves every demonstration's OC problem
         (oc_solve_ms: the first cold, later ones warm from COPIES of the last accepted solution, so that a rejected trial cannot damage it), runs the fused unit once with
@@ -297,7 +483,13 @@ class LMLoop:
         state the solves would start from is a ValueError here, before any launch.
         weights_state ([n], [T+1, n] or [B, T+1, n]), weights_control ([m], [T, m] or [B, T, m]), both >= 0 with 0 = not observed, huber_delta (> 0): the row the loop
         minimises carries the weighted / Huber loss, its exact half derivative and the Gauss-Newton matrix of iteratively reweighted least squares
-        (pdp_oc_pdp_grad_wls_batched); the loop itself is unchanged.  They are checked once, here, and the weights stay on the device."""
+        (pdp_oc_pdp_grad_wls_batched); the loop itself is unchanged.  They are checked once, here, and the weights stay on the device.
+        prior_mean, prior_precision: LMLoop's prior in NATURAL units - the objective is the sum over all demonstrations of their losses + (theta - mean)' P (theta -
+        mean); the loop minimises it divided by the total number of demonstrations (n_total, else B; under a process group n_total is then required).  The loop knows the
+        number of observed entries (covariance(noise="estimated")) on one rank: every entry of demo_u and of rows 1 .. T of demo_x with a weight > 0 that is not a NaN
+        under skip_missing, and row 0 of demo_x where ini_state was given (else its residual is identically zero)."""
+        prior_mean, prior_precision = check_prior("LMLoop.for_irl", prior_mean, prior_precision, mdl.p)
+        count, multi = _sample_count("LMLoop.for_irl", int(np.shape(demo_u)[0]), n_total, prior_mean is not None)
         if skip_missing:                            # judged on what the caller gave (a host array is not moved to the device first)
             _refuse_nan_start("LMLoop.for_irl", demo_x, ini_state, "demo_x")
         wls = _oc_wls_keywords(mdl, demo_u, weights_state, weights_control, huber_delta)
@@ -324,12 +516,17 @@ class LMLoop:
             state["trial"] = (s["state"], s["control"], s["costate"])
             return float(row[p]), row[:p].copy(), row[p + 1:].reshape(p, p).copy()
 
-        loop = cls(evaluate, theta0, **kw)
+        loop = cls(evaluate, theta0, prior_mean=prior_mean, prior_precision=None if prior_precision is None else prior_precision / count, **kw)
         loop.on_accept = lambda: state.update(accepted=state["trial"])
+        loop.sample_count = count
+        if not multi:
+            loop.n_observed = int((rt.count_observed(demo_x, weights_state, skip_missing, _first_row(ini_state, None, mdl.n)) +
+                                   rt.count_observed(demo_u, weights_control, skip_missing)).sum().item())
         return loop
 
     @classmethod
-    def for_sysid(cls, mdl, inputs, states, theta0, n_total=None, ini_state=None, skip_missing=False, estimate_ini=None, weights=None, huber_delta=None, **kw):
+    def for_sysid(cls, mdl, inputs, states, theta0, n_total=None, ini_state=None, skip_missing=False, estimate_ini=None, weights=None, huber_delta=None,
+                  prior_mean=None, prior_precision=None, prior_ini_precision=None, **kw):
         """The SysID drivers' problem (Examples/SysID/*/..._PDP.py) as nonlinear least squares: mdl a runtime.ModelLib of a SysID model, inputs [B, T, m] and states
         [B, T+1, n] the recorded data (this rank's shard under torch.distributed; n_total as in parallel.allreduce_mean_packed), theta0 [p] shared by all trajectories.
         evaluate(theta) is ONE launch - sysid_step with gauss_newton=True: loss, gradient and G = J'J from the sensitivity tiles of the fused kernel - and hands the packed
@@ -345,11 +542,22 @@ class LMLoop:
         ValueError: many recordings, or recordings spread over ranks, are BatchedLMLoop.for_sysid(estimate_ini=)'s problems, one theta per trajectory.
         weights ([n], [T+1, n] or [B, T+1, n], >= 0, 0 = not observed), huber_delta (> 0): the row the loop minimises carries the weighted / Huber loss, its exact half
         derivative and the Gauss-Newton matrix of iteratively reweighted least squares (ModelLib.sysid_step, pdp_sysid_step_wls_batched); the loop itself is unchanged.
-        They are checked once, here."""
+        They are checked once, here.
+        prior_mean, prior_precision ([p]; [p] or [p, p]): LMLoop's prior on theta in NATURAL units - the objective is the sum over all trajectories of their losses +
+        (theta - mean)' P (theta - mean); the loop minimises it divided by the total number of trajectories (n_total, else B; under a process group n_total is then
+        required).  prior_ini_precision [q] (with estimate_ini): a diagonal prior on the estimated components of every recording's initial state, centred on their
+        starting values - it fills the diagonal of the x0_b blocks of the arrow system.  The loop knows the number of observed entries (covariance(noise="estimated")) on
+        one rank: rows 1 .. T of `states` with a weight > 0 that are not a NaN under skip_missing, and of row 0 everything where ini_state was given, else the estimated
+        components (the residual of the others is identically zero)."""
         idx, mask = rt.ini_indices(estimate_ini, mdl.n)
+        prior_mean, prior_precision = check_prior("LMLoop.for_sysid", prior_mean, prior_precision, mdl.p)
+        if prior_ini_precision is not None and not idx:
+            raise ValueError("LMLoop.for_sysid: prior_ini_precision needs estimate_ini")
+        count, multi = _sample_count("LMLoop.for_sysid", int(np.shape(inputs)[0]), n_total, prior_mean is not None)
         wls = _wls_keywords(mdl, inputs, weights, huber_delta)
         if idx:                                     # (nothing selected is estimate_ini=None)
-            return cls._for_sysid_ini(mdl, inputs, states, theta0, n_total, ini_state, skip_missing, idx, mask=mask, wls=wls, **kw)
+            return cls._for_sysid_ini(mdl, inputs, states, theta0, n_total, ini_state, skip_missing, idx, mask=mask, wls=wls, weights=weights,
+                                      prior=(prior_mean, prior_precision, prior_ini_precision), **kw)
         if wls and skip_missing:
             _refuse_nan_start("LMLoop.for_sysid", states, ini_state, "states")
         from . import parallel
@@ -371,10 +579,14 @@ class LMLoop:
                 return None
             return float(row[p]), row[:p].copy(), row[p + 1:].reshape(p, p).copy()
 
-        return cls(evaluate, theta0, **kw)
+        loop = cls(evaluate, theta0, prior_mean=prior_mean, prior_precision=None if prior_precision is None else prior_precision / count, **kw)
+        loop.sample_count = count
+        if not multi:
+            loop.n_observed = int(rt.count_observed(states, weights, skip_missing, _first_row(ini_state, None, mdl.n)).sum().item())
+        return loop
 
     @classmethod
-    def _for_sysid_ini(cls, mdl, inputs, states, theta0, n_total, ini_state, skip_missing, idx, mask=0, wls=None, **kw):
+    def _for_sysid_ini(cls, mdl, inputs, states, theta0, n_total, ini_state, skip_missing, idx, mask=0, wls=None, weights=None, prior=(None, None, None), **kw):
         if skip_missing:                            # an estimated component still needs a finite starting value
             _refuse_nan_start("LMLoop.for_sysid", states, ini_state, "states")
         torch = rt.torch_cuda()
@@ -417,8 +629,11 @@ class LMLoop:
             ini[:, idx] = v[p:].reshape(B, q)
             return v[:p].copy(), ini
 
-        loop = cls(evaluate, th0, **kw)
+        mean, prec, _ = _prior_with_ini("LMLoop.for_sysid", prior[0], prior[1], prior[2] if (prior[2] is not None or prior[0] is None) else np.zeros(q), p, q, ini0[:, idx])
+        loop = cls(evaluate, th0, prior_mean=mean, prior_precision=None if prec is None else prec / float(B), **kw)
         loop.split = split
+        loop.sample_count = float(B)
+        loop.n_observed = int(rt.count_observed(states, weights, skip_missing, _first_row(ini_state, idx, mdl.n)).sum().item())
         return loop
 
 
@@ -448,11 +663,21 @@ class BatchedLMLoop:
     The schedule is LMLoop's, per problem (runtime.lm_update / include/pdp_hip_lm.h: the exact order, and the two differences - a damped matrix that is exactly singular is
     a rejected trial, not a least-squares solve; pivoted elimination).  A problem whose initial point cannot be evaluated is FAILED (LMLoop raises there) and the others go
     on.  step() is one evaluation and one update launch; run() reads counters[1] - problems still START or ACTIVE, one 8-byte copy - every poll_every launches.
+    prior_mean ([p] or [K, p]), prior_precision ([p] or [K, p]: the diagonal; [p, p] or [K, p, p]: full; [p, p] where K == p), in NATURAL units: the objective of a problem
+    is the sum over its S samples of their losses + (theta - mean)' P (theta - mean).  Where K == p the shape [p, p] does not say which of the two it is: prior_kind
+    ("diagonal" or "full") is then required (a ValueError otherwise).  The loop minimises that divided by S - the mean row, as without a prior - and hands
+    P / S to the update kernel, which adds the prior inside the same launch (pdp_lm_update_prior_batched); losses, traces and loss_tol are those of the augmented mean
+    row, results()["prior_loss"] the prior's share of it.  A non-finite entry, a negative diagonal entry or an asymmetric matrix is a ValueError before any launch.
+    Without a prior step() launches pdp_lm_update_batched as before.  covariance(): K error bars for K estimates, one more launch.
     Made for many problems with few samples each; one problem with thousands of samples is LMLoop's job.  Not graph-captured; samples of one problem do not span ranks
     (independent problems shard over ranks without any collective)."""
 
     def __init__(self, evaluate_rows, theta0, samples_per_problem=1, lam0=1e-3, up=10.0, down=10.0, lam_min=1e-12, lam_max=1e8, max_evals=50, loss_tol=0.0, trace_len=None,
-                 K=None):
+                 K=None, prior_mean=None, prior_precision=None, prior_kind=None):
+        shape = tuple(int(v) for v in np.shape(theta0))
+        K_ = shape[0] if len(shape) == 2 else (int(K) if K is not None else 1)
+        mean, prec = check_prior("BatchedLMLoop", prior_mean, prior_precision, shape[-1], K_, prior_kind)
+        diagonal_per_problem = mean is not None and prec.ndim == 2 and prior_layout("BatchedLMLoop", mean.shape, prec.shape, shape[-1], K_, prior_kind) == 0
         torch = rt.torch_cuda()
         f64, i32 = dict(dtype=torch.float64, device="cuda"), dict(dtype=torch.int32, device="cuda")
         th = rt.dev(theta0)
@@ -476,12 +701,24 @@ class BatchedLMLoop:
         self.counters = torch.tensor([0, K], dtype=torch.int64, device="cuda")
         self.after_update = None                # called after every update launch (for_irl: keeps the accepted solutions as the next warm start, on the device)
         self.launches = 0
+        self.prior_mean = self.prior_precision = self.prior_loss = None
+        self.prior_diagonal_per_problem = diagonal_per_problem      # (the layout is fixed here, not read from the shape again: K may equal p)
+        if mean is not None:
+            self.prior_mean, self.prior_precision = rt.dev(mean), rt.dev(prec / float(S))      # (the kernel's scale: that of the mean row)
+            self.prior_loss = torch.full((K,), float("nan"), **f64)
+        self.n_observed = None                  # int64 [K] on the device: entries that enter the loss of each problem (the for_* constructors set it)
 
     def step(self):
         """one evaluation of all trial points and one update launch; nothing is read back"""
         rows, bad = self.evaluate_rows(self.trial)
-        rt.lm_update(rows, self.theta, self.trial, self.lam, self.current, self.state, self.evaluations, self.rejected, self.accepted, self.counters, bad=bad,
-                     accepted_now=self.accepted_now, loss_trace=self.loss_trace, lambda_trace=self.lambda_trace, parameter_trace=self.parameter_trace, **self.schedule)
+        if self.prior_mean is None:
+            rt.lm_update(rows, self.theta, self.trial, self.lam, self.current, self.state, self.evaluations, self.rejected, self.accepted, self.counters, bad=bad,
+                         accepted_now=self.accepted_now, loss_trace=self.loss_trace, lambda_trace=self.lambda_trace, parameter_trace=self.parameter_trace, **self.schedule)
+        else:
+            rt.lm_update_prior(rows, self.theta, self.trial, self.lam, self.current, self.state, self.evaluations, self.rejected, self.accepted, self.counters, bad=bad,
+                               accepted_now=self.accepted_now, loss_trace=self.loss_trace, lambda_trace=self.lambda_trace, parameter_trace=self.parameter_trace,
+                               prior_mean=self.prior_mean, prior_precision=self.prior_precision, prior_loss=self.prior_loss,
+                               diagonal_per_problem=self.prior_diagonal_per_problem, **self.schedule)
         if self.after_update is not None:
             self.after_update()
         self.launches += 1
@@ -503,19 +740,51 @@ class BatchedLMLoop:
 
     def results(self):
         """host copies (one synchronisation), per problem: loss_trace, parameter_trace, lambda_trace (lists of K arrays over the ACCEPTED points, cut at the trace length),
-        evaluations, rejected, accepted [K], state (names), theta [K, p], loss [K] (of theta; NaN for a FAILED problem); launches"""
+        evaluations, rejected, accepted [K], state (names), theta [K, p], loss [K] (of theta; NaN for a FAILED problem); launches; with a prior also prior_loss [K], the
+        prior's share of loss"""
         acc = self.accepted.cpu().numpy()
         n = np.minimum(acc, self.loss_trace.shape[1])
         lt, pt, lmt = self.loss_trace.cpu().numpy(), self.parameter_trace.cpu().numpy(), self.lambda_trace.cpu().numpy()
         state = self.state.cpu().numpy()
         loss = np.where(acc > 0, self.current[:, self.p].cpu().numpy(), np.nan)
-        return {"loss_trace": [lt[k, :n[k]].copy() for k in range(self.K)], "parameter_trace": [pt[k, :n[k]].copy() for k in range(self.K)],
-                "lambda_trace": [lmt[k, :n[k]].copy() for k in range(self.K)], "evaluations": self.evaluations.cpu().numpy(), "rejected": self.rejected.cpu().numpy(),
-                "accepted": acc, "state": [rt.LM_STATES[v] for v in state], "theta": self.theta.cpu().numpy(), "loss": loss, "launches": self.launches}
+        r = {"loss_trace": [lt[k, :n[k]].copy() for k in range(self.K)], "parameter_trace": [pt[k, :n[k]].copy() for k in range(self.K)],
+             "lambda_trace": [lmt[k, :n[k]].copy() for k in range(self.K)], "evaluations": self.evaluations.cpu().numpy(), "rejected": self.rejected.cpu().numpy(),
+             "accepted": acc, "state": [rt.LM_STATES[v] for v in state], "theta": self.theta.cpu().numpy(), "loss": loss, "launches": self.launches}
+        if self.prior_loss is not None:
+            r["prior_loss"] = self.prior_loss.cpu().numpy()
+        return r
+
+    def covariance(self, noise="known", n_observed=None):
+        """K error bars for K estimates, one launch (pdp_lm_covariance_batched) on `current` - G = J'J of the mean row at the accepted points (with a prior: J'J + P / S,
+        the posterior precision).  noise="known": the weights are 1 / sigma^2, Cov = (S G)^-1.  noise="estimated": sigma^2_k = S loss_k / (N_k - p) scales it; N_k is
+        the number of observed entries of problem k (n_observed [K], or what for_sysid / for_irl counted); N_k <= p gives NaN for that problem; with a prior it is a
+        ValueError (the loss of the row contains the prior's share).  Returns host arrays: cov [K, p, p] (symmetrised (C + C') / 2), std_err [K, p], pivot_ratio [K]
+        (smallest over largest pivot magnitude of the elimination: the diagnosis of a partially identifiable problem), status [K] (0, or 1 where G is singular to the
+        elimination or not finite: NaN, pivot_ratio 0), sigma2 [K] (1 for "known").  Under Huber weights this is the covariance of the final reweighted least-squares
+        problem, not the sandwich estimator."""
+        torch = rt.torch_cuda()
+        if noise not in ("known", "estimated"):
+            raise ValueError("BatchedLMLoop.covariance: noise is 'known' or 'estimated'")
+        S, p = float(self.S), self.p
+        if noise == "estimated":
+            if self.prior_mean is not None:
+                raise ValueError("BatchedLMLoop.covariance: noise='estimated' with a prior - the loss of the row contains the prior's share; give the weights as "
+                                 "1 / sigma^2 and use noise='known'")
+            N = n_observed if n_observed is not None else self.n_observed
+            if N is None:
+                raise ValueError("BatchedLMLoop.covariance(noise='estimated'): the number of observed entries per problem is not known: give n_observed [K]")
+            N = torch.as_tensor(N, device="cuda").to(torch.float64).reshape(-1).expand(self.K)
+            sigma2 = torch.where(N > p, S * self.current[:, p] / (N - p), torch.full_like(N, float("nan")))
+        else:
+            sigma2 = torch.ones((self.K,), dtype=torch.float64, device="cuda")
+        out = rt.lm_covariance(self.current, (sigma2 / S).contiguous())
+        cov = 0.5 * (out["cov"] + out["cov"].transpose(1, 2))
+        return {"cov": cov.cpu().numpy(), "std_err": out["std_err"].cpu().numpy(), "pivot_ratio": out["pivot_ratio"].cpu().numpy(), "status": out["status"].cpu().numpy(),
+                "sigma2": sigma2.cpu().numpy()}
 
     @classmethod
     def for_sysid(cls, mdl, inputs, states, theta0, samples_per_problem=1, ini_state=None, skip_missing=False, estimate_ini=None, weights=None, huber_delta=None,
-                  **kw):
+                  prior_ini_precision=None, **kw):
         """One SysID problem per group of samples_per_problem consecutive trajectories: inputs [K S, T, m], states [K S, T+1, n], theta0 [K, p] or [p].  An evaluation is
         ONE launch of mdl.sysid_step(gauss_newton=True) with the trial points as per-sample parameters; a sample is bad where its row holds a non-finite entry (formed on
         the device).  skip_missing, ini_state: as in LMLoop.for_sysid (a NaN in the initial state under skip_missing is a ValueError before any launch).
@@ -524,13 +793,19 @@ class BatchedLMLoop:
         pdp_sysid_step_gn_ini_batched: theta is read from the trial rows in place (row stride W), the estimated components are copied from the trial rows into a
         persistent x0 buffer at a fixed address - one small device copy, no host synchronisation; the update launch is pdp_lm_update_batched's with W as its p.
         loop.split(theta [K, W]) -> (theta [K, p], ini_state [K, n]).
-        weights, huber_delta: as in LMLoop.for_sysid - checked once here, then every evaluation is one launch of pdp_sysid_step_wls_batched."""
+        weights, huber_delta: as in LMLoop.for_sysid - checked once here, then every evaluation is one launch of pdp_sysid_step_wls_batched.
+        prior_mean, prior_precision (keywords of the class, in natural units, on theta: [p] or [K, p]; [p], [K, p], [p, p] or [K, p, p]) pass through;
+        prior_ini_precision [q] (with estimate_ini): a diagonal prior on the estimated components of x0, centred on their starting values - mean and precision are
+        extended to the W = p + q vector.  The loop counts the observed entries per problem (covariance(noise="estimated")) by LMLoop.for_sysid's rule."""
+        if prior_ini_precision is not None and not rt.ini_indices(estimate_ini, mdl.n)[0]:
+            raise ValueError("BatchedLMLoop.for_sysid: prior_ini_precision needs estimate_ini")
         wls = _wls_keywords(mdl, inputs, weights, huber_delta)
         if skip_missing:                            # judged on what the caller gave (a host array is not moved to the device first)
             _refuse_nan_start("BatchedLMLoop.for_sysid", states, ini_state, "states")
         idx, mask = rt.ini_indices(estimate_ini, mdl.n)
         if idx:                                     # (nothing selected is estimate_ini=None; an estimated component still needs the finite starting value checked above)
-            return cls._for_sysid_ini(mdl, inputs, states, theta0, samples_per_problem, ini_state, skip_missing, idx, mask, wls=wls, **kw)
+            return cls._for_sysid_ini(mdl, inputs, states, theta0, samples_per_problem, ini_state, skip_missing, idx, mask, wls=wls, weights=weights,
+                                      prior_ini_precision=prior_ini_precision, **kw)
         torch = rt.torch_cuda()
         inputs, states = rt.dev(inputs), rt.dev(states)
         B, T, S = int(inputs.shape[0]), int(inputs.shape[1]), int(samples_per_problem)
@@ -545,10 +820,13 @@ class BatchedLMLoop:
                 out = mdl.sysid_step(inputs, states, trial, gauss_newton=True, skip_missing=skip_missing, ini_state=x0, buffers=bufs)
             return out["packed_gn"], (~torch.isfinite(out["packed_gn"])).any(dim=1).to(torch.int32)
 
-        return cls(evaluate_rows, theta0, samples_per_problem=S, K=B // S, **kw)
+        loop = cls(evaluate_rows, theta0, samples_per_problem=S, K=B // S, **kw)
+        loop.n_observed = rt.count_observed(states, weights, skip_missing, _first_row(ini_state, None, mdl.n)).view(B // S, S).sum(dim=1)
+        return loop
 
     @classmethod
-    def _for_sysid_ini(cls, mdl, inputs, states, theta0, samples_per_problem, ini_state, skip_missing, idx, mask, wls=None, **kw):
+    def _for_sysid_ini(cls, mdl, inputs, states, theta0, samples_per_problem, ini_state, skip_missing, idx, mask, wls=None, weights=None, prior_ini_precision=None,
+                       prior_mean=None, prior_precision=None, prior_kind=None, **kw):
         torch = rt.torch_cuda()
         inputs, states = rt.dev(inputs), rt.dev(states)
         K, T, p, q = int(inputs.shape[0]), int(inputs.shape[1]), mdl.p, len(idx)
@@ -584,8 +862,13 @@ class BatchedLMLoop:
             ini[:, idx] = v[:, p:]
             return v[:, :p].copy(), ini
 
-        loop = cls(evaluate_rows, th, samples_per_problem=1, K=K, **kw)
+        mean, prec = check_prior("BatchedLMLoop.for_sysid", prior_mean, prior_precision, p, K, prior_kind)
+        mean, prec, prior_kind = _prior_with_ini("BatchedLMLoop.for_sysid", mean, prec, prior_ini_precision, p, q, ini0[:, idx], K=K, prior_kind=prior_kind)
+        if mean is not None and prior_ini_precision is None:        # a prior on theta alone: the components of x0 get none
+            mean, prec, prior_kind = _prior_with_ini("BatchedLMLoop.for_sysid", mean, prec, np.zeros(q), p, q, ini0[:, idx], K=K, prior_kind=prior_kind)
+        loop = cls(evaluate_rows, th, samples_per_problem=1, K=K, prior_mean=mean, prior_precision=prec, prior_kind=prior_kind, **kw)
         loop.split = split
+        loop.n_observed = rt.count_observed(states, weights, skip_missing, _first_row(ini_state, idx, mdl.n))
         return loop
 
     @classmethod
@@ -596,7 +879,9 @@ class BatchedLMLoop:
         last accepted solutions) and runs the fused unit once with gauss_newton=True.  A sample is bad under LMLoop.for_irl's three conditions: its solve did not
         converge, reported trouble, or the unit set a status bit.  After the update the accepted solutions are refreshed where the launch accepted the sample's problem
         (torch.where on accepted_now: no host decision).  skip_missing, ini_state: as in LMLoop.for_irl.
-        weights_state, weights_control, huber_delta: as in LMLoop.for_irl - checked once here, then every evaluation's unit is one launch of pdp_oc_pdp_grad_wls_batched."""
+        weights_state, weights_control, huber_delta: as in LMLoop.for_irl - checked once here, then every evaluation's unit is one launch of pdp_oc_pdp_grad_wls_batched.
+        prior_mean, prior_precision (keywords of the class, in natural units) pass through; the loop counts the observed entries per problem
+        (covariance(noise="estimated")) by LMLoop.for_irl's rule."""
         if skip_missing:
             _refuse_nan_start("BatchedLMLoop.for_irl", demo_x, ini_state, "demo_x")
         wls = _oc_wls_keywords(mdl, demo_u, weights_state, weights_control, huber_delta)
@@ -619,6 +904,8 @@ class BatchedLMLoop:
             return out["packed_gn"], bad.to(torch.int32)
 
         loop = cls(evaluate_rows, theta0, samples_per_problem=S, K=B // S, **kw)
+        loop.n_observed = (rt.count_observed(demo_x, weights_state, skip_missing, _first_row(ini_state, None, mdl.n)) +
+                           rt.count_observed(demo_u, weights_control, skip_missing)).view(B // S, S).sum(dim=1)
 
         def keep_accepted():
             now = (loop.accepted_now != 0)[:, None, None]

@@ -58,6 +58,11 @@ class PdpLmState(C.Structure):
                                           "lambda_trace", "parameter_trace")] + [("trace_len", C.c_int64), ("counters", C.c_void_p)]
 
 
+class PdpLmPrior(C.Structure):                     # include/pdp_hip_lm_prior.h
+    _fields_ = [("mean", C.c_void_p), ("precision", C.c_void_p), ("kind", C.c_int32), ("mean_kstride", C.c_int64), ("precision_kstride", C.c_int64),
+                ("prior_loss", C.c_void_p)]
+
+
 class PdpPolicy(C.Structure):
     _fields_ = [("kind", C.c_int), ("n_pivots", C.c_int), ("pivots", C.c_double * 16), ("n_layers", C.c_int), ("sizes", C.c_int * 16), ("n_basis", C.c_int),
                 ("table", C.c_void_p)]
@@ -74,6 +79,7 @@ MODEL_SYMBOLS = ["pdp_model_get_info", "pdp_oc_rollout_batched", "pdp_oc_rollout
                  "pdp_cp_step_workspace_bytes", "pdp_cp_step_batched", "pdp_sysid_integrate_batched", "pdp_sysid_auxsys_batched", "pdp_sysid_step_batched",
                  "pdp_sysid_step_workspace_bytes", "pdp_sysid_step_ws_batched"]
 CORE_EXT_SYMBOLS = ["pdp_lm_update_batched"]             # declared in the extension header include/pdp_hip_lm.h, exported by libpdp_hip.so
+CORE_LM_PRIOR_SYMBOLS = ["pdp_lm_update_prior_batched", "pdp_lm_covariance_batched"]      # include/pdp_hip_lm_prior.h, exported by libpdp_hip.so
 MODEL_EXT_SYMBOLS = ["pdp_sysid_step_gn_batched"]        # declared in the extension headers (include/pdp_hip_sysid_gn.h): include/pdp_hip.h is pinned at its entry points
 
 MODEL_INI_SYMBOLS = ["pdp_sysid_step_gn_ini_batched"]   # include/pdp_hip_sysid_ini.h: one list per extension header
@@ -118,6 +124,10 @@ def load_core():
                                              [C.c_int64, C.c_void_p, C.c_void_p]
         lib.pdp_lm_update_batched.restype = C.c_int
         lib.pdp_lm_update_batched.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PdpLmSchedule), C.POINTER(PdpLmState), C.c_void_p]
+        lib.pdp_lm_update_prior_batched.restype = C.c_int
+        lib.pdp_lm_update_prior_batched.argtypes = lib.pdp_lm_update_batched.argtypes[:-1] + [C.POINTER(PdpLmPrior), C.c_void_p]
+        lib.pdp_lm_covariance_batched.restype = C.c_int
+        lib.pdp_lm_covariance_batched.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
         _core = lib
     return _core
 
@@ -146,17 +156,13 @@ def gd_update(loss, grad, lr, theta, dtheta, counters, status=None, converged=No
 LM_STATES = ["START", "ACTIVE", "CONVERGED", "STALLED", "BUDGET", "FAILED"]          # PDP_LM_* of include/pdp_hip_lm.h
 
 
-def lm_update(rows, theta, trial, lam, current, state, evaluations, rejected, accepted, counters, up=10.0, down=10.0, lam_min=1e-12, lam_max=1e8, loss_tol=0.0,
-              max_evals=50, bad=None, accepted_now=None, loss_trace=None, lambda_trace=None, parameter_trace=None):
-    """One Levenberg-Marquardt update of K independent problems, one launch (pdp_lm_update_batched, include/pdp_hip_lm.h: the semantics).  rows [K S, p + 1 + p p] =
-    grad | loss | G per sample, evaluated at `trial` (rows may be strided: a view of a wider buffer); the state at fixed device addresses, initialised by the caller:
-    theta [K, p], trial [K S, p], lam [K], current [K, p + 1 + p p] fp64; state, evaluations, rejected, accepted int32 [K]; counters int64 [2] = launches done |
-    problems still START or ACTIVE (initialised 0 | K).  Optional: bad int32 [K S], accepted_now int32 [K S], loss_trace / lambda_trace [K, L], parameter_trace [K, L, p]."""
+def _lm_structs(theta, trial, lam, current, state, evaluations, rejected, accepted, counters, up, down, lam_min, lam_max, loss_tol, max_evals, bad, accepted_now,
+                loss_trace, lambda_trace, parameter_trace):
+    """the checks of the state buffers of lm_update / lm_update_prior and the two structs of include/pdp_hip_lm.h: (PdpLmSchedule, PdpLmState)"""
     torch = torch_cuda()
     K, p = theta.shape
     assert trial.dim() == 2 and trial.shape[1] == p and trial.shape[0] % K == 0
     S, w = trial.shape[0] // K, p + 1 + p * p
-    assert rows.dtype == torch.float64 and rows.dim() == 2 and tuple(rows.shape) == (K * S, w) and rows.stride(1) == 1 and rows.stride(0) >= w
     for t, shape in ((theta, (K, p)), (trial, (K * S, p)), (lam, (K,)), (current, (K, w))):
         assert t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
     for t in (state, evaluations, rejected, accepted):
@@ -170,7 +176,104 @@ def lm_update(rows, theta, trial, lam, current, state, evaluations, rejected, ac
     sch = PdpLmSchedule(float(up), float(down), float(lam_min), float(lam_max), float(loss_tol), int(max_evals))
     st = PdpLmState(*[t.data_ptr() if t is not None else None for t in (theta, trial, lam, current, state, evaluations, rejected, accepted, accepted_now, loss_trace,
                                                                          lambda_trace, parameter_trace)], L, counters.data_ptr())
+    return sch, st
+
+
+def lm_update(rows, theta, trial, lam, current, state, evaluations, rejected, accepted, counters, up=10.0, down=10.0, lam_min=1e-12, lam_max=1e8, loss_tol=0.0,
+              max_evals=50, bad=None, accepted_now=None, loss_trace=None, lambda_trace=None, parameter_trace=None):
+    """One Levenberg-Marquardt update of K independent problems, one launch (pdp_lm_update_batched, include/pdp_hip_lm.h: the semantics).  rows [K S, p + 1 + p p] =
+    grad | loss | G per sample, evaluated at `trial` (rows may be strided: a view of a wider buffer); the state at fixed device addresses, initialised by the caller:
+    theta [K, p], trial [K S, p], lam [K], current [K, p + 1 + p p] fp64; state, evaluations, rejected, accepted int32 [K]; counters int64 [2] = launches done |
+    problems still START or ACTIVE (initialised 0 | K).  Optional: bad int32 [K S], accepted_now int32 [K S], loss_trace / lambda_trace [K, L], parameter_trace [K, L, p]."""
+    torch = torch_cuda()
+    sch, st = _lm_structs(theta, trial, lam, current, state, evaluations, rejected, accepted, counters, up, down, lam_min, lam_max, loss_tol, max_evals, bad, accepted_now,
+                          loss_trace, lambda_trace, parameter_trace)
+    K, p = theta.shape
+    S, w = trial.shape[0] // K, p + 1 + p * p
+    assert rows.dtype == torch.float64 and rows.dim() == 2 and tuple(rows.shape) == (K * S, w) and rows.stride(1) == 1 and rows.stride(0) >= w
     check(load_core().pdp_lm_update_batched(K, S, p, ptr(rows), int(rows.stride(0)), ptr(bad), C.byref(sch), C.byref(st), current_stream_ptr()), "pdp_lm_update_batched")
+
+
+def lm_prior_shapes(prior_mean, prior_precision, K, p, diagonal_per_problem=False):
+    """(kind, mean_kstride, precision_kstride) of a prior from its shapes (tuples): mean [p] or [K, p]; precision [p] (diagonal, shared), [p, p] (full, shared), [K, p]
+    (diagonal, per problem) or [K, p, p] (full, per problem).  Where K == p, [p, p] is the shared full matrix unless diagonal_per_problem says otherwise.  Anything else
+    is a ValueError."""
+    ms, ps = tuple(int(v) for v in prior_mean), tuple(int(v) for v in prior_precision)
+    if ms not in ((p,), (K, p)):
+        raise ValueError("prior_mean is [p] = [%d] or [K, p] = [%d, %d], got %s" % (p, K, p, list(ms)))
+    table = {(p,): (0, 0), (p, p): (1, 0), (K, p, p): (1, p * p)}
+    if diagonal_per_problem:
+        table[(K, p)] = (0, p)
+    table.setdefault((K, p), (0, p))
+    if ps not in table:
+        raise ValueError("prior_precision is [p], [p, p], [K, p] or [K, p, p] with K = %d, p = %d, got %s" % (K, p, list(ps)))
+    kind, pks = table[ps]
+    return kind, (p if len(ms) == 2 else 0), pks
+
+
+def lm_update_prior(rows, theta, trial, lam, current, state, evaluations, rejected, accepted, counters, up=10.0, down=10.0, lam_min=1e-12, lam_max=1e8, loss_tol=0.0,
+                    max_evals=50, bad=None, accepted_now=None, loss_trace=None, lambda_trace=None, parameter_trace=None, prior_mean=None, prior_precision=None,
+                    prior_loss=None, diagonal_per_problem=False):
+    """lm_update with a Gaussian prior (x - mean)' P (x - mean) on the unknowns of every problem, added to the MEAN row inside the update launch
+    (pdp_lm_update_prior_batched, include/pdp_hip_lm_prior.h: the semantics).  prior_mean [p] or [K, p]; prior_precision [p] / [K, p] (the diagonal) or [p, p] /
+    [K, p, p] (full; where K == p, [p, p] is the shared full matrix unless diagonal_per_problem is set), shared by all problems or one per problem by its shape; prior_loss [K] or None: the prior's share of the loss at the accepted
+    point.  All fp64, contiguous, on the device.  Without prior_mean and prior_precision the launch is pdp_lm_update_batched's, through the new entry point."""
+    torch = torch_cuda()
+    assert rows.dtype == torch.float64 and rows.dim() == 2 and rows.stride(1) == 1
+    sch, st = _lm_structs(theta, trial, lam, current, state, evaluations, rejected, accepted, counters, up, down, lam_min, lam_max, loss_tol, max_evals, bad, accepted_now,
+                          loss_trace, lambda_trace, parameter_trace)
+    K, p = theta.shape
+    S, w = trial.shape[0] // K, p + 1 + p * p
+    assert tuple(rows.shape) == (K * S, w) and rows.stride(0) >= w
+    prior = None
+    if prior_mean is not None or prior_precision is not None:
+        if prior_mean is None or prior_precision is None:
+            raise ValueError("lm_update_prior: prior_mean and prior_precision go together")
+        kind, mks, pks = lm_prior_shapes(prior_mean.shape, prior_precision.shape, K, p, diagonal_per_problem)
+        for t in (prior_mean, prior_precision):
+            assert t.dtype == torch.float64 and t.is_contiguous() and t.is_cuda
+        assert prior_loss is None or (prior_loss.dtype == torch.float64 and prior_loss.is_contiguous() and tuple(prior_loss.shape) == (K,))
+        prior = C.byref(PdpLmPrior(prior_mean.data_ptr(), prior_precision.data_ptr(), kind, mks, pks, prior_loss.data_ptr() if prior_loss is not None else None))
+    else:
+        assert prior_loss is None
+    check(load_core().pdp_lm_update_prior_batched(K, S, p, ptr(rows), int(rows.stride(0)), ptr(bad), C.byref(sch), C.byref(st), prior, current_stream_ptr()),
+          "pdp_lm_update_prior_batched")
+
+
+def lm_covariance(rows, scale=None):
+    """The covariance of K estimates, one launch (pdp_lm_covariance_batched): rows [K, p + 1 + p p] = grad | loss | G per problem (BatchedLMLoop.current; rows may be
+    strided), scale [K] or None (1).  Returns dict(cov [K, p, p] = scale G^-1 as computed - not symmetrised, std_err [K, p], pivot_ratio [K], status int32 [K]: 0, or 1
+    where G is singular to the elimination or holds a non-finite entry - cov and std_err of that problem NaN, pivot_ratio 0), device tensors."""
+    torch = torch_cuda()
+    assert rows.dtype == torch.float64 and rows.dim() == 2 and rows.stride(1) == 1 and rows.is_cuda
+    K, w = (int(v) for v in rows.shape)
+    p = int(round((-1.0 + (1.0 + 4.0 * (w - 1)) ** 0.5) / 2.0))
+    assert p >= 1 and p + 1 + p * p == w and rows.stride(0) >= w, "rows is [K, p + 1 + p p]"
+    assert scale is None or (scale.dtype == torch.float64 and scale.is_contiguous() and tuple(scale.shape) == (K,) and scale.is_cuda)
+    cov, std = torch.empty((K, p, p), dtype=torch.float64, device="cuda"), torch.empty((K, p), dtype=torch.float64, device="cuda")
+    ratio, status = torch.empty((K,), dtype=torch.float64, device="cuda"), torch.empty((K,), dtype=torch.int32, device="cuda")
+    check(load_core().pdp_lm_covariance_batched(K, p, ptr(rows), int(rows.stride(0)), ptr(scale), ptr(cov), ptr(std), ptr(ratio), ptr(status), current_stream_ptr()),
+          "pdp_lm_covariance_batched")
+    return dict(cov=cov, std_err=std, pivot_ratio=ratio, status=status)
+
+
+def count_observed(data, weights=None, skip_missing=False, first_row=True):
+    """The number of entries of data [B, R, n] that enter a weighted / partially observed sum-of-squares loss, per trajectory: int64 [B] on the device of `data` (a torch
+    expression: CPU tensors included).  An entry counts iff its weight is > 0 (weights None: 1; [n], [R, n] or [B, R, n]) and, under skip_missing, it is not NaN.
+    first_row: True - row 0 counts like the others; False - it does not (a state row 0 that is the rollout's own initial state: its residual is identically zero); a bool
+    mask [n] - row 0 counts in these components only (the estimated components of the initial state)."""
+    import torch
+    data = torch.as_tensor(data)
+    B, R, n = (int(v) for v in data.shape)
+    on = torch.ones((B, R, n), dtype=torch.bool, device=data.device)
+    if weights is not None:
+        on = on & (torch.as_tensor(weights, device=data.device) > 0).expand(B, R, n)
+    if skip_missing:
+        on = on & ~torch.isnan(data)
+    if first_row is not True:
+        keep = torch.zeros(n, dtype=torch.bool, device=data.device) if first_row is False else torch.as_tensor(first_row, dtype=torch.bool, device=data.device).reshape(n)
+        on = torch.cat([on[:, :1] & keep, on[:, 1:]], dim=1)
+    return on.sum(dim=(1, 2))
 
 
 def torch_cuda():

@@ -11,7 +11,10 @@ Exit status 1 on any difference.  What a host-only change of csrc/*.hip is check
 --rename REGEX REPL: re.sub on every symbol name of both sides before they are compared - for a change that gives a kernel template one more parameter with a default,
 which changes the mangled name of the instantiations it leaves alone and must change nothing else of them.  --allow-added: symbols that only B has are counted, not
 failed - what a change that ADDS instantiations is checked with (profiles/sysid_gn_code_object_diff.txt).  What follows the last kernel of a code object (the
-disassembler's `...` for padding, the footer of the metadata) belongs to no kernel and is dropped: a kernel that is the last one in A need not be in B."""
+disassembler's `...` for padding, the footer of the metadata) belongs to no kernel and is dropped: a kernel that is the last one in A need not be in B.
+--ignore-trailing-nops: the run of `s_nop 0` behind the last instruction of a symbol - the assembler's padding up to the alignment of the next function of the same
+section, behind an s_endpgm or an unconditional branch and never executed - is dropped on both sides: for a kernel that becomes a template instantiation, which gets a
+section of its own and with it no such padding (profiles/lm_prior_code_object_diff.txt)."""
 import glob
 import os
 import re
@@ -22,6 +25,7 @@ from pdp_amd import codegen  # noqa: E402
 
 
 RENAME = None           # (compiled regex, replacement)
+IGNORE_TRAILING_NOPS = False
 
 
 def renamed(name):
@@ -44,6 +48,10 @@ def symbols(dis):
         else:
             after_getpc = 2 if ins.startswith("s_getpc_b64") else 0
         cur.append(ins)
+    if IGNORE_TRAILING_NOPS:
+        for body in out.values():
+            while body and body[-1] == "s_nop 0":
+                body.pop()
     return out, masked
 
 
@@ -90,5 +98,6 @@ if __name__ == "__main__":
         RENAME = (re.compile(argv[i + 1]), argv[i + 2])
         del argv[i:i + 3]
     allow = "--allow-added" in argv
-    argv = [a for a in argv if a != "--allow-added"]
+    IGNORE_TRAILING_NOPS = "--ignore-trailing-nops" in argv
+    argv = [a for a in argv if a not in ("--allow-added", "--ignore-trailing-nops")]
     sys.exit(main(argv[0], argv[1], allow))
