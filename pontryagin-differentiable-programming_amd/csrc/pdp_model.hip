@@ -2,6 +2,7 @@
 // include/pdp_hip.h.  Compiled once per model with -DPDP_MODEL_HEADER="generated/<name>.h" (codegen.py).
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <tuple>
 #include "../../include/pdp_hip.h"
 #include "../../include/pdp_hip_sysid_gn.h"
 #include "../../include/pdp_hip_sysid_ini.h"
@@ -107,6 +108,28 @@ int oc_predict_rec(int B, int T, const double* dth, int dtb, const float* rec, d
 template <class F>
 inline int with_fused_mode(int mode, F&& f) { return with_int<PDP_FUSED_RIC, PDP_FUSED_COT, PDP_FUSED_GN, PDP_FUSED_MISS, PDP_FUSED_GN_MISS, PDP_FUSED_PLAIN>(mode, f); }
 
+// The launch of the fused OC unit, shared by its entry points (oc_pdp, oc_pdp_wls): PDP_E_SIZE where the horizon's staging exceeds the LDS, else the kernel variant
+// with its geometry.  XW: the extra words of the forward row in the caller's layout.  run(kernel, workgroups, threads, LDS bytes) launches with the caller's
+// arguments; pair(K, go) and wave(go) call go(kernel) with the caller's instantiation of oc_pdp_fused3_kernel for K trajectories per workgroup / of
+// oc_pdp_fused_kernel.
+// Kernel variants (environment PDP_FUSED_VARIANT overrides the default): 3 = runner / evaluator wave pair per trajectory, four
+// trajectories per 512-thread workgroup (pdp_fused3_kernels.h) - the default wherever it applies (n > 4, rollout staging within the
+// pool area); 1 = one wavefront per trajectory (systems with n <= 4, long horizons)
+template <class Mdl, int XW, class Run, class Pair, class Wave>
+int oc_pdp_launch(int B, int T, Run&& run, Pair&& pair, Wave&& wave) {
+    const size_t lds = fused_lds_bytes<Mdl, XW>(T);
+    if (lds > 160 * 1024) return PDP_E_SIZE;
+    static const int variant = env_int("PDP_FUSED_VARIANT", PDP_FUSED_DEFAULT_VARIANT);
+    if constexpr (Mdl::NX > 4) {
+        if (variant == 3 && fused3_ok<Mdl, XW>(T)) {
+            static const int tpw_env = env_int("PDP_FUSED_TPW", 0);          // (overrides the batch rule)
+            const int tpw = tpw_env ? tpw_env : traj_per_workgroup(B, device_cu_count(), 4);
+            return with_int<1, 2, 4>(tpw, [&](auto K) { return pair(K, [&](auto kern) { return run(kern, (B + K() - 1) / K(), 128 * K(), K() * 40 * 1024); }); });
+        }
+    }
+    return wave([&](auto kern) { return run(kern, B, 64, lds); });
+}
+
 template <class Mdl>
 int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const double* th, int tb, const double* dx, const double* du, double* x,
            double* lam, double* loss, double* grad, double* dxdp, double* dudp, double* ric, float* prec, int32_t* status, void* ws, int64_t wsb, void* st) {
@@ -120,8 +143,6 @@ int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const dou
         if (miss && (cot || sens)) return PDP_E_ARG;
         if (!(flags & PDP_OC_GIVEN_TRAJ) && !x0) return PDP_E_ARG;
         if (wsb < oc_ws_bytes<Mdl>(B, T)) return PDP_E_ARG;
-        const size_t lds = fused_lds_bytes<Mdl>(T);
-        if (lds > 160 * 1024) return PDP_E_SIZE;
         // the instantiation (a kernel's MODE): with records - and, fused3 only, with any sensitivity output - the one that writes them with buffer stores
         auto mode = [&](bool rec) {
             return rec ? PDP_FUSED_RIC : (cot ? PDP_FUSED_COT : (gn ? (miss ? PDP_FUSED_GN_MISS : PDP_FUSED_GN) : (miss ? PDP_FUSED_MISS : PDP_FUSED_PLAIN)));
@@ -129,25 +150,14 @@ int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const dou
         auto run = [&](auto kern, int wgs, int threads, size_t lds_bytes) {
             return launch(kern, dim3(wgs), dim3(threads), lds_bytes, S(st), B, T, flags, x0, u, th, tb, dx, du, x, lam, loss, grad, dxdp, dudp, status, (double*)ws, ric, prec);
         };
-        // Kernel variants (environment PDP_FUSED_VARIANT overrides the default): 3 = runner / evaluator wave pair per trajectory, four
-        // trajectories per 512-thread workgroup (pdp_fused3_kernels.h) - the default wherever it applies (n > 4, rollout staging within the
-        // pool area); 1 = one wavefront per trajectory (systems with n <= 4, long horizons)
-        static const int variant = env_int("PDP_FUSED_VARIANT", PDP_FUSED_DEFAULT_VARIANT);
-        if constexpr (Mdl::NX > 4) {
-            if (variant == 3 && fused3_ok<Mdl>(T)) {
-                static const int tpw_env = env_int("PDP_FUSED_TPW", 0);          // (overrides the batch rule)
-                const int tpw = tpw_env ? tpw_env : traj_per_workgroup(B, device_cu_count(), 4);
-                return with_fused_mode(mode(sens), [&](auto MODE) {
-                    return with_int<1, 2, 4>(tpw, [&](auto K) { return run(oc_pdp_fused3_kernel<Mdl, K(), MODE()>, (B + K() - 1) / K(), 128 * K(), K() * 40 * 1024); });
-                });
-            }
-        }
-        return with_fused_mode(mode(records), [&](auto MODE) { return run(oc_pdp_fused_kernel<Mdl, MODE()>, B, 64, lds); });
+        return oc_pdp_launch<Mdl, 0>(B, T, run,
+                                     [&](auto K, auto&& go) { return with_fused_mode(mode(sens), [&](auto MODE) { return go(oc_pdp_fused3_kernel<Mdl, K(), MODE()>); }); },
+                                     [&](auto&& go) { return with_fused_mode(mode(records), [&](auto MODE) { return go(oc_pdp_fused_kernel<Mdl, MODE()>); }); });
     } else { return Mdl::KIND == PDP_KIND_OC ? PDP_E_SIZE : PDP_E_MODE; }
 }
 
-// pdp_oc_pdp_grad_wls_batched (include/pdp_hip_oc_wls.h): the PDP_FUSED_GN_W instantiations, chosen as oc_pdp chooses - same variant, PDP_FUSED_TPW and fused3_ok logic,
-// the last two evaluated with the mode's own (longer) layout.  The checks come in the order of the header.
+// pdp_oc_pdp_grad_wls_batched (include/pdp_hip_oc_wls.h): the PDP_FUSED_GN_W instantiations, chosen by oc_pdp_launch with the mode's own (longer) layout.  The checks
+// come in the order of the header.
 template <class Mdl>
 int oc_pdp_wls(int B, int T, int flags, const double* x0, const double* u, const double* th, int tb, const double* dx, const double* du, const double* wx, int64_t wxs,
                const double* wu, int64_t wus, double delta, double* x, double* lam, double* loss, double* packed, int32_t* status, void* ws, int64_t wsb, void* st) {
@@ -161,8 +171,6 @@ int oc_pdp_wls(int B, int T, int flags, const double* x0, const double* u, const
         if (!(flags & PDP_OC_GIVEN_TRAJ) && !x0) return PDP_E_ARG;
         if (B <= 0 || T <= 0) return PDP_E_ARG;
         if (wsb < oc_ws_bytes<Mdl>(B, T)) return PDP_E_ARG;
-        const size_t lds = fused_lds_bytes<Mdl, XW>(T);
-        if (lds > 160 * 1024) return PDP_E_SIZE;
         // without weights the kernels load the demonstrations in their place (readable blocks of the same shape) and select 1.0
         const OcWls a{wx ? wx : dx, wu ? wu : du, wx ? (long long)wxs : (long long)(T + 1) * Mdl::NX, wu ? (long long)wus : (long long)T * Mdl::NU, delta,
                       (wx ? 1 : 0) | (wu ? 2 : 0), (flags & PDP_GRAD_SKIP_MISSING) ? 1 : 0};
@@ -172,17 +180,8 @@ int oc_pdp_wls(int B, int T, int flags, const double* x0, const double* u, const
             return launch(kern, dim3(wgs), dim3(threads), lds_bytes, S(st), B, T, flags, x0, u, th, tb, dx, du, x, lam, loss, packed, no_sens, no_sens, status, (double*)ws,
                           no_sens, no_rec, a);
         };
-        static const int variant = env_int("PDP_FUSED_VARIANT", PDP_FUSED_DEFAULT_VARIANT);
-        if constexpr (Mdl::NX > 4) {
-            if (variant == 3 && fused3_ok<Mdl, XW>(T)) {
-                static const int tpw_env = env_int("PDP_FUSED_TPW", 0);          // (overrides the batch rule)
-                const int tpw = tpw_env ? tpw_env : traj_per_workgroup(B, device_cu_count(), 4);
-                return with_int<1, 2, 4>(tpw, [&](auto K) {
-                    return run(oc_pdp_fused3_kernel<Mdl, K(), PDP_FUSED_GN_W, OcWls>, (B + K() - 1) / K(), 128 * K(), K() * 40 * 1024);
-                });
-            }
-        }
-        return run(oc_pdp_fused_kernel<Mdl, PDP_FUSED_GN_W, OcWls>, B, 64, lds);
+        return oc_pdp_launch<Mdl, XW>(B, T, run, [&](auto K, auto&& go) { return go(oc_pdp_fused3_kernel<Mdl, K(), PDP_FUSED_GN_W, OcWls>); },
+                                      [&](auto&& go) { return go(oc_pdp_fused_kernel<Mdl, PDP_FUSED_GN_W, OcWls>); });
     } else { return Mdl::KIND == PDP_KIND_OC ? PDP_E_SIZE : PDP_E_MODE; }
 }
 
@@ -627,50 +626,41 @@ int sysid_step(int B, int T, const double* u, const double* xobs, const double* 
                          : (xgiven ? sysid_rows_given<Mdl>(T, wgs_env > 0 ? wgs_env : SYSID_GIVEN_WGS<MODE>, EXTRA) : sysid_rows<Mdl>(B, T, cus, EXTRA));
         const size_t lds = sizeof(double) * (size_t)sysid_slice<Mdl>(T, rows, xgiven != nullptr, EXTRA);
         if (lds > 150 * 1024) return PDP_E_SIZE;
+        // the kernels' trailing arguments, a tuple whose TYPE is fixed by MODE: the kernels' `Ini...` is spelled from its element types, never from a call's arguments
+        const auto trailing = [&] {
+            if constexpr (MODE == PDP_SYSID_PLAIN) return std::tuple<>{};
+            else if constexpr (WLS && INI) return std::tuple<const double*, unsigned, SysidWls>{x0, ini_mask, wls};
+            else if constexpr (WLS) return std::tuple<const double*, SysidWls>{x0, wls};
+            else if constexpr (INI) return std::tuple<const double*, unsigned>{x0, ini_mask};
+            else return std::tuple<const double*>{x0};
+        }();
         // PDP_SYSID_VARIANT: 2 = rollout wave + sensitivity wave per trajectory (pdp_cp_pair_kernels.h), the default; 1 = one wavefront per trajectory
         static const int variant = env_int("PDP_SYSID_VARIANT", 2);
-        // the pair pays while SIMDs would idle (B = 256, T = 200: 0.105 -> 0.072 ms); once every SIMD has a trajectory the two waves only share what one had
-        // (B = 1024: 0.0667 against 0.0685 ms, profiles/r03_pair_pipeline.txt) - the one-wave kernel stays for those batches
-        if (variant == 2 && B <= 2 * cus && !xgiven) {
-            const int slice = sysid_slice<Mdl>(T, Mdl::CHUNK, false, EXTRA), tpw = traj_per_workgroup(B, cus, 2);
-            if (slice * tpw * (int)sizeof(double) <= 160 * 1024)
-                return with_int<1, 2>(tpw, [&](auto K) {
-                    if constexpr (MODE == PDP_SYSID_PLAIN)
-                    return launch(sysid_step2_kernel<Mdl, NT, K()>, dim3((B + K() - 1) / K()), dim3(128 * K()), slice * K() * sizeof(double), S(st), B, T, u, xobs, th, tb, loss,
-                                  grad, slice);
-                    else if constexpr (MODE == PDP_SYSID_GN_W)
-                        return launch(sysid_step2_kernel<Mdl, NT, K(), MODE, const double*, SysidWls>, dim3((B + K() - 1) / K()), dim3(128 * K()),
-                                      slice * K() * sizeof(double), S(st), B, T, u, xobs, th, tb, loss, grad, slice, x0, wls);
-                    else if constexpr (MODE == PDP_SYSID_GN_W_INI)
-                        return launch(sysid_step2_kernel<Mdl, NT, K(), MODE, const double*, unsigned, SysidWls>, dim3((B + K() - 1) / K()), dim3(128 * K()),
-                                      slice * K() * sizeof(double), S(st), B, T, u, xobs, th, tb, loss, grad, slice, x0, ini_mask, wls);
-                    else if constexpr (INI)
-                        return launch(sysid_step2_kernel<Mdl, NT, K(), MODE, const double*, unsigned>, dim3((B + K() - 1) / K()), dim3(128 * K()),
-                                      slice * K() * sizeof(double), S(st), B, T, u, xobs, th, tb, loss, grad, slice, x0, ini_mask);
-                    else
-                        return launch(sysid_step2_kernel<Mdl, NT, K(), MODE, const double*>, dim3((B + K() - 1) / K()), dim3(128 * K()), slice * K() * sizeof(double), S(st),
-                                      B, T, u, xobs, th, tb, loss, grad, slice, x0);
-                });
-        }
-        return with_bool(xgiven != nullptr, [&](auto GIVEN) {
-            if constexpr (MODE == PDP_SYSID_PLAIN)
-            return launch(sysid_step_kernel<Mdl, NT, GIVEN()>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad, rows, xgiven);
-            else if constexpr (MODE == PDP_SYSID_GN_W)
-                return launch(sysid_step_kernel<Mdl, NT, GIVEN(), MODE, const double*, SysidWls>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad, rows, xgiven,
-                              x0, wls);
-            else if constexpr (MODE == PDP_SYSID_GN_W_INI)
-                return launch(sysid_step_kernel<Mdl, NT, GIVEN(), MODE, const double*, unsigned, SysidWls>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad,
-                              rows, xgiven, x0, ini_mask, wls);
-            else if constexpr (INI)
-                return launch(sysid_step_kernel<Mdl, NT, GIVEN(), MODE, const double*, unsigned>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad, rows,
-                              xgiven, x0, ini_mask);
-            else
-                return launch(sysid_step_kernel<Mdl, NT, GIVEN(), MODE, const double*>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad, rows, xgiven, x0);
-        });
+        return std::apply([&](auto... extra) {
+            // the pair pays while SIMDs would idle (B = 256, T = 200: 0.105 -> 0.072 ms); once every SIMD has a trajectory the two waves only share what one had
+            // (B = 1024: 0.0667 against 0.0685 ms, profiles/r03_pair_pipeline.txt) - the one-wave kernel stays for those batches
+            if (variant == 2 && B <= 2 * cus && !xgiven) {
+                const int slice = sysid_slice<Mdl>(T, Mdl::CHUNK, false, EXTRA), tpw = traj_per_workgroup(B, cus, 2);
+                if (slice * tpw * (int)sizeof(double) <= 160 * 1024)
+                    return with_int<1, 2>(tpw, [&](auto K) {
+                        return launch(sysid_step2_kernel<Mdl, NT, K(), MODE, decltype(extra)...>, dim3((B + K() - 1) / K()), dim3(128 * K()), slice * K() * sizeof(double),
+                                      S(st), B, T, u, xobs, th, tb, loss, grad, slice, extra...);
+                    });
+            }
+            return with_bool(xgiven != nullptr, [&](auto GIVEN) {
+                return launch(sysid_step_kernel<Mdl, NT, GIVEN(), MODE, decltype(extra)...>, dim3(B), dim3(64), lds, S(st), B, T, u, xobs, th, tb, loss, grad, rows, xgiven,
+                              extra...);
+            });
+        }, trailing);
     } else { return Mdl::KIND == PDP_KIND_SYSID ? PDP_E_SIZE : PDP_E_MODE; }
 }
 
 template <class Mdl> int nnz_path() { return Mdl::PATH_NVAR; }
+
+// what the Gauss-Newton entry points of SysID.step check first: sizes, the pointers every one of them needs, no flag but PDP_GRAD_SKIP_MISSING
+inline bool sysid_gn_args_ok(int B, int T, const double* u, const double* x_obs, const double* theta, const double* loss, const double* packed, int flags) {
+    return B > 0 && T > 0 && u && x_obs && theta && loss && packed && !(flags & ~PDP_GRAD_SKIP_MISSING);
+}
 
 }  // namespace
 
@@ -773,14 +763,14 @@ int pdp_sysid_step_ws_batched(int B, int T, const double* u, const double* x_obs
 }
 int pdp_sysid_step_gn_batched(int B, int T, const double* u, const double* x_obs, const double* x0, const double* theta, int tb, int flags, double* loss, double* packed,
                               void* workspace, int64_t workspace_bytes, void* stream) {
-    if (B <= 0 || T <= 0 || !u || !x_obs || !theta || !loss || !packed || (flags & ~PDP_GRAD_SKIP_MISSING)) return PDP_E_ARG;
+    if (!sysid_gn_args_ok(B, T, u, x_obs, theta, loss, packed, flags)) return PDP_E_ARG;
     return (flags & PDP_GRAD_SKIP_MISSING) ? sysid_step<PdpModel, PDP_SYSID_GN_MISS>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0)
                                            : sysid_step<PdpModel, PDP_SYSID_GN>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0);
 }
 int pdp_sysid_step_gn_ini_batched(int B, int T, const double* u, const double* x_obs, const double* x0, int ini_mask, const double* theta, int tb, int flags, double* loss,
                                   double* packed, void* workspace, int64_t workspace_bytes, void* stream) {
     if (ini_mask == 0) return pdp_sysid_step_gn_batched(B, T, u, x_obs, x0, theta, tb, flags, loss, packed, workspace, workspace_bytes, stream);
-    if (B <= 0 || T <= 0 || !u || !x_obs || !theta || !loss || !packed || (flags & ~PDP_GRAD_SKIP_MISSING)) return PDP_E_ARG;
+    if (!sysid_gn_args_ok(B, T, u, x_obs, theta, loss, packed, flags)) return PDP_E_ARG;
     if (PdpModel::NX < 32 && ((unsigned)ini_mask >> PdpModel::NX) != 0) return PDP_E_ARG;       // a mask bit >= n
     const unsigned mask = (unsigned)ini_mask;
     return (flags & PDP_GRAD_SKIP_MISSING)
@@ -790,7 +780,7 @@ int pdp_sysid_step_gn_ini_batched(int B, int T, const double* u, const double* x
 int pdp_sysid_step_wls_batched(int B, int T, const double* u, const double* x_obs, const double* x0, int ini_mask, const double* weights, int64_t weights_bstride,
                                double huber_delta, const double* theta, int tb, int flags, double* loss, double* packed, void* workspace, int64_t workspace_bytes,
                                void* stream) {
-    if (B <= 0 || T <= 0 || !u || !x_obs || !theta || !loss || !packed || (flags & ~PDP_GRAD_SKIP_MISSING)) return PDP_E_ARG;
+    if (!sysid_gn_args_ok(B, T, u, x_obs, theta, loss, packed, flags)) return PDP_E_ARG;
     if (!(huber_delta > 0.0)) return PDP_E_ARG;                                                  // (<= 0 and NaN)
     if (weights_bstride != 0 && weights_bstride != (int64_t)(T + 1) * PdpModel::NX) return PDP_E_ARG;
     if (PdpModel::NX < 32 && ((unsigned)ini_mask >> PdpModel::NX) != 0) return PDP_E_ARG;       // a mask bit >= n

@@ -198,12 +198,16 @@ def arrow_normal_equations(rows, p, q):
     return out
 
 
-def _refuse_nan_start(who, data, ini_state, name):
-    """skip_missing: a NaN in the initial state that would be used - ini_state, else data[:, 0] - is a ValueError before any launch.  Judged on what the caller gave (a
-    host array is not moved to the device first)."""
-    first = ini_state if ini_state is not None else (data if hasattr(data, "data_ptr") else np.asarray(data, dtype=float))[:, 0]
-    if bool(first.isnan().any()) if hasattr(first, "data_ptr") else bool(np.isnan(np.asarray(first, dtype=float)).any()):
-        raise ValueError("%s: skip_missing=True and the initial state (%s) holds a NaN: give ini_state [B, n]" % (who, "%s[:, 0]" % name if ini_state is None else "ini_state"))
+def bad_irl_samples(solve, out):
+    """The samples of an IRL evaluation that must not be used, bool [B] on the device (no synchronisation): the solve did not converge, it set a status bit other than
+    the informational ones, or the fused unit set a status bit.  solve: the dict of oc_solve_ms, out: the dict of the unit."""
+    informational = 128 | 512 | 1024 | 2048          # PDP_MS_RESTORED, PDP_MS_PREDICT_REJECTED, PDP_MS_SOC, PDP_MS_WATCHDOG
+    return (solve["converged_flags"] == 0) | ((solve["status"] & ~informational) != 0) | (out["status"] != 0)
+
+
+def non_finite_rows(rows):
+    """bool [B] on the device of `rows` [B, w]: the rows that hold a non-finite entry (a diverged rollout: SysID has no status word)"""
+    return (~rows.isfinite()).any(dim=1)
 
 
 def _host(a):
@@ -491,26 +495,21 @@ class LMLoop:
         prior_mean, prior_precision = check_prior("LMLoop.for_irl", prior_mean, prior_precision, mdl.p)
         count, multi = _sample_count("LMLoop.for_irl", int(np.shape(demo_u)[0]), n_total, prior_mean is not None)
         if skip_missing:                            # judged on what the caller gave (a host array is not moved to the device first)
-            _refuse_nan_start("LMLoop.for_irl", demo_x, ini_state, "demo_x")
-        wls = _oc_wls_keywords(mdl, demo_u, weights_state, weights_control, huber_delta)
+            rt.refuse_nan_initial_state("LMLoop.for_irl", demo_x, ini_state, "demo_x")
+        rows, held = mdl.oc_rows_prepared(demo_x, demo_u, skip_missing, weights_state, weights_control, huber_delta)
         from . import parallel
-        demo_x, demo_u = rt.dev(demo_x), rt.dev(demo_u)
+        demo_x, demo_u = held["demo_x"], held["demo_u"]
         B, T, p = int(demo_u.shape[0]), int(demo_u.shape[1]), mdl.p
         assert demo_x.shape == (B, T + 1, mdl.n) and demo_u.shape == (B, T, mdl.m)
         x0 = (demo_x[:, 0] if ini_state is None else rt.dev(ini_state).reshape(B, mdl.n)).contiguous()
-        bufs, state = {}, {"accepted": None, "trial": None}
-        informational = 128 | 512 | 1024 | 2048          # PDP_MS_RESTORED, PDP_MS_PREDICT_REJECTED, PDP_MS_SOC, PDP_MS_WATCHDOG
+        state = {"accepted": None, "trial": None}
 
         def evaluate(theta):
             # no decision on this rank's own flags: solve and unit always run, the flags are counted on the device and travel with the rows, so that every rank issues
             # the same collective and takes the same decision (parallel.mean_row_checked) - and the host reads the device once
             s = mdl.oc_solve_ms(x0, theta, T, tol=tol, max_iter=max_iter, warm=state["accepted"])
-            if wls:
-                out = mdl._oc_pdp_wls_dev(s["control"], *mdl._theta(theta, B), demo_x, demo_u, None, s["state"], s["costate"], bufs, skip_missing, *wls)
-            else:
-                out = mdl.oc_pdp_grad(s["control"], theta, demo_x, demo_u, x=s["state"], lam=s["costate"], gauss_newton=True, skip_missing=skip_missing, buffers=bufs)
-            bad = (s["converged_flags"] == 0) | ((s["status"] & ~informational) != 0) | (out["status"] != 0)
-            row = parallel.mean_row_checked(out["packed_gn"], bad, n_total)
+            out = rows(s["control"], theta, x=s["state"], lam=s["costate"])
+            row = parallel.mean_row_checked(out["packed_gn"], bad_irl_samples(s, out), n_total)
             if row is None:
                 return None
             state["trial"] = (s["state"], s["control"], s["costate"])
@@ -549,32 +548,24 @@ class LMLoop:
         starting values - it fills the diagonal of the x0_b blocks of the arrow system.  The loop knows the number of observed entries (covariance(noise="estimated")) on
         one rank: rows 1 .. T of `states` with a weight > 0 that are not a NaN under skip_missing, and of row 0 everything where ini_state was given, else the estimated
         components (the residual of the others is identically zero)."""
-        idx, mask = rt.ini_indices(estimate_ini, mdl.n)
+        idx, _ = rt.ini_indices(estimate_ini, mdl.n)
         prior_mean, prior_precision = check_prior("LMLoop.for_sysid", prior_mean, prior_precision, mdl.p)
         if prior_ini_precision is not None and not idx:
             raise ValueError("LMLoop.for_sysid: prior_ini_precision needs estimate_ini")
         count, multi = _sample_count("LMLoop.for_sysid", int(np.shape(inputs)[0]), n_total, prior_mean is not None)
-        wls = _wls_keywords(mdl, inputs, weights, huber_delta)
+        rows, held = mdl.sysid_rows_prepared(inputs, states, skip_missing, ini_state, idx, weights, huber_delta, own_x0=bool(idx), who="LMLoop.for_sysid",
+                                             data_name="states")
         if idx:                                     # (nothing selected is estimate_ini=None)
-            return cls._for_sysid_ini(mdl, inputs, states, theta0, n_total, ini_state, skip_missing, idx, mask=mask, wls=wls, weights=weights,
+            return cls._for_sysid_ini(mdl, rows, held, theta0, n_total, ini_state, skip_missing, idx, weights=weights,
                                       prior=(prior_mean, prior_precision, prior_ini_precision), **kw)
-        if wls and skip_missing:
-            _refuse_nan_start("LMLoop.for_sysid", states, ini_state, "states")
         from . import parallel
-        torch = rt.torch_cuda()
-        inputs, states = rt.dev(inputs), rt.dev(states)
+        inputs, states = held["u"], held["xobs"]
         B, T, p = int(inputs.shape[0]), int(inputs.shape[1]), mdl.p
         assert states.shape == (B, T + 1, mdl.n) and inputs.shape == (B, T, mdl.m)
-        x0 = rt.dev(ini_state).reshape(B, mdl.n).contiguous() if ini_state is not None else None
-        bufs = {}
 
         def evaluate(theta):
-            if wls:
-                out = mdl._sysid_step_wls_dev(inputs, states, *mdl._theta(theta, B), skip_missing, x0, bufs, [], 0, *wls)
-            else:
-                out = mdl.sysid_step(inputs, states, theta, gauss_newton=True, skip_missing=skip_missing, ini_state=x0, buffers=bufs)
-            bad = (~torch.isfinite(out["packed_gn"])).any(dim=1)
-            row = parallel.mean_row_checked(out["packed_gn"], bad, n_total)                # (a bad row makes the point None before its sums are read)
+            out = rows(theta)
+            row = parallel.mean_row_checked(out["packed_gn"], non_finite_rows(out["packed_gn"]), n_total)      # (a bad row makes the point None before its sums are read)
             if row is None:
                 return None
             return float(row[p]), row[:p].copy(), row[p + 1:].reshape(p, p).copy()
@@ -586,14 +577,12 @@ class LMLoop:
         return loop
 
     @classmethod
-    def _for_sysid_ini(cls, mdl, inputs, states, theta0, n_total, ini_state, skip_missing, idx, mask=0, wls=None, weights=None, prior=(None, None, None), **kw):
-        if skip_missing:                            # an estimated component still needs a finite starting value
-            _refuse_nan_start("LMLoop.for_sysid", states, ini_state, "states")
+    def _for_sysid_ini(cls, mdl, rows, held, theta0, n_total, ini_state, skip_missing, idx, weights=None, prior=(None, None, None), **kw):
+        """rows, held: the prepared evaluation (checked: an estimated component still needs a finite starting value) with initial states of its own"""
         torch = rt.torch_cuda()
-        inputs, states = rt.dev(inputs), rt.dev(states)
+        inputs, states, x0, cols = held["u"], held["xobs"], held["x0"], held["columns"]      # x0 persistent: the estimated components are written into it
         B, T, p, q = int(inputs.shape[0]), int(inputs.shape[1]), mdl.p, len(idx)
         assert states.shape == (B, T + 1, mdl.n) and inputs.shape == (B, T, mdl.m)
-        x0 = (rt.dev(ini_state).reshape(B, mdl.n) if ini_state is not None else states[:, 0]).contiguous().clone()      # persistent: the estimated components are written into it
         N = p + B * q
         dist = torch.distributed
         if n_total is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
@@ -608,16 +597,11 @@ class LMLoop:
             th0 = np.concatenate([th0, ini0[:, idx].reshape(-1)])
         if th0.size != N:
             raise ValueError("LMLoop.for_sysid(estimate_ini=): theta0 is [p] = [%d] or [p + B q] = [%d], got %d" % (p, N, th0.size))
-        cols = torch.tensor(idx, dtype=torch.int64, device="cuda")
-        bufs = {}
 
         def evaluate(vector):
             v = rt.dev(np.ascontiguousarray(vector, dtype=float))                         # one copy to the device: theta and the estimated components
             x0.index_copy_(1, cols, v[p:].view(B, q))
-            if wls:
-                out = mdl._sysid_step_wls_dev(inputs, states, *mdl._theta(v[:p], B), skip_missing, x0, bufs, idx, mask, *wls)
-            else:
-                out = mdl.sysid_step(inputs, states, v[:p], gauss_newton=True, skip_missing=skip_missing, ini_state=x0, buffers=bufs, estimate_ini=idx)
+            out = rows(v[:p])
             flat = arrow_normal_equations(out["packed_gn"], p, q).cpu().numpy()            # one copy to the host
             if not np.isfinite(flat).all():         # every entry of every row is in there, summed or as it is: a non-finite row shows
                 return None
@@ -635,25 +619,6 @@ class LMLoop:
         loop.sample_count = float(B)
         loop.n_observed = int(rt.count_observed(states, weights, skip_missing, _first_row(ini_state, idx, mdl.n)).sum().item())
         return loop
-
-
-def _oc_wls_keywords(mdl, demo_u, weights_state, weights_control, huber_delta):
-    """The weights_state / weights_control / huber_delta keywords of the for_irl constructors, checked ONCE and with the weights on the device: () when none is given,
-    else the last five arguments of ModelLib._oc_pdp_wls_dev."""
-    if weights_state is None and weights_control is None and huber_delta is None:
-        return ()
-    shape = tuple(np.shape(demo_u))
-    wx, wxs, wu, wus, delta = rt.oc_wls_arguments(weights_state, weights_control, huber_delta, int(shape[0]), int(shape[1]), mdl.n, mdl.m)
-    return (rt.dev(wx).contiguous() if wx is not None else None, wxs, rt.dev(wu).contiguous() if wu is not None else None, wus, delta)
-
-
-def _wls_keywords(mdl, inputs, weights, huber_delta):
-    """The weights / huber_delta keywords of the for_sysid constructors, checked ONCE and with the weights on the device: () when neither is given, else the last three
-    arguments of ModelLib._sysid_step_wls_dev - (weights on the device or None, their batch stride, delta)."""
-    if weights is None and huber_delta is None:
-        return ()
-    w, wbs, delta = rt.wls_arguments(weights, huber_delta, int(inputs.shape[0]), int(inputs.shape[1]), mdl.n)
-    return (rt.dev(w).contiguous() if w is not None else None, wbs, delta)
 
 
 class BatchedLMLoop:
@@ -799,62 +764,45 @@ class BatchedLMLoop:
         extended to the W = p + q vector.  The loop counts the observed entries per problem (covariance(noise="estimated")) by LMLoop.for_sysid's rule."""
         if prior_ini_precision is not None and not rt.ini_indices(estimate_ini, mdl.n)[0]:
             raise ValueError("BatchedLMLoop.for_sysid: prior_ini_precision needs estimate_ini")
-        wls = _wls_keywords(mdl, inputs, weights, huber_delta)
-        if skip_missing:                            # judged on what the caller gave (a host array is not moved to the device first)
-            _refuse_nan_start("BatchedLMLoop.for_sysid", states, ini_state, "states")
-        idx, mask = rt.ini_indices(estimate_ini, mdl.n)
-        if idx:                                     # (nothing selected is estimate_ini=None; an estimated component still needs the finite starting value checked above)
-            return cls._for_sysid_ini(mdl, inputs, states, theta0, samples_per_problem, ini_state, skip_missing, idx, mask, wls=wls, weights=weights,
-                                      prior_ini_precision=prior_ini_precision, **kw)
+        idx, _ = rt.ini_indices(estimate_ini, mdl.n)
+        rows, held = mdl.sysid_rows_prepared(inputs, states, skip_missing, ini_state, idx, weights, huber_delta, own_x0=bool(idx), who="BatchedLMLoop.for_sysid",
+                                             data_name="states")
         torch = rt.torch_cuda()
-        inputs, states = rt.dev(inputs), rt.dev(states)
+
+        def evaluate_rows(trial):                   # trial at a fixed address: [K S, p], or [K, W] = theta_k (read in place) | x0_k[idx] (copied into held["x0"])
+            out = rows(trial)
+            return out["packed_gn"], non_finite_rows(out["packed_gn"]).to(torch.int32)
+        if idx:                                     # (nothing selected is estimate_ini=None; an estimated component still needs the finite starting value checked above)
+            return cls._for_sysid_ini(mdl, evaluate_rows, held, theta0, samples_per_problem, ini_state, skip_missing, idx, weights=weights,
+                                      prior_ini_precision=prior_ini_precision, **kw)
+        inputs, states = held["u"], held["xobs"]
         B, T, S = int(inputs.shape[0]), int(inputs.shape[1]), int(samples_per_problem)
         assert states.shape == (B, T + 1, mdl.n) and inputs.shape == (B, T, mdl.m) and B % S == 0
-        x0 = rt.dev(ini_state).reshape(B, mdl.n).contiguous() if ini_state is not None else None
-        bufs = {}
-
-        def evaluate_rows(trial):
-            if wls:
-                out = mdl._sysid_step_wls_dev(inputs, states, *mdl._theta(trial, B), skip_missing, x0, bufs, [], 0, *wls)
-            else:
-                out = mdl.sysid_step(inputs, states, trial, gauss_newton=True, skip_missing=skip_missing, ini_state=x0, buffers=bufs)
-            return out["packed_gn"], (~torch.isfinite(out["packed_gn"])).any(dim=1).to(torch.int32)
 
         loop = cls(evaluate_rows, theta0, samples_per_problem=S, K=B // S, **kw)
         loop.n_observed = rt.count_observed(states, weights, skip_missing, _first_row(ini_state, None, mdl.n)).view(B // S, S).sum(dim=1)
         return loop
 
     @classmethod
-    def _for_sysid_ini(cls, mdl, inputs, states, theta0, samples_per_problem, ini_state, skip_missing, idx, mask, wls=None, weights=None, prior_ini_precision=None,
+    def _for_sysid_ini(cls, mdl, evaluate_rows, held, theta0, samples_per_problem, ini_state, skip_missing, idx, weights=None, prior_ini_precision=None,
                        prior_mean=None, prior_precision=None, prior_kind=None, **kw):
         torch = rt.torch_cuda()
-        inputs, states = rt.dev(inputs), rt.dev(states)
+        inputs, states, x0, cols = held["u"], held["xobs"], held["x0"], held["columns"]      # x0 persistent, at a fixed address
         K, T, p, q = int(inputs.shape[0]), int(inputs.shape[1]), mdl.p, len(idx)
         W = p + q
         assert states.shape == (K, T + 1, mdl.n) and inputs.shape == (K, T, mdl.m)
-        x0 = (rt.dev(ini_state).reshape(K, mdl.n) if ini_state is not None else states[:, 0]).contiguous().clone()      # persistent, at a fixed address
         if int(samples_per_problem) != 1:
             raise ValueError("BatchedLMLoop.for_sysid(estimate_ini=): one problem per trajectory (samples_per_problem == 1); one shared theta with an initial state "
                              "per recording is LMLoop.for_sysid(estimate_ini=)")
         if W > 16:
             raise ValueError("BatchedLMLoop.for_sysid(estimate_ini=): p + q = %d + %d > 16 unknowns per problem" % (p, q))
         ini0 = x0.cpu().numpy().copy()
-        cols = torch.tensor(idx, dtype=torch.int64, device="cuda")
         th = rt.dev(theta0)
         th = (th[None].expand(K, -1) if th.dim() == 1 else th).reshape(K, -1)
         if th.shape[1] == p:
             th = torch.cat([th, x0[:, cols]], dim=1)
         if th.shape[1] != W:
             raise ValueError("BatchedLMLoop.for_sysid(estimate_ini=): theta0 is [p], [K, p] or [K, p + q] = [%d, %d], got %s" % (K, W, tuple(th.shape)))
-        bufs = {}
-
-        def evaluate_rows(trial):                   # trial [K, W] at a fixed address: theta_k in its first p columns (read in place), x0_k[idx] behind them
-            x0.index_copy_(1, cols, trial[:, p:])
-            if wls:
-                out = mdl._sysid_step_wls_dev(inputs, states, trial, W, skip_missing, x0, bufs, idx, mask, *wls)
-            else:
-                out = mdl._sysid_step_gn_ini(inputs, states, trial, W, True, skip_missing, x0, bufs, idx, mask)
-            return out["packed_gn"], (~torch.isfinite(out["packed_gn"])).any(dim=1).to(torch.int32)
 
         def split(theta):
             v = np.asarray(theta.cpu() if hasattr(theta, "cpu") else theta, dtype=float).reshape(K, W)
@@ -883,25 +831,20 @@ class BatchedLMLoop:
         prior_mean, prior_precision (keywords of the class, in natural units) pass through; the loop counts the observed entries per problem
         (covariance(noise="estimated")) by LMLoop.for_irl's rule."""
         if skip_missing:
-            _refuse_nan_start("BatchedLMLoop.for_irl", demo_x, ini_state, "demo_x")
-        wls = _oc_wls_keywords(mdl, demo_u, weights_state, weights_control, huber_delta)
+            rt.refuse_nan_initial_state("BatchedLMLoop.for_irl", demo_x, ini_state, "demo_x")
+        rows, held = mdl.oc_rows_prepared(demo_x, demo_u, skip_missing, weights_state, weights_control, huber_delta)
         torch = rt.torch_cuda()
-        demo_x, demo_u = rt.dev(demo_x), rt.dev(demo_u)
+        demo_x, demo_u = held["demo_x"], held["demo_u"]
         B, T, S = int(demo_u.shape[0]), int(demo_u.shape[1]), int(samples_per_problem)
         assert demo_x.shape == (B, T + 1, mdl.n) and demo_u.shape == (B, T, mdl.m) and B % S == 0
         x0 = (demo_x[:, 0] if ini_state is None else rt.dev(ini_state).reshape(B, mdl.n)).contiguous()
-        bufs, sols = {}, {"accepted": None, "trial": None}
-        informational = 128 | 512 | 1024 | 2048          # PDP_MS_RESTORED, PDP_MS_PREDICT_REJECTED, PDP_MS_SOC, PDP_MS_WATCHDOG
+        sols = {"accepted": None, "trial": None}
 
         def evaluate_rows(trial):
             s = mdl.oc_solve_ms(x0, trial, T, tol=tol, max_iter=max_iter, warm=sols["accepted"])
-            if wls:
-                out = mdl._oc_pdp_wls_dev(s["control"], *mdl._theta(trial, B), demo_x, demo_u, None, s["state"], s["costate"], bufs, skip_missing, *wls)
-            else:
-                out = mdl.oc_pdp_grad(s["control"], trial, demo_x, demo_u, x=s["state"], lam=s["costate"], gauss_newton=True, skip_missing=skip_missing, buffers=bufs)
+            out = rows(s["control"], trial, x=s["state"], lam=s["costate"])
             sols["trial"] = (s["state"], s["control"], s["costate"])
-            bad = (s["converged_flags"] == 0) | ((s["status"] & ~informational) != 0) | (out["status"] != 0)
-            return out["packed_gn"], bad.to(torch.int32)
+            return out["packed_gn"], bad_irl_samples(s, out).to(torch.int32)
 
         loop = cls(evaluate_rows, theta0, samples_per_problem=S, K=B // S, **kw)
         loop.n_observed = (rt.count_observed(demo_x, weights_state, skip_missing, _first_row(ini_state, None, mdl.n)) +

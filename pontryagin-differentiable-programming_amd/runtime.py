@@ -422,60 +422,111 @@ def ini_indices(estimate_ini, n):
     return idx, sum(1 << i for i in idx)
 
 
-def _refuse_nan_initial_state(xobs, ini_state):
-    """skip_missing: a NaN in the initial state the rollouts would start from - ini_state, else xobs[:, 0] - is a ValueError before any launch.  Judged on what the
-    caller gave (a host array is not moved to the device first)."""
-    first = ini_state if ini_state is not None else (xobs if hasattr(xobs, "data_ptr") else np.asarray(xobs, dtype=float))[:, 0]
+def refuse_nan_initial_state(who, data, ini_state, name):
+    """skip_missing: a NaN in the initial state that would be used - ini_state, else data[:, 0] - is a ValueError before any launch, in the name of the caller `who`
+    (`name`: what it calls `data`).  Judged on what the caller gave (a host array is not moved to the device first)."""
+    first = ini_state if ini_state is not None else (data if hasattr(data, "data_ptr") else np.asarray(data, dtype=float))[:, 0]
     if bool(first.isnan().any()) if hasattr(first, "data_ptr") else bool(np.isnan(np.asarray(first, dtype=float)).any()):
-        raise ValueError("sysid_step: skip_missing=True and the initial state (%s) holds a NaN: give ini_state [B, n]" % ("xobs[:, 0]" if ini_state is None else "ini_state"))
+        raise ValueError("%s: skip_missing=True and the initial state (%s) holds a NaN: give ini_state [B, n]" % (who, "%s[:, 0]" % name if ini_state is None else "ini_state"))
+
+
+def _huber_threshold(huber_delta):
+    """huber_delta as a float, +inf for off (None); not > 0 is a ValueError"""
+    delta = float("inf") if huber_delta is None else float(huber_delta)
+    if not delta > 0.0:
+        raise ValueError("huber_delta: a threshold > 0 (None: plain least squares), got %r" % (huber_delta,))
+    return delta
+
+
+def _weight_block(w, name, B, rows, k, rows_text, letter):
+    """One block of weights, checked on what the caller gave (a host array is not moved to the device first): (the weights as given but shaped [rows, k] or
+    [B, rows, k], or None; their batch stride).  They broadcast from [k], [rows, k] or [B, rows, k]; a negative or non-finite weight or another shape is a ValueError
+    in the name of the keyword (`rows_text` and `letter`: how the message spells rows and k)."""
+    if w is None:
+        return None, 0
+    w = w if hasattr(w, "data_ptr") else np.asarray(w, dtype=float)
+    shape = tuple(w.shape)
+    if shape not in ((k,), (rows, k), (B, rows, k)):
+        raise ValueError("%s: shape [%s], [%s, %s] or [B, %s, %s] = (%d,), (%d, %d) or (%d, %d, %d), got %s"
+                         % (name, letter, rows_text, letter, rows_text, letter, k, rows, k, B, rows, k, shape))
+    if not bool(((w >= 0) & (w < float("inf"))).all()):          # (a NaN fails the comparison)
+        raise ValueError("%s: finite and >= 0 (0: the entry is not observed)" % name)
+    if len(shape) == 1:
+        w = w.expand(rows, k) if hasattr(w, "data_ptr") else np.broadcast_to(w, (rows, k))
+    return w, (0 if len(w.shape) == 2 else rows * k)
 
 
 def wls_arguments(weights, huber_delta, B, T, n):
     """The weights and Huber's threshold of pdp_sysid_step_wls_batched, normalised and checked on what the caller gave (a host array is not moved to the device first):
     returns (weights as given but shaped [T+1, n] or [B, T+1, n], or None; weights_bstride; delta as a float, +inf for off).  weights broadcast from [n], [T+1, n] or
-    [B, T+1, n]; a negative or non-finite weight, another shape, or a huber_delta that is not > 0 is a ValueError before any launch.  The loops of irl.py call it
-    once and evaluate many times (ModelLib._sysid_step_wls_dev)."""
-    delta = float("inf") if huber_delta is None else float(huber_delta)
-    if not delta > 0.0:
-        raise ValueError("huber_delta: a threshold > 0 (None: plain least squares), got %r" % (huber_delta,))
-    if weights is None:
-        return None, 0, delta
-    w = weights if hasattr(weights, "data_ptr") else np.asarray(weights, dtype=float)
-    shape = tuple(w.shape)
-    if shape not in ((n,), (T + 1, n), (B, T + 1, n)):
-        raise ValueError("weights: shape [n], [T+1, n] or [B, T+1, n] = (%d,), (%d, %d) or (%d, %d, %d), got %s" % (n, T + 1, n, B, T + 1, n, shape))
-    if not bool(((w >= 0) & (w < float("inf"))).all()):          # (a NaN fails the comparison)
-        raise ValueError("weights: finite and >= 0 (0: the entry is not observed)")
-    if len(shape) == 1:
-        w = w.expand(T + 1, n) if hasattr(w, "data_ptr") else np.broadcast_to(w, (T + 1, n))
-    return w, (0 if len(w.shape) == 2 else (T + 1) * n), delta
+    [B, T+1, n]; a negative or non-finite weight, another shape, or a huber_delta that is not > 0 is a ValueError before any launch.  ModelLib.sysid_rows_prepared
+    calls it once for many evaluations."""
+    delta = _huber_threshold(huber_delta)
+    return _weight_block(weights, "weights", B, T + 1, n, "T+1", "n") + (delta,)
 
 
 def oc_wls_arguments(weights_x, weights_u, huber_delta, B, T, n, m):
     """The weights and Huber's threshold of pdp_oc_pdp_grad_wls_batched, normalised and checked on what the caller gave, in the spirit of wls_arguments: returns
     (weights_x shaped [T+1, n] or [B, T+1, n], or None; its batch stride; weights_u shaped [T, m] or [B, T, m], or None; its batch stride; delta as a float, +inf for
     off).  weights_x broadcasts from [n], [T+1, n] or [B, T+1, n], weights_u from [m], [T, m] or [B, T, m]; a negative or non-finite weight, another shape, or a
-    huber_delta that is not > 0 is a ValueError before any launch.  The loops of irl.py call it once and evaluate many times (ModelLib._oc_pdp_wls_dev)."""
-    delta = float("inf") if huber_delta is None else float(huber_delta)
-    if not delta > 0.0:
-        raise ValueError("huber_delta: a threshold > 0 (None: plain least squares), got %r" % (huber_delta,))
+    huber_delta that is not > 0 is a ValueError before any launch.  ModelLib.oc_rows_prepared calls it once for many evaluations."""
+    delta = _huber_threshold(huber_delta)
+    return _weight_block(weights_x, "weights_x", B, T + 1, n, "T+1", "n") + _weight_block(weights_u, "weights_u", B, T, m, "T", "m") + (delta,)
 
-    def one(w, name, rows, k, letter):
-        if w is None:
-            return None, 0
-        w = w if hasattr(w, "data_ptr") else np.asarray(w, dtype=float)
-        shape = tuple(w.shape)
-        if shape not in ((k,), (rows, k), (B, rows, k)):
-            raise ValueError("%s: shape [%s], [%s, %s] or [B, %s, %s] = (%d,), (%d, %d) or (%d, %d, %d), got %s"
-                             % (name, letter, "T+1" if rows == T + 1 else "T", letter, "T+1" if rows == T + 1 else "T", letter, k, rows, k, B, rows, k, shape))
-        if not bool(((w >= 0) & (w < float("inf"))).all()):          # (a NaN fails the comparison)
-            raise ValueError("%s: finite and >= 0 (0: the entry is not observed)" % name)
-        if len(shape) == 1:
-            w = w.expand(rows, k) if hasattr(w, "data_ptr") else np.broadcast_to(w, (rows, k))
-        return w, (0 if len(w.shape) == 2 else rows * k)
-    wx, wxs = one(weights_x, "weights_x", T + 1, n, "n")
-    wu, wus = one(weights_u, "weights_u", T, m, "m")
-    return wx, wxs, wu, wus, delta
+
+def _buffer(bufs, key, shape, dtype=None):
+    """The tensor `key` of a caller's dict of buffers (outputs and workspaces reused between calls) in the asked shape and dtype (None: fp64): allocated when it is
+    not there, again when the shape changed"""
+    t = bufs.get(key)
+    if t is None or tuple(t.shape) != tuple(shape):
+        torch = torch_cuda()
+        t = bufs[key] = torch.empty(shape, dtype=torch.float64 if dtype is None else dtype, device="cuda")
+    return t
+
+
+def packed_row_from_sensitivities(packed, sides, rule, delta=float("inf"), skip_missing=False):
+    """The packed row grad [W] | loss | G [W][W] of a sum-of-squares loss from MATERIALISED sensitivities, written into packed [B, W + 1 + W W]: what the fused
+    least-squares entry points write themselves within their tiles, for the problems beyond them (PDP_E_SIZE).  sides: a list of (values [B, R, k], data [B, R, k],
+    weights broadcastable to [B, R, k] or None, sensitivities [B, R, k, W]) - the states for SysID.step, states and controls for the OC unit; their losses, gradients
+    and matrices add up.  rule, always as selects - never a product with 0:
+      "plain"             every entry counts;
+      "missing_residual"  SysID's skip_missing: the loss leaves out the entries whose DATA is NaN, gradient and G those whose DIFFERENCE is NaN - an observed entry
+                          with a non-finite state keeps its NaN in the loss, as in the kernels;
+      "missing_data"      the OC unit's skip_missing: everything leaves out the entries whose data is NaN;
+      "weighted"          weights w and Huber's threshold delta on e = sqrt(w) (values - data): an entry counts iff w > 0 and, under skip_missing, its data is not NaN;
+                          the residuals and the rows of the sensitivities are scaled by sqrt(w), beyond delta by sqrt(w delta / |e|).
+    Tensors of any one device (no check, no synchronisation)."""
+    import torch
+    B, W = packed.shape[0], sides[0][3].shape[-1]
+    zero = torch.zeros((), dtype=torch.float64, device=packed.device)
+    loss = grad = G = None
+    for v, data, w, S in sides:
+        d = v - data
+        if rule == "plain":
+            rho = (d * d).sum(dim=(1, 2))
+        elif rule == "missing_residual":
+            rho = torch.where(data == data, d * d, zero).sum(dim=(1, 2))
+            obs = d == d
+            d, S = torch.where(obs, d, zero), torch.where(obs[..., None], S, zero)
+        elif rule == "missing_data":
+            obs = ~torch.isnan(data)
+            d = torch.where(obs, d, zero)
+            rho = (d ** 2).sum(dim=(1, 2))
+            S = torch.where(obs[..., None], S, zero)
+        else:
+            wf = (w if w is not None else torch.ones((), dtype=torch.float64, device=packed.device)).expand(*data.shape)
+            obs = (wf > 0) & (data == data) if skip_missing else wf > 0
+            e = wf.sqrt() * d
+            ae = e.abs()
+            quad = ae <= delta
+            s = torch.where(quad, wf, wf * (delta / ae)).sqrt()
+            rho = torch.where(obs, torch.where(quad, e * e, 2.0 * delta * ae - delta * delta), zero).sum(dim=(1, 2))
+            d, S = torch.where(obs, s * d, zero), torch.where((obs & (s != 0))[..., None], s[..., None] * S, zero)
+        g, GG = torch.einsum("bti,btip->bp", d, S), torch.einsum("btip,btiq->bpq", S, S)
+        loss, grad, G = (rho, g, GG) if loss is None else (loss + rho, grad + g, G + GG)
+    packed[:, W] = loss
+    packed[:, :W] = grad
+    packed[:, W + 1:] = G.reshape(B, W * W)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -755,16 +806,25 @@ class ModelLib:
         (packed_gn, grad, loss, gn as views) of the weighted / robust loss; they combine with skip_missing, x0, a given (x, lam) and buffers={"packed_gn": ...}; with
         want_sens, want_riccati, want_predict_record or packed: ValueError.  Beyond the fused kernels' limits the same row comes from scaled residuals and row-scaled
         materialised sensitivities."""
-        if weights_x is not None or weights_u is not None or huber_delta is not None:
+        weighted = weights_x is not None or weights_u is not None or huber_delta is not None
+        if weighted:
             for name, on in (("want_sens", want_sens), ("want_riccati", want_riccati), ("want_predict_record", want_predict_record), ("packed", packed)):
                 if on:
                     raise ValueError("oc_pdp_grad: weights_x, weights_u and huber_delta give the packed Gauss-Newton row only - not together with %s" % name)
-            return self._oc_pdp_wls(u, theta, demo_x, demo_u, x0, x, lam, buffers, skip_missing, weights_x, weights_u, huber_delta)
+            u_shape = tuple(np.shape(u))
+            if len(u_shape) != 3 or u_shape[2] != self.m:
+                raise ValueError("oc_pdp_grad: u must be [B, T, %d], got %s" % (self.m, u_shape))
         if skip_missing and (want_sens or want_riccati or want_predict_record):
             raise ValueError("oc_pdp_grad: skip_missing=True goes with the gradient, packed or gauss_newton rows only - not with want_sens, want_riccati or "
                              "want_predict_record")
         if gauss_newton and (want_sens or want_riccati or want_predict_record or packed):
             raise ValueError("oc_pdp_grad: gauss_newton=True goes with the plain gradient only - not with want_sens, want_riccati, want_predict_record or packed")
+        if weighted or gauss_newton:
+            if x is not None and lam is None:
+                raise ValueError("oc_pdp_grad: a given trajectory needs x and lam")
+            if x is None and x0 is None:
+                raise ValueError("oc_pdp_grad: x0 [B, %d] is needed unless (x, lam) are given" % self.n)
+            return self.oc_rows_prepared(demo_x, demo_u, skip_missing, weights_x, weights_u, huber_delta, buffers)[0](u, theta, x0, x, lam)
         torch = torch_cuda()
         u, demo_x, demo_u = dev(u), dev(demo_x), dev(demo_u)
         B, T = u.shape[0], u.shape[1]
@@ -778,35 +838,25 @@ class ModelLib:
         else:
             x0 = dev(x0).reshape(B, n)
         bufs = buffers if buffers is not None else {}
-
-        def buf(key, shape, dtype=torch.float64):
-            t = bufs.get(key)
-            if t is None or tuple(t.shape) != tuple(shape):
-                t = torch.empty(shape, dtype=dtype, device="cuda")
-                bufs[key] = t
-            return t
         if x is None:
-            x, lam = buf("x", (B, T + 1, n)), buf("lam", (B, T, n))
-        loss = buf("loss", (B,))
+            x, lam = _buffer(bufs, "x", (B, T + 1, n)), _buffer(bufs, "lam", (B, T, n))
+        loss = _buffer(bufs, "loss", (B,))
         if packed:
-            pk = buf("packed", (B, p + 1))
+            pk = _buffer(bufs, "packed", (B, p + 1))
             grad, flags = pk[:, :p], flags | 2
-        elif gauss_newton:
-            pk = buf("packed_gn", (B, p + 1 + p * p))
-            grad, flags = pk[:, :p], flags | 16
         else:
-            pk = grad = buf("grad", (B, p))
-        status = buf("status", (B,), torch.int32)
-        dxdp = buf("dxdp", (B, T + 1, n, p)) if want_sens else None
-        dudp = buf("dudp", (B, T, m, p)) if want_sens else None
-        ric = buf("riccati", (B, T, int(self.lib.pdp_oc_riccati_doubles()))) if want_riccati else None
-        prec = buf("predict_record", (B, T, int(self.lib.pdp_oc_predict_record_floats())), torch.float32) if want_predict_record else None
+            pk = grad = _buffer(bufs, "grad", (B, p))
+        status = _buffer(bufs, "status", (B,), torch.int32)
+        dxdp = _buffer(bufs, "dxdp", (B, T + 1, n, p)) if want_sens else None
+        dudp = _buffer(bufs, "dudp", (B, T, m, p)) if want_sens else None
+        ric = _buffer(bufs, "riccati", (B, T, int(self.lib.pdp_oc_riccati_doubles()))) if want_riccati else None
+        prec = _buffer(bufs, "predict_record", (B, T, int(self.lib.pdp_oc_predict_record_floats())), torch.float32) if want_predict_record else None
         if want_predict_record == "primal":
             flags |= 4
         if skip_missing:
             flags |= 32
         nbytes = self.lib.pdp_oc_pdp_workspace_bytes(B, T)
-        ws = buf("ws", (max(nbytes, 8) // 8,))
+        ws = _buffer(bufs, "ws", (max(nbytes, 8) // 8,))
         if want_riccati or want_predict_record:
             so = PdpOcSensOut(dxdp.data_ptr() if dxdp is not None else None, dudp.data_ptr() if dudp is not None else None,
                               ric.data_ptr() if ric is not None else None, prec.data_ptr() if prec is not None else None)
@@ -821,32 +871,19 @@ class ModelLib:
             # m + p > 16 (beyond the fused kernel's single parameter tile), n > 16 / m > 4 (beyond one tile per matrix: the size-generic LQR
             # kernel takes over - any n, m), or a horizon whose staging exceeds the LDS: the reference's own route, kernel by kernel
             self._warn_materialised(T)
-            if gauss_newton or skip_missing:                    # the sensitivities through HBM, contracted here: the same row
-                dxdp, dudp = torch.empty((B, T + 1, n, p), dtype=torch.float64, device="cuda"), torch.empty((B, T, m, p), dtype=torch.float64, device="cuda")
-            if skip_missing:
-                # the want_sens launch on the demonstrations with their NaNs replaced by zeros gives x, lam, status and the sensitivities; loss and gradient are
-                # re-formed here from the masked residuals (selected, not multiplied: an inf in an absent slot cannot exist - only NaN is absent)
-                wx, wu = ~torch.isnan(demo_x), ~torch.isnan(demo_u)
-                zero = torch.zeros((), dtype=torch.float64, device="cuda")
-                self._oc_pdp_grad_materialised(u, theta, torch.where(wx, demo_x, zero), torch.where(wu, demo_u, zero), x0, x, lam, flags, loss, grad, status, dxdp, dudp)
-                ex, eu = torch.where(wx, x - demo_x, zero), torch.where(wu, u - demo_u, zero)
-                loss.copy_((ex ** 2).sum(dim=(1, 2)) + (eu ** 2).sum(dim=(1, 2)))
-                dxdp, dudp = torch.where(wx[..., None], dxdp, zero), torch.where(wu[..., None], dudp, zero)
-                grad.copy_(torch.einsum("bti,btip->bp", ex, dxdp) + torch.einsum("bti,btip->bp", eu, dudp))
+            if skip_missing:                                    # loss and gradient of the masked row (_oc_rows: the same route, the same contraction)
+                row = torch.empty((B, p + 1 + p * p), dtype=torch.float64, device="cuda")
+                self._oc_rows_materialised(u, th, demo_x, demo_u, x0, x, lam, flags, loss, row, status, "missing_data")
+                grad.copy_(row[:, :p])
             else:
                 self._oc_pdp_grad_materialised(u, theta, demo_x, demo_u, x0, x, lam, flags, loss, grad, status, dxdp, dudp)
-            if packed or gauss_newton:
+            if packed:
                 pk[:, p].copy_(loss)
-            if gauss_newton:
-                pk[:, p + 1:].copy_((torch.einsum("btip,btiq->bpq", dxdp, dxdp) + torch.einsum("btip,btiq->bpq", dudp, dudp)).reshape(B, p * p))
             rc = 0
         check(rc, "pdp_oc_pdp_grad_batched")
         out = dict(loss=loss, grad=grad, x=x, lam=lam, status=status)
         if packed:
             out["packed"] = pk
-        if gauss_newton:
-            out["packed_gn"] = pk
-            out["gn"] = pk[:, p + 1:].view(B, p, p)
         if want_sens:
             out.update(dxdp=dxdp, dudp=dudp)
         if want_riccati:
@@ -855,77 +892,84 @@ class ModelLib:
             out["predict_record"] = prec
         return out
 
-    def _oc_pdp_wls(self, u, theta, demo_x, demo_u, x0, x, lam, buffers, skip_missing, weights_x, weights_u, huber_delta):
-        """oc_pdp_grad with weights and / or Huber's loss: the arguments are checked and moved to the device here, the call is _oc_pdp_wls_dev's"""
-        u_shape = tuple(np.shape(u))
-        if len(u_shape) != 3 or u_shape[2] != self.m:
-            raise ValueError("oc_pdp_grad: u must be [B, T, %d], got %s" % (self.m, u_shape))
-        B, T = int(u_shape[0]), int(u_shape[1])
-        wx, wxs, wu, wus, delta = oc_wls_arguments(weights_x, weights_u, huber_delta, B, T, self.n, self.m)
-        if x is not None and lam is None:
-            raise ValueError("oc_pdp_grad: a given trajectory needs x and lam")
-        if x is None and x0 is None:
-            raise ValueError("oc_pdp_grad: x0 [B, %d] is needed unless (x, lam) are given" % self.n)
-        u, demo_x, demo_u = dev(u), dev(demo_x), dev(demo_u)
-        th, tb = self._theta(theta, B)
-        if x is not None:
-            x, lam, x0 = dev(x), dev(lam), None
-        else:
-            x0 = dev(x0).reshape(B, self.n)
-        return self._oc_pdp_wls_dev(u, th, tb, demo_x, demo_u, x0, x, lam, buffers, skip_missing, dev(wx) if wx is not None else None, wxs,
-                                    dev(wu) if wu is not None else None, wus, delta)
-
-    def _oc_pdp_wls_dev(self, u, th, tb, demo_x, demo_u, x0, x, lam, buffers, skip_missing, wxd, wxs, wud, wus, delta):
-        """pdp_oc_pdp_grad_wls_batched on device tensors and normalised arguments (oc_wls_arguments: wxd [T+1, n] or [B, T+1, n] or None, wud [T, m] or [B, T, m] or
-        None, their batch strides, delta a float), no check and no host synchronisation: what the loops of irl.py call per evaluation.  th [1 or B, p] with row stride
-        tb; (x, lam) given (PDP_OC_GIVEN_TRAJ) or x0 [B, n].  Always the packed Gauss-Newton dict."""
+    def _oc_rows_materialised(self, u, th, demo_x, demo_u, x0, x, lam, flags, loss, pk, status, rule, wxd=None, wud=None, delta=float("inf")):
+        """The packed row of the OC unit beyond the fused kernels' limits, by `rule` of packed_row_from_sensitivities: the want_sens launch of the kernel-by-kernel
+        route gives x, lam, status and the sensitivities.  "plain": loss and gradient are that launch's own and G is contracted here.  Else the launch runs on the
+        demonstrations with their NaNs replaced by zeros and the whole row is re-formed here from masked / scaled residuals and sensitivities (selected, not
+        multiplied: an inf in an absent slot cannot exist - only NaN is absent).  Fills loss [B], pk [B, p + 1 + p p] and status."""
         torch = torch_cuda()
-        B, T, n, m, p = u.shape[0], u.shape[1], self.n, self.m, self.p
-        bufs = buffers if buffers is not None else {}
+        (B, T), n, m, p = u.shape[:2], self.n, self.m, self.p
+        dxdp, dudp = torch.empty((B, T + 1, n, p), dtype=torch.float64, device="cuda"), torch.empty((B, T, m, p), dtype=torch.float64, device="cuda")
+        if rule == "plain":
+            self._oc_pdp_grad_materialised(u, th, demo_x, demo_u, x0, x, lam, flags, loss, pk[:, :p], status, dxdp, dudp)
+            pk[:, p].copy_(loss)
+            pk[:, p + 1:].copy_((torch.einsum("btip,btiq->bpq", dxdp, dxdp) + torch.einsum("btip,btiq->bpq", dudp, dudp)).reshape(B, p * p))
+            return
+        zero = torch.zeros((), dtype=torch.float64, device="cuda")
+        self._oc_pdp_grad_materialised(u, th, torch.where(torch.isnan(demo_x), zero, demo_x), torch.where(torch.isnan(demo_u), zero, demo_u), x0, x, lam, flags, loss,
+                                       pk[:, :p], status, dxdp, dudp)
+        packed_row_from_sensitivities(pk, [(x, demo_x, wxd, dxdp), (u, demo_u, wud, dudp)], rule, delta, bool(flags & 32))
+        loss.copy_(pk[:, p])
 
-        def buf(key, shape, dtype=torch.float64):
-            t = bufs.get(key)
-            if t is None or tuple(t.shape) != tuple(shape):
-                t = bufs[key] = torch.empty(shape, dtype=dtype, device="cuda")
-            return t
+    def _oc_rows(self, u, th, tb, demo_x, demo_u, x0, x, lam, buffers, skip_missing=False, wls=None):
+        """The fused OC unit as a least-squares evaluation on device tensors and normalised arguments, no check and no host synchronisation, ONE launch: what
+        oc_pdp_grad runs with gauss_newton or weights and what every evaluation of the IRL loops of irl.py runs (oc_rows_prepared marshals for it).  th [1 or B, p]
+        with row stride tb; (x, lam) given (PDP_OC_GIVEN_TRAJ) or x0 [B, n]; wls: None - pdp_oc_pdp_grad_batched with PDP_GRAD_GAUSS_NEWTON - or (weights_x
+        [T+1, n] or [B, T+1, n] or None, its batch stride, weights_u [T, m] or [B, T, m] or None, its batch stride, delta as a float) from oc_wls_arguments -
+        pdp_oc_pdp_grad_wls_batched.  Returns the packed Gauss-Newton dict: packed_gn [B, p + 1 + p p] and loss, grad, gn as views of it, x, lam, status."""
+        torch = torch_cuda()
+        B, T, n, p = u.shape[0], u.shape[1], self.n, self.p
+        bufs = buffers if buffers is not None else {}
         flags = 32 if skip_missing else 0
         if x is not None:
             flags |= 1
         else:
-            x, lam = buf("x", (B, T + 1, n)), buf("lam", (B, T, n))
-        loss, pk, status = buf("loss", (B,)), buf("packed_gn", (B, p + 1 + p * p)), buf("status", (B,), torch.int32)
+            x, lam = _buffer(bufs, "x", (B, T + 1, n)), _buffer(bufs, "lam", (B, T, n))
+        loss, pk, status = _buffer(bufs, "loss", (B,)), _buffer(bufs, "packed_gn", (B, p + 1 + p * p)), _buffer(bufs, "status", (B,), torch.int32)
         nbytes = self.lib.pdp_oc_pdp_workspace_bytes(B, T)
-        ws = buf("ws", (max(nbytes, 8) // 8,))
-        rc = self.lib.pdp_oc_pdp_grad_wls_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(demo_x), ptr(demo_u), ptr(wxd), wxs, ptr(wud), wus, delta, ptr(x),
-                                                  ptr(lam), ptr(loss), ptr(pk), ptr(status), ptr(ws), nbytes, current_stream_ptr())
-        if rc == -2:
-            # beyond the fused kernels' limits: the want_sens launch of the kernel-by-kernel route on zero-filled demonstrations gives x, lam, status and the
-            # sensitivities; the row is formed here from scaled residuals and row-scaled sensitivities (selects, as in the kernels: never a product with 0)
+        ws = _buffer(bufs, "ws", (max(nbytes, 8) // 8,))
+        if wls is not None:
+            name, (wxd, wxs, wud, wus, delta) = "pdp_oc_pdp_grad_wls_batched", wls
+            rc = self.lib.pdp_oc_pdp_grad_wls_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(demo_x), ptr(demo_u), ptr(wxd), wxs, ptr(wud), wus, delta, ptr(x),
+                                                      ptr(lam), ptr(loss), ptr(pk), ptr(status), ptr(ws), nbytes, current_stream_ptr())
+        else:
+            name, flags = "pdp_oc_pdp_grad_batched", flags | 16
+            rc = self.lib.pdp_oc_pdp_grad_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(demo_x), ptr(demo_u), ptr(x), ptr(lam), ptr(loss), ptr(pk), ptr(None),
+                                                  ptr(None), ptr(status), ptr(ws), nbytes, current_stream_ptr())
+        if rc == -2:                                # beyond the fused kernels' limits: the same row from the materialised sensitivities
             self._warn_materialised(T)
-            zero, one = torch.zeros((), dtype=torch.float64, device="cuda"), torch.ones((), dtype=torch.float64, device="cuda")
-            dxdp, dudp = torch.empty((B, T + 1, n, p), dtype=torch.float64, device="cuda"), torch.empty((B, T, m, p), dtype=torch.float64, device="cuda")
-            self._oc_pdp_grad_materialised(u, th, torch.where(torch.isnan(demo_x), zero, demo_x), torch.where(torch.isnan(demo_u), zero, demo_u), x0, x, lam, flags & 1,
-                                           loss, pk[:, :p], status, dxdp, dudp)
-
-            def side(v, demo, w, S):
-                wf = (w if w is not None else one).expand(*demo.shape)
-                d = v - demo
-                obs = (wf > 0) & (demo == demo) if skip_missing else wf > 0
-                e = wf.sqrt() * d
-                ae = e.abs()
-                quad = ae <= delta
-                s = torch.where(quad, wf, wf * (delta / ae)).sqrt()
-                rho = torch.where(obs, torch.where(quad, e * e, 2.0 * delta * ae - delta * delta), zero).sum(dim=(1, 2))
-                return rho, torch.where(obs, s * d, zero), torch.where((obs & (s != 0))[..., None], s[..., None] * S, zero)
-            lx, sdx, sX = side(x, demo_x, wxd, dxdp)
-            lu, sdu, sU = side(u, demo_u, wud, dudp)
-            loss.copy_(lx + lu)
-            pk[:, p].copy_(loss)
-            pk[:, :p].copy_(torch.einsum("bti,btip->bp", sdx, sX) + torch.einsum("bti,btip->bp", sdu, sU))
-            pk[:, p + 1:].copy_((torch.einsum("btip,btiq->bpq", sX, sX) + torch.einsum("btip,btiq->bpq", sU, sU)).reshape(B, p * p))
+            if wls is not None:
+                self._oc_rows_materialised(u, th, demo_x, demo_u, x0, x, lam, flags, loss, pk, status, "weighted", wxd, wud, delta)
+            else:
+                self._oc_rows_materialised(u, th, demo_x, demo_u, x0, x, lam, flags, loss, pk, status, "missing_data" if skip_missing else "plain")
             rc = 0
-        check(rc, "pdp_oc_pdp_grad_wls_batched")
+        check(rc, name)
         return dict(packed_gn=pk, loss=pk[:, p], grad=pk[:, :p], gn=pk[:, p + 1:].view(B, p, p), x=x, lam=lam, status=status)
+
+    def oc_rows_prepared(self, demo_x, demo_u, skip_missing=False, weights_x=None, weights_u=None, huber_delta=None, buffers=None):
+        """The OC unit's least-squares evaluation as a PREPARED call: weights_x, weights_u and huber_delta are checked once (oc_wls_arguments on the shape of demo_u:
+        ValueErrors before anything is moved), demonstrations and weights moved to the device once; the returned rows(u, theta, x0=None, x=None, lam=None) is then
+        one launch per call (_oc_rows: pdp_oc_pdp_grad_wls_batched where one of the three keywords was given, else pdp_oc_pdp_grad_batched with
+        PDP_GRAD_GAUSS_NEWTON) and returns the packed Gauss-Newton dict.  theta [p] shared or [B, p] per sample; (x, lam) a given trajectory, else x0.  Returns
+        (rows, held) with held = dict(demo_x, demo_u): the device tensors the evaluations read."""
+        wls = None
+        if weights_x is not None or weights_u is not None or huber_delta is not None:
+            B, T = (int(v) for v in np.shape(demo_u)[:2])
+            wx, wxs, wu, wus, delta = oc_wls_arguments(weights_x, weights_u, huber_delta, B, T, self.n, self.m)
+            wls = (dev(wx).contiguous() if wx is not None else None, wxs, dev(wu).contiguous() if wu is not None else None, wus, delta)
+        demo_x, demo_u = dev(demo_x), dev(demo_u)
+        bufs = buffers if buffers is not None else {}
+
+        def rows(u, theta, x0=None, x=None, lam=None):
+            u = dev(u)
+            B = u.shape[0]
+            th, tb = self._theta(theta, B)
+            if x is not None:
+                x, lam, x0 = dev(x), dev(lam), None
+            else:
+                x0 = dev(x0).reshape(B, self.n)
+            return self._oc_rows(u, th, tb, demo_x, demo_u, x0, x, lam, bufs, skip_missing, wls)
+        return rows, dict(demo_x=demo_x, demo_u=demo_u)
 
     def oc_pdp_vjp(self, u, theta, gx, gu, x0=None, x=None, lam=None, buffers=None):
         """The fused unit as a vector-Jacobian product of the OC solution (PDP_OC_COTANGENT, include/pdp_hip.h): gx [B, T+1, n] = dL/dx and gu [B, T, m] = dL/du are the
@@ -955,19 +999,12 @@ class ModelLib:
         else:
             x0 = dev(x0).reshape(B, n)
         bufs = buffers if buffers is not None else {}
-
-        def buf(key, shape, dtype=torch.float64):
-            t = bufs.get(key)
-            if t is None or tuple(t.shape) != tuple(shape):
-                t = torch.empty(shape, dtype=dtype, device="cuda")
-                bufs[key] = t
-            return t
         if x is None:
-            x, lam = buf("x", (B, T + 1, n)), buf("lam", (B, T, n))
-        grad = buf("grad", (B, p))
-        status = buf("status", (B,), torch.int32)
+            x, lam = _buffer(bufs, "x", (B, T + 1, n)), _buffer(bufs, "lam", (B, T, n))
+        grad = _buffer(bufs, "grad", (B, p))
+        status = _buffer(bufs, "status", (B,), torch.int32)
         nbytes = self.lib.pdp_oc_pdp_workspace_bytes(B, T)
-        ws = buf("ws", (max(nbytes, 8) // 8,))
+        ws = _buffer(bufs, "ws", (max(nbytes, 8) // 8,))
         rc = self.lib.pdp_oc_pdp_grad_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(gx), ptr(gu), ptr(x), ptr(lam), ptr(None),
                                               ptr(grad), ptr(None), ptr(None), ptr(status), ptr(ws), nbytes, current_stream_ptr())
         if rc == -2:
@@ -1235,13 +1272,11 @@ class ModelLib:
         observed (xobs may hold anything there).  huber_delta > 0 acts on the standardised residual e = sqrt(w) (x - xobs): rho = e^2 up to delta, 2 delta |e| - delta^2
         beyond; loss = sum rho, grad its exact half derivative, gn the Gauss-Newton matrix of iteratively reweighted least squares (include/pdp_hip_sysid_wls.h).  They
         combine with skip_missing, ini_state and estimate_ini; W > 16 or n > 16: the same row from scaled residuals and row-scaled materialised sensitivities."""
-        idx, mask = ini_indices(estimate_ini, self.n)
-        if weights is not None or huber_delta is not None:
-            return self._sysid_step_wls(u, xobs, theta, skip_missing, ini_state, buffers, idx, mask, weights, huber_delta)
-        if idx:                                     # (nothing selected is estimate_ini=None: today's calls and today's rows)
-            return self._sysid_step_gn(u, xobs, theta, gauss_newton, skip_missing, ini_state, buffers, idx, mask)
-        if gauss_newton or skip_missing or ini_state is not None:
-            return self._sysid_step_gn(u, xobs, theta, gauss_newton, skip_missing, ini_state, buffers)
+        idx, _ = ini_indices(estimate_ini, self.n)
+        weighted = weights is not None or huber_delta is not None
+        if weighted or idx or gauss_newton or skip_missing or ini_state is not None:      # (nothing selected is estimate_ini=None: today's calls and today's rows)
+            out = self.sysid_rows_prepared(u, xobs, skip_missing, ini_state, idx, weights, huber_delta, buffers)[0](theta)
+            return out if gauss_newton or weighted else (out["loss"], out["grad"])
         torch = torch_cuda()
         u, xobs = dev(u), dev(xobs)
         B, T = u.shape[0], u.shape[1]
@@ -1279,130 +1314,75 @@ class ModelLib:
             X0[:, i, p + k] = 1.0
         return x, sysid_aux_integrate(F, Ew, X0)
 
-    def _sysid_step_gn(self, u, xobs, theta, gauss_newton, skip_missing, ini_state, buffers, ini_index=(), ini_mask=0):
-        if skip_missing:
-            _refuse_nan_initial_state(xobs, ini_state)
-        torch = torch_cuda()
-        u, xobs = dev(u), dev(xobs)
-        B, T, n, p = u.shape[0], u.shape[1], self.n, self.p
-        x0 = dev(ini_state).reshape(B, n).contiguous() if ini_state is not None else None
-        th, tb = self._theta(theta, B)
-        q = len(ini_index)
-        if q:
-            return self._sysid_step_gn_ini(u, xobs, th, tb, gauss_newton, skip_missing, x0, buffers, list(ini_index), ini_mask)
+    def _sysid_rows(self, u, xobs, th, tb, x0, buffers, skip_missing=False, ini_index=(), ini_mask=0, wls=None):
+        """SysID.step as a least-squares evaluation on device tensors and normalised arguments, no check and no host synchronisation, ONE launch: what every Gauss-Newton
+        mode of sysid_step and every evaluation of the loops of irl.py runs (sysid_rows_prepared marshals for it).  th [1 or B, >= p] with row stride tb (wider rows
+        are read in place); x0 [B, n] or None (xobs[:, 0]); ini_index / ini_mask: the estimated components of x0 (ini_indices), W = p + q unknowns; wls: None, or
+        (weights [T+1, n] or [B, T+1, n] or None, their batch stride, delta as a float) from wls_arguments.  Weights or delta go to pdp_sysid_step_wls_batched
+        (buffer packed_gn_wls), estimated components to pdp_sysid_step_gn_ini_batched (packed_gn_ini), everything else to pdp_sysid_step_gn_batched (packed_gn).
+        Returns the packed dict over W: packed_gn [B, W + 1 + W W] and loss, grad, gn as views of it, ini_index where components are estimated."""
+        B, T, W = u.shape[0], u.shape[1], self.p + len(ini_index)
         bufs = buffers if buffers is not None else {}
-
-        def buf(key, shape):
-            t = bufs.get(key)
-            if t is None or tuple(t.shape) != tuple(shape):
-                t = bufs[key] = torch.empty(shape, dtype=torch.float64, device="cuda")
-            return t
-        loss, packed = buf("loss", (B,)), buf("packed_gn", (B, p + 1 + p * p))
+        flags = 32 if skip_missing else 0
+        loss = _buffer(bufs, "loss", (B,))
+        packed = _buffer(bufs, "packed_gn_wls" if wls is not None else ("packed_gn_ini" if ini_mask else "packed_gn"), (B, W + 1 + W * W))
         ws, nbytes = self._sysid_workspace(B, T)
-        rc = self.lib.pdp_sysid_step_gn_batched(B, T, ptr(u), ptr(xobs), ptr(x0), ptr(th), tb, 32 if skip_missing else 0, ptr(loss), ptr(packed), ptr(ws), nbytes,
-                                                current_stream_ptr())
-        if rc == -2:                                # beyond the fused kernels' tiles: the same row from the materialised sensitivities
-            x, X = self._sysid_materialised(u, xobs, th, x0)                        # X [B, T+1, n, p]
-            d = x - xobs
-            if skip_missing:                        # selects, as in the kernels: an observed entry with a non-finite state keeps its NaN in the loss
-                zero = torch.zeros((), dtype=torch.float64, device="cuda")
-                packed[:, p] = torch.where(xobs == xobs, d * d, zero).sum(dim=(1, 2))
-                obs = d == d
-                d, X = torch.where(obs, d, zero), torch.where(obs[..., None], X, zero)
-            else:
-                packed[:, p] = (d * d).sum(dim=(1, 2))
-            packed[:, :p] = torch.einsum("bti,btip->bp", d, X)
-            packed[:, p + 1:] = torch.einsum("btip,btiq->bpq", X, X).reshape(B, p * p)
-            rc = 0
-        check(rc, "pdp_sysid_step_gn_batched")
-        if not gauss_newton:
-            return packed[:, p], packed[:, :p]
-        return dict(packed_gn=packed, loss=packed[:, p], grad=packed[:, :p], gn=packed[:, p + 1:].view(B, p, p))
-
-    def _sysid_step_gn_ini(self, u, xobs, th, tb, gauss_newton, skip_missing, x0, buffers, ini_index, ini_mask):
-        """sysid_step with estimated components of the initial state (device tensors; th [1 or B, p], tb its row stride)"""
-        torch = torch_cuda()
-        B, T, n, p = u.shape[0], u.shape[1], self.n, self.p
-        W = p + len(ini_index)
-        bufs = buffers if buffers is not None else {}
-
-        def buf(key, shape):
-            t = bufs.get(key)
-            if t is None or tuple(t.shape) != tuple(shape):
-                t = bufs[key] = torch.empty(shape, dtype=torch.float64, device="cuda")
-            return t
-        loss, packed = buf("loss", (B,)), buf("packed_gn_ini", (B, W + 1 + W * W))
-        ws, nbytes = self._sysid_workspace(B, T)
-        rc = self.lib.pdp_sysid_step_gn_ini_batched(B, T, ptr(u), ptr(xobs), ptr(x0), ini_mask, ptr(th), tb, 32 if skip_missing else 0, ptr(loss), ptr(packed), ptr(ws),
-                                                    nbytes, current_stream_ptr())
-        if rc == -2:                                # beyond the fused kernels' tile: the same row from the materialised sensitivities, started at the selection matrix
+        if wls is not None:
+            name, (wd, wbs, delta) = "pdp_sysid_step_wls_batched", wls
+            rc = self.lib.pdp_sysid_step_wls_batched(B, T, ptr(u), ptr(xobs), ptr(x0), ini_mask, ptr(wd), wbs, delta, ptr(th), tb, flags, ptr(loss), ptr(packed), ptr(ws),
+                                                     nbytes, current_stream_ptr())
+        elif ini_mask:
+            name = "pdp_sysid_step_gn_ini_batched"
+            rc = self.lib.pdp_sysid_step_gn_ini_batched(B, T, ptr(u), ptr(xobs), ptr(x0), ini_mask, ptr(th), tb, flags, ptr(loss), ptr(packed), ptr(ws), nbytes,
+                                                        current_stream_ptr())
+        else:
+            name = "pdp_sysid_step_gn_batched"
+            rc = self.lib.pdp_sysid_step_gn_batched(B, T, ptr(u), ptr(xobs), ptr(x0), ptr(th), tb, flags, ptr(loss), ptr(packed), ptr(ws), nbytes, current_stream_ptr())
+        if rc == -2:                                # beyond the fused kernels' tile: the same row from the materialised sensitivities (started at the selection matrix)
             x, X = self._sysid_materialised(u, xobs, th, x0, ini_index)             # X [B, T+1, n, W]
-            d = x - xobs
-            if skip_missing:                        # selects, as in the kernels: an observed entry with a non-finite state keeps its NaN in the loss
-                zero = torch.zeros((), dtype=torch.float64, device="cuda")
-                packed[:, W] = torch.where(xobs == xobs, d * d, zero).sum(dim=(1, 2))
-                obs = d == d
-                d, X = torch.where(obs, d, zero), torch.where(obs[..., None], X, zero)
+            if wls is not None:
+                packed_row_from_sensitivities(packed, [(x, xobs, wls[0], X)], "weighted", wls[2], skip_missing)
             else:
-                packed[:, W] = (d * d).sum(dim=(1, 2))
-            packed[:, :W] = torch.einsum("bti,btip->bp", d, X)
-            packed[:, W + 1:] = torch.einsum("btip,btiq->bpq", X, X).reshape(B, W * W)
+                packed_row_from_sensitivities(packed, [(x, xobs, None, X)], "missing_residual" if skip_missing else "plain")
             rc = 0
-        check(rc, "pdp_sysid_step_gn_ini_batched")
-        if not gauss_newton:
-            return packed[:, W], packed[:, :W]
-        return dict(packed_gn=packed, loss=packed[:, W], grad=packed[:, :W], gn=packed[:, W + 1:].view(B, W, W), ini_index=ini_index)
-
-    def _sysid_step_wls(self, u, xobs, theta, skip_missing, ini_state, buffers, ini_index, ini_mask, weights, huber_delta):
-        """sysid_step with weights and / or Huber's loss: the arguments are checked and moved to the device here, the call is _sysid_step_wls_dev's"""
-        w, wbs, delta = wls_arguments(weights, huber_delta, int(u.shape[0]), int(u.shape[1]), self.n)
-        if skip_missing:
-            _refuse_nan_initial_state(xobs, ini_state)
-        u, xobs = dev(u), dev(xobs)
-        B = u.shape[0]
-        x0 = dev(ini_state).reshape(B, self.n).contiguous() if ini_state is not None else None
-        th, tb = self._theta(theta, B)
-        return self._sysid_step_wls_dev(u, xobs, th, tb, skip_missing, x0, buffers, ini_index, ini_mask, dev(w).contiguous() if w is not None else None, wbs, delta)
-
-    def _sysid_step_wls_dev(self, u, xobs, th, tb, skip_missing, x0, buffers, ini_index, ini_mask, wd, wbs, delta):
-        """pdp_sysid_step_wls_batched on device tensors and normalised arguments (wls_arguments: wd [T+1, n] or [B, T+1, n] or None, wbs its batch stride, delta a
-        float), no check and no host synchronisation: what the loops of irl.py call per evaluation.  th [1 or B, >= p] with row stride tb; always the packed dict over
-        W = p + q."""
-        torch = torch_cuda()
-        B, T, n, p = u.shape[0], u.shape[1], self.n, self.p
-        W = p + len(ini_index)
-        bufs = buffers if buffers is not None else {}
-
-        def buf(key, shape):
-            t = bufs.get(key)
-            if t is None or tuple(t.shape) != tuple(shape):
-                t = bufs[key] = torch.empty(shape, dtype=torch.float64, device="cuda")
-            return t
-        loss, packed = buf("loss", (B,)), buf("packed_gn_wls", (B, W + 1 + W * W))
-        ws, nbytes = self._sysid_workspace(B, T)
-        rc = self.lib.pdp_sysid_step_wls_batched(B, T, ptr(u), ptr(xobs), ptr(x0), ini_mask, ptr(wd), wbs, delta, ptr(th), tb, 32 if skip_missing else 0, ptr(loss),
-                                                 ptr(packed), ptr(ws), nbytes, current_stream_ptr())
-        if rc == -2:                                # beyond the fused kernels' tile: the same row from scaled residuals and row-scaled materialised sensitivities
-            x, X = self._sysid_materialised(u, xobs, th, x0, ini_index)             # X [B, T+1, n, W]
-            zero = torch.zeros((), dtype=torch.float64, device="cuda")
-            wf = (wd if wd is not None else torch.ones((), dtype=torch.float64, device="cuda")).expand(B, T + 1, n)
-            d = x - xobs
-            obs = (wf > 0) & (xobs == xobs) if skip_missing else wf > 0
-            e = wf.sqrt() * d
-            ae = e.abs()
-            quad = ae <= delta
-            s = torch.where(quad, wf, wf * (delta / ae)).sqrt()
-            packed[:, W] = torch.where(obs, torch.where(quad, e * e, 2.0 * delta * ae - delta * delta), zero).sum(dim=(1, 2))
-            sd = torch.where(obs, s * d, zero)                                      # selects, as in the kernels: never a product with 0
-            sX = torch.where((obs & (s != 0))[..., None], s[..., None] * X, zero)
-            packed[:, :W] = torch.einsum("bti,btip->bp", sd, sX)
-            packed[:, W + 1:] = torch.einsum("btip,btiq->bpq", sX, sX).reshape(B, W * W)
-            rc = 0
-        check(rc, "pdp_sysid_step_wls_batched")
+        check(rc, name)
         out = dict(packed_gn=packed, loss=packed[:, W], grad=packed[:, :W], gn=packed[:, W + 1:].view(B, W, W))
         if ini_index:
             out["ini_index"] = list(ini_index)
         return out
+
+    def sysid_rows_prepared(self, u, xobs, skip_missing=False, ini_state=None, estimate_ini=None, weights=None, huber_delta=None, buffers=None, own_x0=False,
+                            who="sysid_step", data_name="xobs"):
+        """SysID.step's least-squares evaluation as a PREPARED call: the keywords of sysid_step are checked once (ValueErrors in the name of `who`, which calls xobs
+        `data_name`), data and weights moved to the device once; the returned rows(theta) is then one launch per call, no check and no host synchronisation
+        (_sysid_rows), and returns sysid_step's packed dict.  theta: [p] shared, [B, p] per sample, or - with estimate_ini and own_x0 - wide rows [B, W] = theta_b |
+        x0_b[idx] as a device tensor: theta is read from them in place (row stride W) and the estimated components are copied into x0, one small device copy.
+        own_x0: the initial states are a tensor of this call's own at a fixed address, started from ini_state or xobs[:, 0] - what wide rows are copied into, and
+        what a caller with another layout of its unknowns writes the estimated components into itself between evaluations.  Returns (rows, held) with held =
+        dict(u, xobs, x0, columns): the device tensors the evaluations read; columns the estimated components as an index tensor (None without own_x0 or them)."""
+        idx, mask = ini_indices(estimate_ini, self.n)
+        wls = wls_arguments(weights, huber_delta, int(u.shape[0]), int(u.shape[1]), self.n) if weights is not None or huber_delta is not None else None
+        if skip_missing:
+            refuse_nan_initial_state(who, xobs, ini_state, data_name)
+        torch = torch_cuda()
+        u, xobs = dev(u), dev(xobs)
+        B, p = u.shape[0], self.p
+        x0 = dev(ini_state).reshape(B, self.n).contiguous() if ini_state is not None else None
+        if own_x0:
+            x0 = (x0 if x0 is not None else xobs[:, 0]).contiguous().clone()
+        if wls is not None and wls[0] is not None:
+            wls = (dev(wls[0]).contiguous(),) + wls[1:]
+        cols = torch.tensor(idx, dtype=torch.int64, device="cuda") if idx and own_x0 else None
+        bufs = buffers if buffers is not None else {}
+
+        def rows(theta):
+            if cols is not None and hasattr(theta, "data_ptr") and theta.dim() == 2 and theta.shape[1] == p + len(idx):
+                x0.index_copy_(1, cols, theta[:, p:])
+                th, tb = theta, p + len(idx)
+            else:
+                th, tb = self._theta(theta, B)
+            return self._sysid_rows(u, xobs, th, tb, x0, bufs, skip_missing, idx, mask, wls)
+        return rows, dict(u=u, xobs=xobs, x0=x0, columns=cols)
 
 
 def load_model(path):

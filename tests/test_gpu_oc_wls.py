@@ -308,3 +308,54 @@ def test_example_method_lm_with_huber_on_corrupted_cartpole_demonstrations():
     accepted = [float(ln.split("loss")[1].split()[0]) for ln in r.stdout.splitlines() if ln.startswith("accepted")]
     assert len(done) == 1 and len(accepted) >= 2 and (np.diff(accepted) <= 0).all() and accepted[-1] < 0.5 * accepted[0], r.stdout[-3000:]      # (seven printed digits)
     assert any("outliers" in ln for ln in r.stdout.splitlines())
+
+
+# ---- the wiring of the Python evaluation: the entry points with hand-built arguments, to the bit ---------------------------------------------------------------------
+@pytest.mark.parametrize("per_sample", [False, True], ids=["shared_theta", "per_sample_theta"])
+@pytest.mark.parametrize("mode", ["gn", "gn_flag", "weights_both"])
+def test_python_evaluation_launches_the_entry_point_with_these_arguments(mode, per_sample):
+    """Cart-pole, B = 5, T = 7, one oc_solve_ms; the rows of ModelLib.oc_rows_prepared's evaluation on the solutions - what oc_pdp_grad and the IRL loops run - are
+    torch.equal to the rows of a direct ctypes call of the mode's entry point on the given (x, lam) with hand-built arguments: both launch the same deterministic
+    kernel.  The loss the kernel writes beside the row is the row's own."""
+    import torch
+    import oc_vjp_common as c
+    from pdp_amd import runtime as rt, zoo
+    mdl = zoo.get("cartpole", "irl")
+    inp = c.make_inputs("cartpole", 5, 7)
+    B, T, n, m, p = 5, 7, mdl.n, mdl.m, mdl.p
+    theta = inp["theta_b"] if per_sample else inp["theta"]
+    s = mdl.oc_solve_ms(inp["x0"], theta, T)
+    assert bool(s["converged"].all())
+    x, u, lam = s["state"], s["control"], s["costate"]
+    demo_x, demo_u = inp["demo_x"].copy(), inp["demo_u"].copy()
+    skip = mode == "gn_flag"
+    if skip:
+        demo_x[:, 1::3, 1] = np.nan
+        demo_u[:, 2::3] = np.nan
+    wx = wu = None
+    if mode == "weights_both":
+        wx = np.broadcast_to(1.0 / (0.5 + np.arange(n)) ** 2, (B, T + 1, n)).copy()
+        wx[:, 1::4, 2] = 0.0
+        wu = np.full((T, m), 0.25)
+        wu[3] = 0.0
+    rows = mdl.oc_rows_prepared(demo_x, demo_u, skip, wx, wu, 0.05 if wx is not None else None)[0]
+    out = rows(u, theta, x=x, lam=lam)
+    got = out["packed_gn"].clone()
+    assert tuple(got.shape) == (B, p + 1 + p * p) and not bool(out["status"].any())
+    th_d = rt.dev(theta).reshape(-1, p)
+    tb, dx_d, du_d = (p if per_sample else 0), rt.dev(demo_x), rt.dev(demo_u)
+    f64 = dict(dtype=torch.float64, device="cuda")
+    packed, loss, status = torch.full((B, p + 1 + p * p), 7.0, **f64), torch.full((B,), 7.0, **f64), torch.zeros((B,), dtype=torch.int32, device="cuda")
+    nbytes = int(mdl.lib.pdp_oc_pdp_workspace_bytes(B, T))
+    ws = torch.empty((max(nbytes, 8) // 8,), **f64)
+    P, st, flags = rt.ptr, rt.current_stream_ptr(), 1 | (32 if skip else 0)
+    if wx is not None:
+        wx_d, wu_d = rt.dev(wx), rt.dev(wu)
+        rc = mdl.lib.pdp_oc_pdp_grad_wls_batched(B, T, flags, None, P(u), P(th_d), tb, P(dx_d), P(du_d), P(wx_d), (T + 1) * n, P(wu_d), 0, 0.05, P(x), P(lam), P(loss),
+                                                 P(packed), P(status), P(ws), nbytes, st)
+    else:
+        rc = mdl.lib.pdp_oc_pdp_grad_batched(B, T, flags | 16, None, P(u), P(th_d), tb, P(dx_d), P(du_d), P(x), P(lam), P(loss), P(packed), None, None, P(status), P(ws),
+                                             nbytes, st)
+    assert rc == 0
+    assert torch.isfinite(packed).all() and float(packed.abs().max()) > 0 and torch.equal(got, packed)
+    assert torch.equal(loss, packed[:, p]) and torch.equal(out["loss"], packed[:, p])

@@ -327,6 +327,67 @@ def test_argument_errors_write_nothing():
         mdl.sysid_step(inputs, sg.mask_states(states), theta, weights=np.ones(n), skip_missing=True)        # row 0 is not observed and no ini_state is given
 
 
+# ---- the wiring of the Python evaluation: every mode's entry point with hand-built arguments, to the bit ---------------------------------------------------------------
+WIRING = [("gn", dict()), ("gn_flag", dict(skip_missing=True)), ("ini", dict(estimate_ini=[1, 3])), ("ini_flag", dict(estimate_ini=[1, 3], skip_missing=True)),
+          ("weights_delta", dict(weights=True, huber_delta=0.05)), ("weights_ini", dict(weights=True, estimate_ini=[1, 3]))]
+
+
+@pytest.mark.parametrize("theta_form", ["shared", "per_sample", "wide_rows"])
+@pytest.mark.parametrize("mode", WIRING, ids=[w[0] for w in WIRING])
+def test_python_evaluation_launches_the_entry_point_with_these_arguments(mode, theta_form):
+    """Cart-pole, B = 5 (odd: the tail of the trajectories-per-workgroup split), T = 7.  The rows of ModelLib.sysid_rows_prepared's evaluation - what sysid_step and the
+    Levenberg-Marquardt loops run - are torch.equal to the rows of a direct ctypes call of the mode's entry point with hand-built arguments: both launch the same
+    deterministic kernel.  theta [p] shared, [B, p] per sample, or wide rows [B, W] = theta_b | x0_b[idx] read in place with stride W (without estimated components
+    W = p: the per-sample rows of a tensor that is passed as it is)."""
+    import torch
+    from pdp_amd import runtime as rt
+    _, kw = mode
+    mdl = model("cartpole")
+    theta = sg.stored("cartpole")[3]
+    B, T, n, p = 5, 7, mdl.n, mdl.p
+    rng = np.random.default_rng(5)                                                  # (the stored recordings are three: five short ones around rest instead)
+    inputs, states = 0.5 * rng.standard_normal((B, T, mdl.m)), 0.1 * rng.standard_normal((B, T + 1, n))
+    skip, idx = kw.get("skip_missing", False), kw.get("estimate_ini", [])
+    W, mask = p + len(idx), sum(1 << i for i in idx)
+    x0 = states[:, 0] + 0.01
+    if skip:
+        states[:, 2::3, 1] = np.nan
+    w = None
+    if kw.get("weights"):
+        w = np.broadcast_to(component_weights(n), (B, T + 1, n)).copy()
+        w[:, 1::4, 2] = 0.0
+    delta = kw.get("huber_delta")
+    theta_b = theta[None] * (1.0 + 0.02 * rng.standard_normal((B, p)))
+    rows, held = mdl.sysid_rows_prepared(inputs, states, skip, x0, idx, w, delta, own_x0=True)
+    if theta_form == "shared":
+        given, th_d, tb = theta, rt.dev(theta), 0
+    elif theta_form == "per_sample":
+        given = th_d = rt.dev(theta_b)
+        tb = p
+    else:
+        given = th_d = rt.dev(np.concatenate([theta_b, x0[:, idx] + 0.02], axis=1))
+        tb = W
+    got = rows(given)["packed_gn"].clone()
+    assert tuple(got.shape) == (B, W + 1 + W * W)
+    x0_d = rt.dev(x0)
+    if theta_form == "wide_rows" and idx:
+        x0_d[:, idx] = th_d[:, p:]
+        assert torch.equal(held["x0"], x0_d)                                          # the estimated components went from the rows into the persistent x0
+    u_d, xo_d = rt.dev(inputs), rt.dev(states)
+    packed, loss = torch.full((B, W + 1 + W * W), 7.0, dtype=torch.float64, device="cuda"), torch.full((B,), 7.0, dtype=torch.float64, device="cuda")
+    P, st, flags = rt.ptr, rt.current_stream_ptr(), 32 if skip else 0
+    if w is not None:
+        w_d = rt.dev(w)
+        rc = mdl.lib.pdp_sysid_step_wls_batched(B, T, P(u_d), P(xo_d), P(x0_d), mask, P(w_d), (T + 1) * n, INF if delta is None else delta, P(th_d), tb, flags, P(loss),
+                                                P(packed), None, 0, st)
+    elif idx:
+        rc = mdl.lib.pdp_sysid_step_gn_ini_batched(B, T, P(u_d), P(xo_d), P(x0_d), mask, P(th_d), tb, flags, P(loss), P(packed), None, 0, st)
+    else:
+        rc = mdl.lib.pdp_sysid_step_gn_batched(B, T, P(u_d), P(xo_d), P(x0_d), P(th_d), tb, flags, P(loss), P(packed), None, 0, st)
+    assert rc == 0
+    assert torch.isfinite(packed).all() and float(packed.abs().max()) > 0 and torch.equal(got, packed)
+
+
 # ---- Levenberg-Marquardt -----------------------------------------------------------------------------------------------------------------------------------------------
 def _print(tag, orc, r):
     print("%s\n  oracle %d evaluations, %d rejected: %s\n  GPU    %d evaluations, %d rejected: %s" % (tag, orc["evaluations"], orc["rejected"], " ".join("%.3e" % v for v in orc["loss_trace"]),

@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+import ls_rows_common as lr
 import sysid_gn_common as sg
 
 ROOT = sg.ROOT
@@ -67,42 +68,11 @@ def test_oracle_lm_schedule_reproduces_the_evaluation_counts(k):
     assert r["loss_trace"][-1] <= 1e-16 and (np.diff(r["loss_trace"]) < 0).all()
 
 
-class _Recorder:
-    """stands in for the foreign library: records every call and answers 0"""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def f(*args):
-            self.calls.append((name, args))
-            return 0
-        return f
-
-
 def test_sysid_step_with_default_arguments_is_todays_call(monkeypatch):
     """no GPU: tensors are replaced by a stand-in, the library by a recorder.  The default call passes today's eleven arguments to pdp_sysid_step_ws_batched and never
     touches the new entry point; each of the three new arguments alone goes to pdp_sysid_step_gn_batched with the flags it asks for."""
-    import torch
-    from pdp_amd import runtime
-
-    class _Torch:                                   # torch on the CPU under the names the runtime uses
-        float64 = torch.float64
-
-        class cuda:
-            @staticmethod
-            def is_current_stream_capturing():
-                return False
-
-        @staticmethod
-        def empty(shape, dtype=None, device=None):
-            return torch.zeros(shape, dtype=dtype)
-        zeros = staticmethod(lambda shape, dtype=None, device=None: torch.zeros(shape, dtype=dtype))
-    monkeypatch.setattr(runtime, "torch_cuda", lambda: _Torch)
-    monkeypatch.setattr(runtime, "dev", lambda a: a if hasattr(a, "data_ptr") else torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=float))))
-    monkeypatch.setattr(runtime, "current_stream_ptr", lambda: None)
-    mdl = runtime.ModelLib.__new__(runtime.ModelLib)
-    mdl.n, mdl.m, mdl.p, mdl.lib = 4, 1, 3, _Recorder()
+    lr.stand_in_torch(monkeypatch)
+    mdl = lr.stand_in_model()
     B, T = 3, 6
     u, xo, th = np.zeros((B, T, 1)), np.zeros((B, T + 1, 4)), np.ones(3)
     loss, grad = mdl.sysid_step(u, xo, th)
