@@ -755,6 +755,26 @@ class SysID(_CasadiFrontEnd):
         x = self.model().sysid_integrate(_vec(ini_state)[None], np.asarray(inputs, float).reshape(1, -1, self.n_control), _vec(auxvar_value))
         return _np(x)[0]
 
+    def integrateDyn_batch(self, ini_state, inputs, auxvar_value):
+        """integrateDyn for a batch, one launch: ini_state [B, n], inputs [B, T, m], auxvar_value [p] or [B, p] (arrays or tensors) -> the rollouts [B, T+1, n], a
+        CUDA tensor.  Shape errors are ValueErrors before any launch."""
+        shape = lambda a: tuple(int(k) for k in (a.shape if hasattr(a, "shape") else np.shape(a)))
+        su = shape(inputs)
+        if len(su) != 3 or su[2] != self.n_control or su[0] < 1 or su[1] < 1:
+            raise ValueError("integrateDyn_batch: inputs must be [B, T, m] with m = %d and B, T >= 1, got %s" % (self.n_control, su))
+        if shape(ini_state) != (su[0], self.n_state):
+            raise ValueError("integrateDyn_batch: ini_state must be [B, n] = %s, got %s" % ((su[0], self.n_state), shape(ini_state)))
+        if shape(auxvar_value) not in ((self.n_auxvar,), (su[0], self.n_auxvar)):
+            raise ValueError("integrateDyn_batch: auxvar_value must be [p] or [B, p] with p = %d, B = %d, got %s" % (self.n_auxvar, su[0], shape(auxvar_value)))
+        return self.model().sysid_integrate(ini_state, inputs, auxvar_value)
+
+    def rollout_vjp_batch(self, state_traj, inputs, auxvar_value, grad_state, want_ini=True):
+        """The gradient of ANY scalar loss L(state_traj) of the rollouts state_traj = integrateDyn_batch(ini_state, inputs, auxvar_value), for a batch: grad_state
+        [B, T+1, n] = dL/dstate_traj (a cotangent, e.g. from torch.autograd.grad) -> dict(grad_theta [B, p] = dL/dauxvar per trajectory, grad_x0 [B, n] = dL/dini_state
+        with want_ini) by the adjoint sweep lam_t = g_t + F_t' lam_{t+1}, grad += E_t' lam_{t+1} in one launch (include/pdp_hip_sysid_vjp.h).  step_batch's gradient is
+        the special case grad_state = state_traj - batch_states.  pdp_amd.autograd.sysid_trajectory wraps rollout + this call as a torch.autograd layer."""
+        return self.model().sysid_rollout_vjp(state_traj, inputs, auxvar_value, grad_state, want_ini=want_ini)
+
     def getAuxSys(self, state_traj, control_traj, auxvar_value):                # PDP.py:1225-1239
         F, E = self.model().sysid_auxsys(np.asarray(state_traj, float)[None], np.asarray(control_traj, float).reshape(1, -1, self.n_control),
                                          _vec(auxvar_value))

@@ -8,6 +8,7 @@
 #include "../../include/pdp_hip_sysid_ini.h"
 #include "../../include/pdp_hip_sysid_wls.h"
 #include "../../include/pdp_hip_oc_wls.h"
+#include "../../include/pdp_hip_sysid_vjp.h"
 #ifndef PDP_MODEL_HEADER
 #error "compile with -DPDP_MODEL_HEADER=\"generated/<model>.h\""
 #endif
@@ -25,6 +26,7 @@ namespace pdp { extern __device__ long long g_rb_stamp[16]; }
 #include "pdp_fused3_kernels.h"
 #include "pdp_cp_pair_kernels.h"
 #include "pdp_cp_generic_kernels.h"
+#include "pdp_sysid_vjp_kernels.h"
 #include "pdp_launch.h"
 
 using namespace pdp;
@@ -655,6 +657,21 @@ int sysid_step(int B, int T, const double* u, const double* xobs, const double* 
     } else { return Mdl::KIND == PDP_KIND_SYSID ? PDP_E_SIZE : PDP_E_MODE; }
 }
 
+// The rollout's vector-Jacobian product (pdp_sysid_rollout_vjp_batched, include/pdp_hip_sysid_vjp.h): one launch of sysid_vjp_kernel on the given trajectory.  The
+// argument checks come first, whatever the model; the kernel exists for n <= 64 and p <= 512 (eight parameter slots per lane).
+template <class Mdl>
+int sysid_rollout_vjp(int B, int T, const double* x, const double* u, const double* th, int tb, const double* gx, double* grad_theta, double* grad_x0, void* st) {
+    if (B <= 0 || T <= 0 || !x || !u || !th || !gx || (!grad_theta && !grad_x0) || (tb != 0 && tb < Mdl::NP)) return PDP_E_ARG;
+    if constexpr (Mdl::KIND != PDP_KIND_SYSID) return PDP_E_MODE;
+    else if constexpr (Mdl::NX > 64 || Mdl::NP > 512) return PDP_E_SIZE;
+    else {
+        const int rows = sysid_vjp_rows<Mdl>(B, device_cu_count());
+        const size_t lds = sizeof(double) * (size_t)sysid_vjp_slice<Mdl>(rows);
+        if (lds > 150 * 1024) return PDP_E_SIZE;
+        return launch(sysid_vjp_kernel<Mdl>, dim3(B), dim3(64), lds, S(st), B, T, x, u, th, tb, gx, grad_theta, grad_x0, rows);
+    }
+}
+
 template <class Mdl> int nnz_path() { return Mdl::PATH_NVAR; }
 
 // what the Gauss-Newton entry points of SysID.step check first: sizes, the pointers every one of them needs, no flag but PDP_GRAD_SKIP_MISSING
@@ -790,6 +807,10 @@ int pdp_sysid_step_wls_batched(int B, int T, const double* u, const double* x_ob
                        (flags & PDP_GRAD_SKIP_MISSING) ? 1 : 0};
     return mask ? sysid_step<PdpModel, PDP_SYSID_GN_W_INI>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0, mask, wls)
                 : sysid_step<PdpModel, PDP_SYSID_GN_W>(B, T, u, x_obs, theta, tb, loss, packed, workspace, workspace_bytes, stream, x0, 0u, wls);
+}
+int pdp_sysid_rollout_vjp_batched(int B, int T, const double* x, const double* u, const double* theta, int tb, const double* grad_x, double* grad_theta,
+                                  double* grad_x0, void* stream) {
+    return sysid_rollout_vjp<PdpModel>(B, T, x, u, theta, tb, grad_x, grad_theta, grad_x0, stream);
 }
 int pdp_oc_pdp_grad_wls_batched(int B, int T, int flags, const double* x0, const double* u, const double* theta, int theta_bstride, const double* demo_x,
                                 const double* demo_u, const double* weights_x, int64_t weights_x_bstride, const double* weights_u, int64_t weights_u_bstride,

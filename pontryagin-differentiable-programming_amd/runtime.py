@@ -85,6 +85,7 @@ MODEL_EXT_SYMBOLS = ["pdp_sysid_step_gn_batched"]        # declared in the exten
 MODEL_INI_SYMBOLS = ["pdp_sysid_step_gn_ini_batched"]   # include/pdp_hip_sysid_ini.h: one list per extension header
 MODEL_WLS_SYMBOLS = ["pdp_sysid_step_wls_batched"]      # include/pdp_hip_sysid_wls.h
 MODEL_OC_WLS_SYMBOLS = ["pdp_oc_pdp_grad_wls_batched"]  # include/pdp_hip_oc_wls.h
+MODEL_VJP_SYMBOLS = ["pdp_sysid_rollout_vjp_batched"]   # include/pdp_hip_sysid_vjp.h
 
 _core = None
 
@@ -568,6 +569,8 @@ _MODEL_SIGS = {
     "pdp_sysid_step_wls_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _I64, C.c_double, _VP, _I, _I, _VP, _VP, _VP, _I64, _VP]),
     # include/pdp_hip_oc_wls.h
     "pdp_oc_pdp_grad_wls_batched": (_I, [_I, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I64, _VP, _I64, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    # include/pdp_hip_sysid_vjp.h
+    "pdp_sysid_rollout_vjp_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
 }
 _models = {}
 
@@ -1228,6 +1231,43 @@ class ModelLib:
         E = torch.empty((B, T, self.n, self.p), dtype=torch.float64, device="cuda")
         check(self.lib.pdp_sysid_auxsys_batched(B, T, ptr(x), ptr(u), ptr(th), tb, ptr(F), ptr(E), current_stream_ptr()), "pdp_sysid_auxsys_batched")
         return F, E
+
+    def sysid_rollout_vjp(self, x, u, theta, grad_x, want_ini=True, want_theta=True):
+        """The rollout as a vector-Jacobian product (pdp_sysid_rollout_vjp_batched, include/pdp_hip_sysid_vjp.h: the semantics): x [B, T+1, n] the rollout of
+        sysid_integrate for u [B, T, m] and theta ([p] or [B, p]), grad_x [B, T+1, n] = dL/dx of any scalar loss L -> dict(grad_theta [B, p] = dL/dtheta per trajectory,
+        grad_x0 [B, n] = dL/dx_0), one launch of the adjoint sweep.  want_ini / want_theta = False: that output is not computed (not both).  Shape errors are
+        ValueErrors before any launch."""
+        shape = lambda a: tuple(int(k) for k in (a.shape if hasattr(a, "shape") else np.shape(a)))
+        su = shape(u)
+        if len(su) != 3 or su[2] != self.m or su[0] < 1 or su[1] < 1:
+            raise ValueError("sysid_rollout_vjp: inputs must be [B, T, %d] with B, T >= 1, got %s" % (self.m, su))
+        B, T = su[0], su[1]
+        for name, a in (("state_traj", x), ("grad_state", grad_x)):
+            if shape(a) != (B, T + 1, self.n):
+                raise ValueError("sysid_rollout_vjp: %s must be [B, T+1, n] = %s, got %s" % (name, (B, T + 1, self.n), shape(a)))
+        if shape(theta) not in ((self.p,), (1, self.p), (B, self.p)):
+            raise ValueError("sysid_rollout_vjp: theta must be [p] or [B, p] with p = %d, B = %d, got %s" % (self.p, B, shape(theta)))
+        if not (want_ini or want_theta):
+            raise ValueError("sysid_rollout_vjp: want_theta and want_ini are both False - nothing to compute")
+        torch = torch_cuda()
+        x, u, g, th = dev(x), dev(u), dev(grad_x), dev(theta)
+        tb = self.p if (th.dim() == 2 and th.shape[0] == B and B > 1) else 0
+        out = {}
+        if want_theta:
+            out["grad_theta"] = torch.empty((B, self.p), dtype=torch.float64, device="cuda")
+        if want_ini:
+            out["grad_x0"] = torch.empty((B, self.n), dtype=torch.float64, device="cuda")
+        check(self.lib.pdp_sysid_rollout_vjp_batched(B, T, ptr(x), ptr(u), ptr(th), tb, ptr(g), ptr(out["grad_theta"]) if want_theta else None,
+                                                     ptr(out["grad_x0"]) if want_ini else None, current_stream_ptr()), "pdp_sysid_rollout_vjp_batched")
+        return out
+
+    def sysid_vjp_rows(self, B, cus):
+        """pool rows (time steps per Jacobian pass) of sysid_rollout_vjp's kernel for a batch of B on a chip of `cus` compute units: the host's rule
+        (sysid_vjp_rows, csrc/pdp_sysid_vjp_kernels.h) restated - the chunk edges the tests aim at"""
+        if B <= 4 * cus:
+            return self.chunk
+        fit = 2400 // ((self.nnz_path + self.n) | 1)
+        return min(fit, self.chunk) if fit >= 4 else self.chunk
 
     def _sysid_workspace(self, B, T):
         """(workspace tensor or None, its bytes) of the fused SysID.step entry points"""
