@@ -14,6 +14,7 @@ import numpy
 import numpy as np
 
 from . import codegen, runtime, sx
+from .abi import PDP_STATUS_PIVOT
 from .sx import SX, jacobian, dot, vcat, mtimes, tanh
 
 
@@ -378,7 +379,7 @@ class LQR:
             Hxu=self._tv(self.Hxu, "Hxu", n, m), Hxe=self._tv(self.Hxe, "Hxe", n, p), Hue=self._tv(self.Hue, "Hue", m, p),
             X0=numpy.asarray(self.ini_x, float).reshape(n, p), T=int(horizon))
         st = int(status[0])
-        if st & 2:
+        if st & PDP_STATUS_PIVOT:
             raise numpy.linalg.LinAlgError("Singular matrix")           # what numpy.linalg.inv raises in the reference (PDP.py:566, 575)
         X, U, Lam = _np(X)[0], _np(U)[0], _np(Lam)[0]
         return {"state_traj_opt": [x for x in X], "control_traj_opt": [u for u in U], "costate_traj_opt": [l for l in Lam],

@@ -24,6 +24,7 @@ one launch of pdp_lm_update_batched (csrc/pdp_lm_kernels.h) does for all of them
 import numpy as np
 
 from . import runtime as rt
+from .abi import PDP_MS_PREDICT_REJECTED, PDP_MS_RESTORED, PDP_MS_SOC, PDP_MS_WATCHDOG
 
 
 class _DeviceLoop:
@@ -201,7 +202,7 @@ def arrow_normal_equations(rows, p, q):
 def bad_irl_samples(solve, out):
     """The samples of an IRL evaluation that must not be used, bool [B] on the device (no synchronisation): the solve did not converge, it set a status bit other than
     the informational ones, or the fused unit set a status bit.  solve: the dict of oc_solve_ms, out: the dict of the unit."""
-    informational = 128 | 512 | 1024 | 2048          # PDP_MS_RESTORED, PDP_MS_PREDICT_REJECTED, PDP_MS_SOC, PDP_MS_WATCHDOG
+    informational = PDP_MS_RESTORED | PDP_MS_PREDICT_REJECTED | PDP_MS_SOC | PDP_MS_WATCHDOG
     return (solve["converged_flags"] == 0) | ((solve["status"] & ~informational) != 0) | (out["status"] != 0)
 
 

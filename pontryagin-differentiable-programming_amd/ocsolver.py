@@ -25,6 +25,8 @@ Hessians: the full Hamiltonian Hessians give Newton's method (quadratic converge
 import numpy as np
 
 from . import runtime
+from .abi import (PDP_MS_INERTIA, PDP_MS_MAXITER, PDP_MS_RESTORATION, PDP_MS_RESTORED, PDP_MS_SOC, PDP_STATUS_INDEFINITE, PDP_STATUS_NONFINITE,
+                  PDP_STATUS_PIVOT)
 
 # stationarity residual (relative to the control magnitude) below which a sample switches from Gauss-Newton to Newton steps
 # (swept on 256-problem batches of cart-pole / robot arm / quadrotor: switching earlier stalls the swing-up problems)
@@ -181,7 +183,7 @@ def solve_batch_ms_generic(oc, ini_state, horizon, auxvar_value, tol=1e-10, max_
             hxx, E = A["hxx"] + dw.view(B, 1, 1) * eye_n, r["c"].unsqueeze(-1).contiguous()
         X, U, L, st = runtime.lqr_solve(A["dynF"], A["dynG"], Hxx, Huu, hxx, r["rx"][:, T].unsqueeze(-1).contiguous(), E=E, Hxu=Hxu,
                                         Hxe=r["rx"][:, :T].unsqueeze(-1).contiguous(), Hue=r["ru"].unsqueeze(-1).contiguous(), T=T)
-        return X[..., 0], U[..., 0], L[..., 0], (st & (256 | 2 | 1)) == 0
+        return X[..., 0], U[..., 0], L[..., 0], (st & (PDP_STATUS_INDEFINITE | PDP_STATUS_PIVOT | PDP_STATUS_NONFINITE)) == 0
 
     def put(dst, src, mask):
         dst.copy_(torch.where(mask.view(-1, *([1] * (dst.dim() - 1))), src, dst))
@@ -215,13 +217,13 @@ def solve_batch_ms_generic(oc, ini_state, horizon, auxvar_value, tol=1e-10, max_
         scale = 1.0 + torch.maximum(x.abs().amax((1, 2)), u.abs().amax((1, 2)))
         lscale = 1.0 + lam.abs().amax((1, 2))
         fin = torch.isfinite(r["f"]) & torch.isfinite(r["inf_pr"]) & torch.isfinite(r["inf_du"])
-        status = torch.where(active & ~fin, status | 1, status)                                                      # PDP_STATUS_NONFINITE
+        status = torch.where(active & ~fin, status | PDP_STATUS_NONFINITE, status)
         conv = conv | (active & fin & (r["inf_pr"] <= tol * scale) & (r["inf_du"] <= tol * lscale))
         active = ~conv & (status == 0)
         if not bool(active.any()):
             break
         if it == max_iter:
-            status = torch.where(active, status | 8, status)                                                         # PDP_MS_MAXITER
+            status = torch.where(active, status | PDP_MS_MAXITER, status)
             break
         iters = torch.where(active, iters + 1, iters)
         # ---- search direction with inertia correction (Algorithm IC), every sample on its own dw
@@ -239,7 +241,7 @@ def solve_batch_ms_generic(oc, ini_state, horizon, auxvar_value, tol=1e-10, max_
             dw_new = torch.where(dw == 0.0, torch.where(first, torch.full_like(dw, 1e-4), (dw_last / 3.0).clamp(min=1e-20)), dw * torch.where(first, 100.0, 8.0))
             dw = torch.where(need, dw_new, dw)
             dead = need & (dw > 1e20)
-            status = torch.where(dead, status | 16, status)                                                          # PDP_MS_INERTIA
+            status = torch.where(dead, status | PDP_MS_INERTIA, status)
             need = need & ~dead
             if not bool(need.any()):
                 break
@@ -315,12 +317,12 @@ def solve_batch_ms_generic(oc, ini_state, horizon, auxvar_value, tol=1e-10, max_
         if bool(failed.any()):
             # ---- restoration (oracle/ipopt_ms.py: solve; include/pdp_hip.h): current point into the filter, states <- rollout of the controls, multipliers reset
             can = failed & (theta > 0.0) if restoration else torch.zeros_like(failed)
-            status = torch.where(failed & ~can, status | 4, status)                                                   # PDP_MS_RESTORATION
+            status = torch.where(failed & ~can, status | PDP_MS_RESTORATION, status)
             if bool(can.any()):
                 filter_add(can, theta, f)
                 xr, _ = mdl.oc_rollout(x0, u, th, want_cost=False)
                 finr = torch.isfinite(xr).all(dim=(1, 2))
-                status = torch.where(can & ~finr, status | 4, status)
+                status = torch.where(can & ~finr, status | PDP_MS_RESTORATION, status)
                 can = can & finr
                 put(x, xr, can)
                 put(lam, torch.zeros_like(lam), can)
@@ -333,8 +335,8 @@ def solve_batch_ms_generic(oc, ini_state, horizon, auxvar_value, tol=1e-10, max_
                 restored = restored | can
         if print_level > 0:
             print("  ms-generic iteration %3d: %d / %d converged" % (it, int(conv.sum()), B))
-    status = torch.where(restored, status | 128, status)                                                             # PDP_MS_RESTORED (informational)
-    status = torch.where(corrected, status | 1024, status)                                                           # PDP_MS_SOC (informational)
+    status = torch.where(restored, status | PDP_MS_RESTORED, status)                                                 # (informational)
+    status = torch.where(corrected, status | PDP_MS_SOC, status)                                                     # (informational)
     out = {"state": x, "control": u, "costate": lam, "cost": r["f"], "resid": torch.stack([r["inf_pr"], r["inf_du"]], dim=1), "converged": conv,
            "iterations": iters, "status": status}
     if log is not None:

@@ -1,4 +1,5 @@
-"""ctypes binding of the C-ABI in include/pdp_hip.h + torch tensor plumbing (device memory, streams).
+"""ctypes binding of the C-ABI in include/*.h + torch tensor plumbing (device memory, streams).  abi.py mirrors the headers (structures, constants, the table of entry
+points); the structures, PDP_E and LM_STATES are re-exported here for the callers that always found them here.
 
 PyTorch is used for HBM allocation / stream handles only; every arithmetic result of the hot path comes
 from the HIP kernels in libpdp_hip.so / libpdp_model_*.so.  There is NO CPU fallback: if the shared
@@ -9,83 +10,14 @@ import os
 
 import numpy as np
 
+from .abi import (LM_STATES, PDP_E, PDP_E_SIZE, PDP_GRAD_GAUSS_NEWTON, PDP_GRAD_SKIP_MISSING, PDP_MS_FROM_CONTROLS, PDP_MS_NO_RESTORATION,  # noqa: F401
+                  PDP_MS_PREDICT, PDP_MS_PREDICT_GUARD, PDP_MS_PREDICT_PRIMAL, PDP_MS_WARM, PDP_MS_WITH_SOC, PDP_MS_WITH_WATCHDOG, PDP_OC_COTANGENT, PDP_OC_GIVEN_TRAJ,
+                  PDP_OC_PACKED, PDP_OC_RECORD_PRIMAL, PDP_POLICY_MLP, PDP_POLICY_POLY, PDP_POLICY_TABLE, PdpLmPrior, PdpLmSchedule, PdpLmState, PdpLqrProblem, PdpMat,
+                  PdpModelInfo, PdpOcAuxsys, PdpOcMsOpts, PdpOcSensOut, PdpOcSolveOpts, PdpPolicy, entry_points)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
 CORE_LIB = os.path.join(LIB_DIR, "libpdp_hip.so")
-
-PDP_E = {-1: "PDP_E_ARG (null pointer / bad size)", -2: "PDP_E_SIZE (dimension outside kernel limits)",
-         -3: "PDP_E_LAUNCH (HIP launch failed)", -4: "PDP_E_MODE (entry point not provided by this model kind)"}
-
-
-class PdpMat(C.Structure):
-    _fields_ = [("ptr", C.c_void_p), ("bstride", C.c_int64), ("tstride", C.c_int64)]
-
-
-class PdpLqrProblem(C.Structure):
-    _fields_ = [("B", C.c_int), ("T", C.c_int), ("n", C.c_int), ("m", C.c_int), ("p", C.c_int)] + \
-               [(k, PdpMat) for k in ("F", "G", "E", "Hxx", "Hxu", "Hxe", "Huu", "Hue", "hxx", "hxe", "X0")]
-
-
-class PdpModelInfo(C.Structure):
-    _fields_ = [("kind", C.c_int), ("n", C.c_int), ("m", C.c_int), ("p", C.c_int), ("nnz_path", C.c_int), ("chunk", C.c_int),
-                ("name", C.c_char_p)]
-
-
-class PdpOcAuxsys(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("dynF", "dynG", "dynE", "Hxx", "Hxu", "Hxe", "Hux", "Huu", "Hue", "hxx", "hxe", "dHu", "Huu_damp")]
-
-
-class PdpOcSolveOpts(C.Structure):
-    _fields_ = [("tol", C.c_double), ("newton_switch", C.c_double), ("max_iter", C.c_int), ("check_every", C.c_int), ("ls_trials", C.c_int),
-                ("straggler_patience", C.c_int), ("print_level", C.c_int)]
-
-
-class PdpOcMsOpts(C.Structure):
-    _fields_ = [("tol", C.c_double), ("max_iter", C.c_int), ("flags", C.c_int), ("log_rows", C.c_int), ("dtheta_bstride", C.c_int),
-                ("dtheta", C.c_void_p), ("dxdp", C.c_void_p), ("dudp", C.c_void_p), ("riccati", C.c_void_p), ("predict_record", C.c_void_p)]
-
-
-class PdpOcSensOut(C.Structure):
-    _fields_ = [("dxdp", C.c_void_p), ("dudp", C.c_void_p), ("riccati", C.c_void_p), ("predict_record", C.c_void_p)]
-
-
-class PdpLmSchedule(C.Structure):                  # include/pdp_hip_lm.h
-    _fields_ = [("up", C.c_double), ("down", C.c_double), ("lam_min", C.c_double), ("lam_max", C.c_double), ("loss_tol", C.c_double), ("max_evals", C.c_int32)]
-
-
-class PdpLmState(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("theta", "trial", "lam", "current", "state", "evaluations", "rejected", "accepted", "accepted_now", "loss_trace",
-                                          "lambda_trace", "parameter_trace")] + [("trace_len", C.c_int64), ("counters", C.c_void_p)]
-
-
-class PdpLmPrior(C.Structure):                     # include/pdp_hip_lm_prior.h
-    _fields_ = [("mean", C.c_void_p), ("precision", C.c_void_p), ("kind", C.c_int32), ("mean_kstride", C.c_int64), ("precision_kstride", C.c_int64),
-                ("prior_loss", C.c_void_p)]
-
-
-class PdpPolicy(C.Structure):
-    _fields_ = [("kind", C.c_int), ("n_pivots", C.c_int), ("pivots", C.c_double * 16), ("n_layers", C.c_int), ("sizes", C.c_int * 16), ("n_basis", C.c_int),
-                ("table", C.c_void_p)]
-
-
-CORE_SYMBOLS = ["pdp_hip_version", "pdp_lqr_workspace_bytes", "pdp_lqr_solve_batched", "pdp_cp_aux_integrate_batched",
-                "pdp_sysid_aux_integrate_batched", "pdp_gd_update_batched"]
-MODEL_SYMBOLS = ["pdp_model_get_info", "pdp_oc_rollout_batched", "pdp_oc_rollout_feedback_batched", "pdp_oc_costate_batched", "pdp_oc_ms_residuals_batched",
-                 "pdp_oc_auxsys_batched",
-                 "pdp_oc_solve_workspace_bytes", "pdp_oc_solve_batched", "pdp_oc_solve_ms_workspace_bytes", "pdp_oc_solve_ms_batched",
-                 "pdp_oc_pdp_workspace_bytes", "pdp_oc_pdp_grad_batched", "pdp_oc_riccati_doubles", "pdp_oc_predict_record_floats", "pdp_oc_pdp_grad_sens_batched",
-                 "pdp_oc_predict_batched", "pdp_oc_predict_record_batched",
-                 "pdp_cp_integrate_batched", "pdp_cp_auxsys_batched",
-                 "pdp_cp_step_workspace_bytes", "pdp_cp_step_batched", "pdp_sysid_integrate_batched", "pdp_sysid_auxsys_batched", "pdp_sysid_step_batched",
-                 "pdp_sysid_step_workspace_bytes", "pdp_sysid_step_ws_batched"]
-CORE_EXT_SYMBOLS = ["pdp_lm_update_batched"]             # declared in the extension header include/pdp_hip_lm.h, exported by libpdp_hip.so
-CORE_LM_PRIOR_SYMBOLS = ["pdp_lm_update_prior_batched", "pdp_lm_covariance_batched"]      # include/pdp_hip_lm_prior.h, exported by libpdp_hip.so
-MODEL_EXT_SYMBOLS = ["pdp_sysid_step_gn_batched"]        # declared in the extension headers (include/pdp_hip_sysid_gn.h): include/pdp_hip.h is pinned at its entry points
-
-MODEL_INI_SYMBOLS = ["pdp_sysid_step_gn_ini_batched"]   # include/pdp_hip_sysid_ini.h: one list per extension header
-MODEL_WLS_SYMBOLS = ["pdp_sysid_step_wls_batched"]      # include/pdp_hip_sysid_wls.h
-MODEL_OC_WLS_SYMBOLS = ["pdp_oc_pdp_grad_wls_batched"]  # include/pdp_hip_oc_wls.h
-MODEL_VJP_SYMBOLS = ["pdp_sysid_rollout_vjp_batched"]   # include/pdp_hip_sysid_vjp.h
 
 _core = None
 
@@ -110,25 +42,9 @@ def load_core():
             raise RuntimeError("libpdp_hip.so not built (%s): run `python -c 'import __graft_entry__ as g; g.build()'`; "
                                "there is no CPU fallback" % CORE_LIB)
         lib = _dlopen(CORE_LIB)
-        lib.pdp_hip_version.restype = C.c_char_p
-        lib.pdp_lqr_workspace_bytes.restype = C.c_int64
-        lib.pdp_lqr_workspace_bytes.argtypes = [C.c_int] * 6
-        lib.pdp_lqr_solve_batched.restype = C.c_int
-        lib.pdp_lqr_solve_batched.argtypes = [C.POINTER(PdpLqrProblem), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_int64, C.c_void_p]
-        lib.pdp_cp_aux_integrate_batched.restype = C.c_int
-        lib.pdp_cp_aux_integrate_batched.argtypes = [C.c_int] * 5 + [C.c_void_p] * 7 + [C.c_void_p]
-        lib.pdp_sysid_aux_integrate_batched.restype = C.c_int
-        lib.pdp_sysid_aux_integrate_batched.argtypes = [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_void_p]
-        lib.pdp_gd_update_batched.restype = C.c_int
-        lib.pdp_gd_update_batched.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 4 + \
-                                             [C.c_int64, C.c_void_p, C.c_void_p]
-        lib.pdp_lm_update_batched.restype = C.c_int
-        lib.pdp_lm_update_batched.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PdpLmSchedule), C.POINTER(PdpLmState), C.c_void_p]
-        lib.pdp_lm_update_prior_batched.restype = C.c_int
-        lib.pdp_lm_update_prior_batched.argtypes = lib.pdp_lm_update_batched.argtypes[:-1] + [C.POINTER(PdpLmPrior), C.c_void_p]
-        lib.pdp_lm_covariance_batched.restype = C.c_int
-        lib.pdp_lm_covariance_batched.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        for name, (res, args) in entry_points(library="core").items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
         _core = lib
     return _core
 
@@ -152,9 +68,6 @@ def gd_update(loss, grad, lr, theta, dtheta, counters, status=None, converged=No
         assert parameter_trace.is_contiguous() and parameter_trace.shape[1] == p
     check(load_core().pdp_gd_update_batched(B, p, ptr(loss), ptr(grad), int(grad.stride(0)), ptr(status), ptr(converged), ptr(iterations), float(lr), ptr(theta), ptr(dtheta),
                                             ptr(loss_trace), ptr(parameter_trace), int(tl), ptr(counters), current_stream_ptr()), "pdp_gd_update_batched")
-
-
-LM_STATES = ["START", "ACTIVE", "CONVERGED", "STALLED", "BUDGET", "FAILED"]          # PDP_LM_* of include/pdp_hip_lm.h
 
 
 def _lm_structs(theta, trial, lam, current, state, evaluations, rejected, accepted, counters, up, down, lam_min, lam_max, loss_tol, max_evals, bad, accepted_now,
@@ -533,45 +446,6 @@ def packed_row_from_sensitivities(packed, sides, rule, delta=float("inf"), skip_
 # ------------------------------------------------------------------------------------------------------
 # per-model libraries (section B of include/pdp_hip.h)
 # ------------------------------------------------------------------------------------------------------
-_VP, _I, _I64 = C.c_void_p, C.c_int, C.c_int64
-_MODEL_SIGS = {
-    "pdp_model_get_info": (None, [C.POINTER(PdpModelInfo)]),
-    "pdp_oc_rollout_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
-    "pdp_oc_costate_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _VP]),
-    "pdp_oc_ms_residuals_batched": (_I, [_I, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
-    "pdp_oc_rollout_feedback_batched": (_I, [_I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
-    "pdp_oc_auxsys_batched": (_I, [_I, _I, _VP, _VP, _VP, _VP, _I, C.POINTER(PdpOcAuxsys), _VP]),
-    "pdp_oc_solve_workspace_bytes": (_I64, [_I, _I, _I]),
-    "pdp_oc_solve_batched": (_I, [_I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(PdpOcSolveOpts), C.POINTER(C.c_int), _VP, _I64, _VP]),
-    "pdp_oc_solve_ms_workspace_bytes": (_I64, [_I, _I, _I]),
-    "pdp_oc_solve_ms_batched": (_I, [_I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(PdpOcMsOpts), _VP, _I64, _VP]),
-    "pdp_oc_pdp_workspace_bytes": (_I64, [_I, _I]),
-    "pdp_oc_pdp_grad_batched": (_I, [_I, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
-    "pdp_oc_riccati_doubles": (_I64, []),
-    "pdp_oc_predict_record_floats": (_I64, []),
-    "pdp_oc_pdp_grad_sens_batched": (_I, [_I, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(PdpOcSensOut), _VP, _VP, _I64, _VP]),
-    "pdp_oc_predict_batched": (_I, [_I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "pdp_oc_predict_record_batched": (_I, [_I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
-    "pdp_cp_integrate_batched": (_I, [_I, _I, C.POINTER(PdpPolicy), _I, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
-    "pdp_cp_auxsys_batched": (_I, [_I, _I, C.POINTER(PdpPolicy), _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    "pdp_cp_step_workspace_bytes": (_I64, [_I, _I, C.POINTER(PdpPolicy), _I]),
-    "pdp_cp_step_batched": (_I, [_I, _I, C.POINTER(PdpPolicy), _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
-    "pdp_sysid_integrate_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _VP]),
-    "pdp_sysid_auxsys_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
-    "pdp_sysid_step_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
-    "pdp_sysid_step_workspace_bytes": (_I64, [_I, _I]),
-    "pdp_sysid_step_ws_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I64, _VP]),
-    # include/pdp_hip_sysid_gn.h
-    "pdp_sysid_step_gn_batched": (_I, [_I, _I, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I64, _VP]),
-    # include/pdp_hip_sysid_ini.h
-    "pdp_sysid_step_gn_ini_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _I, _I, _VP, _VP, _VP, _I64, _VP]),
-    # include/pdp_hip_sysid_wls.h
-    "pdp_sysid_step_wls_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _I64, C.c_double, _VP, _I, _I, _VP, _VP, _VP, _I64, _VP]),
-    # include/pdp_hip_oc_wls.h
-    "pdp_oc_pdp_grad_wls_batched": (_I, [_I, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I64, _VP, _I64, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
-    # include/pdp_hip_sysid_vjp.h
-    "pdp_sysid_rollout_vjp_batched": (_I, [_I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
-}
 _models = {}
 
 
@@ -581,19 +455,19 @@ def make_policy(kind, pivots=None, layers=None, table=None):
     device tensor alive through the returned struct (pol._table)."""
     pol = PdpPolicy()
     if kind == "poly":
-        pol.kind = 0
+        pol.kind = PDP_POLICY_POLY
         pol.n_pivots = len(pivots)
         assert pol.n_pivots <= 16, "at most 16 Lagrange pivots"
         for i, v in enumerate(pivots):
             pol.pivots[i] = float(v)
     elif kind == "table":
-        pol.kind = 2
+        pol.kind = PDP_POLICY_TABLE
         pol._table = dev(np.ascontiguousarray(np.asarray(table, dtype=float)))
         assert pol._table.dim() == 2
         pol.n_basis = int(pol._table.shape[1])
         pol.table = pol._table.data_ptr()
     else:
-        pol.kind = 1
+        pol.kind = PDP_POLICY_MLP
         pol.n_layers = len(layers)
         assert pol.n_layers <= 16, "at most 16 weight layers"
         for i, v in enumerate(layers):
@@ -609,7 +483,7 @@ class ModelLib:
             raise RuntimeError("model library %s not built; there is no CPU fallback" % path)
         self.path = path
         self.lib = _dlopen(path)
-        for name, (res, args) in _MODEL_SIGS.items():
+        for name, (res, args) in entry_points(library="model").items():
             fn = getattr(self.lib, name)
             fn.restype, fn.argtypes = res, args
         info = PdpModelInfo()
@@ -684,8 +558,8 @@ class ModelLib:
         warm = the solution at the previous parameter: the kernel starts from its first-order prediction for the step dtheta (PDP_MS_PREDICT: what oc_predict computes,
         applied while the point is loaded - no extra launch; with consume_warm the previous solution's tensors are overwritten by the new one, as an IRL loop wants it).
         predict["guard"] (default True, PDP_MS_PREDICT_GUARD): the previous solution is evaluated beside its prediction and the solve starts from whichever has the smaller
-        scaled KKT error (a first-order prediction across a large parameter step can be worse than no prediction: status & 512 marks the trajectories where it was dropped).
-        soc=True (PDP_MS_WITH_SOC): IPOPT's second-order correction in the line search (status & 1024: a corrected step was taken; include/pdp_hip.h says why it is off by default).
+        scaled KKT error (a first-order prediction across a large parameter step can be worse than no prediction: status & PDP_MS_PREDICT_REJECTED (512) marks the trajectories where it was dropped).
+        soc=True (PDP_MS_WITH_SOC): IPOPT's second-order correction in the line search (status & PDP_MS_SOC (1024): a corrected step was taken; include/pdp_hip.h says why it is off by default).
         Returns dict(state, control, costate, cost,
         resid [B,2], converged (bool), iterations [B], status [B][, gains])."""
         torch = torch_cuda()
@@ -717,12 +591,14 @@ class ModelLib:
         nbytes = self.lib.pdp_oc_solve_ms_workspace_bytes(B, T, int(max_iter))
         ws = torch.empty((max(nbytes, 8) // 8,), **f64)
         log = torch.zeros((B, int(log_rows), 8), **f64) if log_rows > 0 else None
-        opts = PdpOcMsOpts(float(tol), int(max_iter), (1 if warm is not None else 0) | (0 if restoration else 2) | (9 if u_init is not None else 0) | (128 if soc else 0) | (256 if watchdog else 0), int(log_rows))
+        flags = (PDP_MS_WARM if warm is not None else 0) | (0 if restoration else PDP_MS_NO_RESTORATION) | (PDP_MS_WARM | PDP_MS_FROM_CONTROLS if u_init is not None else 0) | \
+            (PDP_MS_WITH_SOC if soc else 0) | (PDP_MS_WITH_WATCHDOG if watchdog else 0)
+        opts = PdpOcMsOpts(float(tol), int(max_iter), flags, int(log_rows))
         keep = None
         if predict is not None:
             assert warm is not None, "predict needs the previous solution as the warm point"
             dth, dtb = self._theta(predict["dtheta"], B)
-            opts.flags |= 16
+            opts.flags |= PDP_MS_PREDICT
             opts.dtheta_bstride, opts.dtheta = dtb, dth.data_ptr()
             if predict.get("record") is not None:           # the packed fp32 record (oc_pdp_grad(want_predict_record=True))
                 keep = (dth, predict["record"])
@@ -733,10 +609,10 @@ class ModelLib:
                 assert keep[1].shape == (B, T + 1, self.n, self.p) and keep[2].shape == (B, T, self.m, self.p)
                 opts.dxdp, opts.dudp = keep[1].data_ptr(), keep[2].data_ptr()
                 opts.riccati = keep[3].data_ptr() if keep[3] is not None else None
-            if predict.get("primal"):                       # PDP_MS_PREDICT_PRIMAL: states and controls only (a record written with want_predict_record="primal" holds nothing else)
-                opts.flags |= 32
-            if predict.get("guard", True):                  # PDP_MS_PREDICT_GUARD (default): the prediction is kept only if its KKT error does not exceed the previous solution's;
-                opts.flags |= 64                            # status bit 512 (PDP_MS_PREDICT_REJECTED) says where it was not
+            if predict.get("primal"):                       # states and controls only (a record written with want_predict_record="primal" holds nothing else)
+                opts.flags |= PDP_MS_PREDICT_PRIMAL
+            if predict.get("guard", True):                  # (default) the prediction is kept only if its KKT error does not exceed the previous solution's;
+                opts.flags |= PDP_MS_PREDICT_GUARD          # status bit PDP_MS_PREDICT_REJECTED says where it was not
         check(self.lib.pdp_oc_solve_ms_batched(B, T, ptr(x0), ptr(th), tb, ptr(x), ptr(u), ptr(lam), ptr(cost), ptr(resid), ptr(conv), ptr(iters),
                                                ptr(status), ptr(gains), ptr(log), C.byref(opts), ptr(ws), nbytes, current_stream_ptr()), "pdp_oc_solve_ms_batched")
         out = {"state": x, "control": u, "costate": lam, "cost": cost, "resid": resid, "converged": conv != 0, "converged_flags": conv, "iterations": iters, "status": status}
@@ -836,7 +712,7 @@ class ModelLib:
         flags = 0
         if x is not None:
             assert lam is not None
-            x, lam, flags = dev(x), dev(lam), 1
+            x, lam, flags = dev(x), dev(lam), PDP_OC_GIVEN_TRAJ
             x0 = None
         else:
             x0 = dev(x0).reshape(B, n)
@@ -846,7 +722,7 @@ class ModelLib:
         loss = _buffer(bufs, "loss", (B,))
         if packed:
             pk = _buffer(bufs, "packed", (B, p + 1))
-            grad, flags = pk[:, :p], flags | 2
+            grad, flags = pk[:, :p], flags | PDP_OC_PACKED
         else:
             pk = grad = _buffer(bufs, "grad", (B, p))
         status = _buffer(bufs, "status", (B,), torch.int32)
@@ -855,9 +731,9 @@ class ModelLib:
         ric = _buffer(bufs, "riccati", (B, T, int(self.lib.pdp_oc_riccati_doubles()))) if want_riccati else None
         prec = _buffer(bufs, "predict_record", (B, T, int(self.lib.pdp_oc_predict_record_floats())), torch.float32) if want_predict_record else None
         if want_predict_record == "primal":
-            flags |= 4
+            flags |= PDP_OC_RECORD_PRIMAL
         if skip_missing:
-            flags |= 32
+            flags |= PDP_GRAD_SKIP_MISSING
         nbytes = self.lib.pdp_oc_pdp_workspace_bytes(B, T)
         ws = _buffer(bufs, "ws", (max(nbytes, 8) // 8,))
         if want_riccati or want_predict_record:
@@ -865,12 +741,12 @@ class ModelLib:
                               ric.data_ptr() if ric is not None else None, prec.data_ptr() if prec is not None else None)
             rc = self.lib.pdp_oc_pdp_grad_sens_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(demo_x), ptr(demo_u), ptr(x), ptr(lam), ptr(loss),
                                                        ptr(pk), C.byref(so), ptr(status), ptr(ws), nbytes, current_stream_ptr())
-            if rc == -2:
+            if rc == PDP_E_SIZE:
                 raise RuntimeError("pdp_oc_pdp_grad_sens_batched: the Riccati / prediction records are outputs of the fused kernels (n <= 16, m <= 4, m + p <= 16)")
         else:
             rc = self.lib.pdp_oc_pdp_grad_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(demo_x), ptr(demo_u), ptr(x), ptr(lam), ptr(loss),
                                                   ptr(pk), ptr(dxdp), ptr(dudp), ptr(status), ptr(ws), nbytes, current_stream_ptr())
-        if rc == -2:
+        if rc == PDP_E_SIZE:
             # m + p > 16 (beyond the fused kernel's single parameter tile), n > 16 / m > 4 (beyond one tile per matrix: the size-generic LQR
             # kernel takes over - any n, m), or a horizon whose staging exceeds the LDS: the reference's own route, kernel by kernel
             self._warn_materialised(T)
@@ -911,7 +787,7 @@ class ModelLib:
         zero = torch.zeros((), dtype=torch.float64, device="cuda")
         self._oc_pdp_grad_materialised(u, th, torch.where(torch.isnan(demo_x), zero, demo_x), torch.where(torch.isnan(demo_u), zero, demo_u), x0, x, lam, flags, loss,
                                        pk[:, :p], status, dxdp, dudp)
-        packed_row_from_sensitivities(pk, [(x, demo_x, wxd, dxdp), (u, demo_u, wud, dudp)], rule, delta, bool(flags & 32))
+        packed_row_from_sensitivities(pk, [(x, demo_x, wxd, dxdp), (u, demo_u, wud, dudp)], rule, delta, bool(flags & PDP_GRAD_SKIP_MISSING))
         loss.copy_(pk[:, p])
 
     def _oc_rows(self, u, th, tb, demo_x, demo_u, x0, x, lam, buffers, skip_missing=False, wls=None):
@@ -923,9 +799,9 @@ class ModelLib:
         torch = torch_cuda()
         B, T, n, p = u.shape[0], u.shape[1], self.n, self.p
         bufs = buffers if buffers is not None else {}
-        flags = 32 if skip_missing else 0
+        flags = PDP_GRAD_SKIP_MISSING if skip_missing else 0
         if x is not None:
-            flags |= 1
+            flags |= PDP_OC_GIVEN_TRAJ
         else:
             x, lam = _buffer(bufs, "x", (B, T + 1, n)), _buffer(bufs, "lam", (B, T, n))
         loss, pk, status = _buffer(bufs, "loss", (B,)), _buffer(bufs, "packed_gn", (B, p + 1 + p * p)), _buffer(bufs, "status", (B,), torch.int32)
@@ -936,10 +812,10 @@ class ModelLib:
             rc = self.lib.pdp_oc_pdp_grad_wls_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(demo_x), ptr(demo_u), ptr(wxd), wxs, ptr(wud), wus, delta, ptr(x),
                                                       ptr(lam), ptr(loss), ptr(pk), ptr(status), ptr(ws), nbytes, current_stream_ptr())
         else:
-            name, flags = "pdp_oc_pdp_grad_batched", flags | 16
+            name, flags = "pdp_oc_pdp_grad_batched", flags | PDP_GRAD_GAUSS_NEWTON
             rc = self.lib.pdp_oc_pdp_grad_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(demo_x), ptr(demo_u), ptr(x), ptr(lam), ptr(loss), ptr(pk), ptr(None),
                                                   ptr(None), ptr(status), ptr(ws), nbytes, current_stream_ptr())
-        if rc == -2:                                # beyond the fused kernels' limits: the same row from the materialised sensitivities
+        if rc == PDP_E_SIZE:                        # beyond the fused kernels' limits: the same row from the materialised sensitivities
             self._warn_materialised(T)
             if wls is not None:
                 self._oc_rows_materialised(u, th, demo_x, demo_u, x0, x, lam, flags, loss, pk, status, "weighted", wxd, wud, delta)
@@ -995,9 +871,9 @@ class ModelLib:
         torch = torch_cuda()
         u, gx, gu = dev(u), dev(gx), dev(gu)
         th, tb = self._theta(theta, B)
-        flags = 8                                               # PDP_OC_COTANGENT
+        flags = PDP_OC_COTANGENT
         if x is not None:
-            x, lam, flags = dev(x), dev(lam), flags | 1
+            x, lam, flags = dev(x), dev(lam), flags | PDP_OC_GIVEN_TRAJ
             x0 = None
         else:
             x0 = dev(x0).reshape(B, n)
@@ -1010,7 +886,7 @@ class ModelLib:
         ws = _buffer(bufs, "ws", (max(nbytes, 8) // 8,))
         rc = self.lib.pdp_oc_pdp_grad_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(gx), ptr(gu), ptr(x), ptr(lam), ptr(None),
                                               ptr(grad), ptr(None), ptr(None), ptr(status), ptr(ws), nbytes, current_stream_ptr())
-        if rc == -2:
+        if rc == PDP_E_SIZE:
             self._warn_materialised(T)
             self._oc_pdp_grad_materialised(u, theta, gx, gu, x0, x, lam, flags, None, grad, status)
             rc = 0
@@ -1046,7 +922,7 @@ class ModelLib:
         ws = torch.empty((max(nbytes, 8) // 8,), **f64)
         keep = (u, th, demo_x, demo_u, x0, x, lam, loss, pk, status, ws)                 # (the closure owns every buffer the kernel touches)
         fn = self.lib.pdp_oc_pdp_grad_batched
-        args = (B, T, 2, ptr(x0), ptr(u), ptr(th), tb, ptr(demo_x), ptr(demo_u), ptr(x), ptr(lam), ptr(loss), ptr(pk), ptr(None), ptr(None), ptr(status), ptr(ws), nbytes)
+        args = (B, T, PDP_OC_PACKED, ptr(x0), ptr(u), ptr(th), tb, ptr(demo_x), ptr(demo_u), ptr(x), ptr(lam), ptr(loss), ptr(pk), ptr(None), ptr(None), ptr(status), ptr(ws), nbytes)
         rc0 = fn(*args, current_stream_ptr())
         if rc0 != 0:
             raise RuntimeError("pdp_oc_pdp_grad_batched (prepared call): %s - problems outside the fused kernel's limits take oc_pdp_grad" % PDP_E.get(rc0, rc0))
@@ -1087,18 +963,18 @@ class ModelLib:
     def _oc_pdp_grad_materialised(self, u, theta, demo_x, demo_u, x0, x, lam, flags, loss, grad, status, dxdp=None, dudp=None):
         """The PDP gradient unit by the reference's own route (PDP.py:272-314, 557-608 and the chain rule of cartpole_PDP.py:63-74), one
         kernel per stage: trajectory and costates (unless given), aux matrices to HBM, lqrSolver (column blocks for any p), contraction
-        with (x - x_demo, u - u_demo) - or, with flags & 8 (PDP_OC_COTANGENT), with the cotangents that demo_x / demo_u then carry (row 0 of demo_x unread; no loss).
+        with (x - x_demo, u - u_demo) - or, with flags & PDP_OC_COTANGENT, with the cotangents that demo_x / demo_u then carry (row 0 of demo_x unread; no loss).
         Fills the given output tensors."""
         torch = torch_cuda()
         B, T = u.shape[0], u.shape[1]
         n, m, p = self.n, self.m, self.p
-        if not (flags & 1):
+        if not (flags & PDP_OC_GIVEN_TRAJ):
             x.copy_(self.oc_rollout(x0, u, theta, want_cost=False)[0])
             lam.copy_(self.oc_costate(x, u, theta))
         aux = self.oc_auxsys(x, u, lam, theta)
         X, U, _, st = lqr_solve(aux["dynF"], aux["dynG"], aux["Hxx"], aux["Huu"], aux["hxx"], aux["hxe"], E=aux["dynE"], Hxu=aux["Hxu"], Hxe=aux["Hxe"],
                                 Hue=aux["Hue"], want_costate=False)
-        if flags & 8:
+        if flags & PDP_OC_COTANGENT:
             ex, eu = demo_x.clone(), demo_u
             ex[:, 0] = 0.0
         else:
@@ -1106,8 +982,6 @@ class ModelLib:
             loss.copy_((ex ** 2).sum(dim=(1, 2)) + (eu ** 2).sum(dim=(1, 2)))
         g = torch.empty((B, p), dtype=torch.float64, device="cuda")
         core = load_core()
-        core.pdp_cp_grad_contract_batched.restype = C.c_int
-        core.pdp_cp_grad_contract_batched.argtypes = [C.c_int] * 5 + [C.c_void_p] * 7
         ex_path, ex_fin, eu_c = ex[:, :T].contiguous(), ex[:, T].contiguous(), eu.contiguous()      # (named: they must outlive the launch)
         check(core.pdp_cp_grad_contract_batched(B, T, n, m, p, ptr(ex_path), ptr(eu_c), ptr(ex_fin), ptr(X), ptr(U), ptr(g), current_stream_ptr()),
               "pdp_cp_grad_contract_batched")
@@ -1126,7 +1000,7 @@ class ModelLib:
         f64 = dict(dtype=torch.float64, device="cuda")
         flags = 0
         if x is not None:
-            x, lam, flags = dev(x).clone(), dev(lam).clone(), 1
+            x, lam, flags = dev(x).clone(), dev(lam).clone(), PDP_OC_GIVEN_TRAJ
         else:
             x0 = dev(x0).reshape(B, self.n)
             x, lam = torch.empty((B, T + 1, self.n), **f64), torch.empty((B, T, self.n), **f64)
@@ -1151,7 +1025,7 @@ class ModelLib:
         u = torch.empty((B, T, self.m), dtype=torch.float64, device="cuda")
         cost = torch.empty((B,), dtype=torch.float64, device="cuda")
         rc = self.lib.pdp_cp_integrate_batched(B, T, C.byref(pol), p, ptr(x0), ptr(th), tb, ptr(x), ptr(u), ptr(cost), current_stream_ptr())
-        if rc == -2:        # a network wider than the lane-per-trajectory integrator's local arrays: the size-generic step kernel rolls out as well (its gradient is dropped)
+        if rc == PDP_E_SIZE:        # a network wider than the lane-per-trajectory integrator's local arrays: the size-generic step kernel rolls out as well (its gradient is dropped)
             loss, _, x, u = self.cp_step(pol, p, x0, th, T, want_traj=True)
             return x, u, loss
         check(rc, "pdp_cp_integrate_batched")
@@ -1206,8 +1080,6 @@ class ModelLib:
         X, U = cp_aux_integrate(aux["dynF"], aux["dynG"], aux["dUx"], aux["dUe"])
         grad = torch.empty((B, p), dtype=torch.float64, device="cuda")
         lib = load_core()
-        lib.pdp_cp_grad_contract_batched.restype = C.c_int
-        lib.pdp_cp_grad_contract_batched.argtypes = [C.c_int] * 5 + [C.c_void_p] * 7
         check(lib.pdp_cp_grad_contract_batched(B, int(T), self.n, self.m, p, ptr(aux["dcx"]), ptr(aux["dcu"]), ptr(aux["dhx"]), ptr(X), ptr(U),
                                                ptr(grad), current_stream_ptr()), "pdp_cp_grad_contract_batched")
         return (loss, grad, x, u) if want_traj else (loss, grad)
@@ -1325,7 +1197,7 @@ class ModelLib:
         grad = torch.empty((B, self.p), dtype=torch.float64, device="cuda")
         ws, nbytes = self._sysid_workspace(B, T)
         rc = self.lib.pdp_sysid_step_ws_batched(B, T, ptr(u), ptr(xobs), ptr(th), tb, ptr(loss), ptr(grad), ptr(ws), nbytes, current_stream_ptr())
-        if rc == -2:
+        if rc == PDP_E_SIZE:
             x = self.sysid_integrate(xobs[:, 0].contiguous(), u, th)
             F, E = self.sysid_auxsys(x, u, th)
             X = sysid_aux_integrate(F, E)                                           # [B, T+1, n, p]
@@ -1363,7 +1235,7 @@ class ModelLib:
         Returns the packed dict over W: packed_gn [B, W + 1 + W W] and loss, grad, gn as views of it, ini_index where components are estimated."""
         B, T, W = u.shape[0], u.shape[1], self.p + len(ini_index)
         bufs = buffers if buffers is not None else {}
-        flags = 32 if skip_missing else 0
+        flags = PDP_GRAD_SKIP_MISSING if skip_missing else 0
         loss = _buffer(bufs, "loss", (B,))
         packed = _buffer(bufs, "packed_gn_wls" if wls is not None else ("packed_gn_ini" if ini_mask else "packed_gn"), (B, W + 1 + W * W))
         ws, nbytes = self._sysid_workspace(B, T)
@@ -1378,7 +1250,7 @@ class ModelLib:
         else:
             name = "pdp_sysid_step_gn_batched"
             rc = self.lib.pdp_sysid_step_gn_batched(B, T, ptr(u), ptr(xobs), ptr(x0), ptr(th), tb, flags, ptr(loss), ptr(packed), ptr(ws), nbytes, current_stream_ptr())
-        if rc == -2:                                # beyond the fused kernels' tile: the same row from the materialised sensitivities (started at the selection matrix)
+        if rc == PDP_E_SIZE:                        # beyond the fused kernels' tile: the same row from the materialised sensitivities (started at the selection matrix)
             x, X = self._sysid_materialised(u, xobs, th, x0, ini_index)             # X [B, T+1, n, W]
             if wls is not None:
                 packed_row_from_sensitivities(packed, [(x, xobs, wls[0], X)], "weighted", wls[2], skip_missing)
