@@ -39,8 +39,22 @@ def _symbols(name, lib):
     return tuple(list(sp.symbols("%s0:%d" % (s, k), real=True)) for s, k in (("x", n), ("u", m), ("w", p)))
 
 
-def equations(name, lib):
-    """(state, control, auxvar, dynamics, path cost, final cost) as lists of scalars / scalars of the symbolic library `lib` ("sx": pdp_amd.sx, else sympy)"""
+def equations(name, lib, theta=None):
+    """(state, control, auxvar, dynamics, path cost, final cost) as lists of scalars / scalars of the symbolic library `lib` ("sx": pdp_amd.sx, else sympy).
+    theta [p] (tests/cp_edge_common.py: ControlPlanning has no auxvar): the parameters are replaced by these doubles - pdp_amd.sx.substitute / sympy's .subs on the
+    finished expressions, so both libraries are given the same numbers in the same places - and the auxvar comes back as an empty list"""
+    if theta is not None:
+        xs, us, ws, f, path, final = equations(name, lib)
+        vals = [float(v) for v in theta]
+        assert len(vals) == len(ws)
+        if lib == "sx":
+            from pdp_amd import sx
+            old, new = sx.vertcat(*ws), sx.SX(np.array(vals).reshape(-1, 1))
+            sub = lambda e: sx.substitute(e, old, new)
+            return xs, us, [], [sub(fi) for fi in f], sub(path), sub(final)
+        import sympy as sp
+        rep = dict(zip(ws, (sp.Float(v, 40) for v in vals)))              # the double itself, carried at 40 digits: products of constants are not rounded to 53 bits
+        return xs, us, [], [fi.subs(rep) for fi in f], path.subs(rep), final.subs(rep)
     n, m, p = MODELS[name]
     xs, us, ws = _symbols(name, lib)
     nm, odd, nw = n // 2, n % 2 == 1, p - 4
