@@ -22,7 +22,7 @@ extern "C" {
  * There is no masking and no status word: a NaN in a trajectory's x, u, theta or grad_x shows in that trajectory's outputs and in no other's.  With finite Jacobians a
  * zero cotangent gives exact zeros, and a cotangent that is non-zero at t = 0 only gives grad_theta = 0 and grad_x0 = g_0 to the bit.  A trajectory's output bits do
  * not depend on the batch size or on its position in the batch.
- * Left out: the gradient with respect to u (SysID models do not generate df/du), second order.
+ * Left out: second order; the gradient with respect to u is pdp_sysid_rollout_vjp_u_batched's (pdp_hip_sysid_vjp_u.h).
  * NULL x, u, theta or grad_x, both outputs NULL, B <= 0, T <= 0, a theta_bstride that is neither 0 nor >= p: PDP_E_ARG before any launch; not a SysID model:
  * PDP_E_MODE; n > 64 or p > 512 (a lane owns one state component and at most eight parameters): PDP_E_SIZE. */
 int pdp_sysid_rollout_vjp_batched(int B, int T, const double* x, const double* u, const double* theta, int theta_bstride, const double* grad_x, double* grad_theta,

@@ -769,12 +769,14 @@ class SysID(_CasadiFrontEnd):
             raise ValueError("integrateDyn_batch: auxvar_value must be [p] or [B, p] with p = %d, B = %d, got %s" % (self.n_auxvar, su[0], shape(auxvar_value)))
         return self.model().sysid_integrate(ini_state, inputs, auxvar_value)
 
-    def rollout_vjp_batch(self, state_traj, inputs, auxvar_value, grad_state, want_ini=True):
+    def rollout_vjp_batch(self, state_traj, inputs, auxvar_value, grad_state, want_ini=True, want_theta=True, want_inputs=False):
         """The gradient of ANY scalar loss L(state_traj) of the rollouts state_traj = integrateDyn_batch(ini_state, inputs, auxvar_value), for a batch: grad_state
         [B, T+1, n] = dL/dstate_traj (a cotangent, e.g. from torch.autograd.grad) -> dict(grad_theta [B, p] = dL/dauxvar per trajectory, grad_x0 [B, n] = dL/dini_state
         with want_ini) by the adjoint sweep lam_t = g_t + F_t' lam_{t+1}, grad += E_t' lam_{t+1} in one launch (include/pdp_hip_sysid_vjp.h).  step_batch's gradient is
-        the special case grad_state = state_traj - batch_states.  pdp_amd.autograd.sysid_trajectory wraps rollout + this call as a torch.autograd layer."""
-        return self.model().sysid_rollout_vjp(state_traj, inputs, auxvar_value, grad_state, want_ini=want_ini)
+        the special case grad_state = state_traj - batch_states.  want_inputs=True: also grad_u [B, T, m] = dL/dinputs through the dynamics, G_t' lam_{t+1} from the
+        same launch (include/pdp_hip_sysid_vjp_u.h); want_theta=False leaves grad_theta out.  pdp_amd.autograd.sysid_trajectory wraps rollout + this call as a
+        torch.autograd layer."""
+        return self.model().sysid_rollout_vjp(state_traj, inputs, auxvar_value, grad_state, want_ini=want_ini, want_theta=want_theta, want_inputs=want_inputs)
 
     def getAuxSys(self, state_traj, control_traj, auxvar_value):                # PDP.py:1225-1239
         F, E = self.model().sysid_auxsys(np.asarray(state_traj, float)[None], np.asarray(control_traj, float).reshape(1, -1, self.n_control),

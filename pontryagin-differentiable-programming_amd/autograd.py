@@ -12,19 +12,23 @@ trajectory - one launch of the fused unit in its cotangent mode (OCSys.pdp_vjp_b
 the incoming gradients on the chip and never written out.
 
 `sysid_trajectory` is the same for the rollouts of a PDP.SysID: it maps (ini_state, theta) to the states of x_{t+1} = f(x_t, u_t, theta) for given inputs and is
-differentiable in theta and ini_state, so that a loss that is not "state minus recorded state" - a bearing or camera measurement h(x), a regulariser on the rollout, a
-learned term - trains the model's parameters and unknown initial states:
+differentiable in theta and ini_state - and, with input_grad=True, in the inputs - so that a loss that is not "state minus recorded state" - a bearing or camera
+measurement h(x), a regulariser on the rollout, a learned term - trains the model's parameters and unknown initial states, and plans or refines inputs through the model:
 
     state = sysid_trajectory(sid, ini_state, inputs, theta)              # [B, T+1, n]; theta (and ini_state) CUDA fp64, requires_grad
     loss = ((torch.sin(state[:, :, 0]) - recorded_sin) ** 2).sum()
     loss.backward()                                                      # theta.grad, ini_state.grad
 
-Forward: SysID.integrateDyn_batch.  Backward: the adjoint sweep lam_t = dL/dx_t + F_t' lam_{t+1}, dL/dtheta += E_t' lam_{t+1}, dL/dx_0 = lam_0 in one launch
-(SysID.rollout_vjp_batch, include/pdp_hip_sysid_vjp.h).
+    state = sysid_trajectory(sid, ini_state, inputs, theta, input_grad=True)      # inputs: CUDA fp64, requires_grad
+    loss = ((state[:, -1] - goal) ** 2).sum() + 0.01 * (inputs ** 2).sum()
+    loss.backward()                                                      # inputs.grad (and theta.grad, ini_state.grad where they require one)
+
+Forward: SysID.integrateDyn_batch.  Backward: the adjoint sweep lam_t = dL/dx_t + F_t' lam_{t+1}, dL/dtheta += E_t' lam_{t+1}, dL/dx_0 = lam_0 - and, with input_grad,
+dL/du_t = G_t' lam_{t+1} - in one launch (SysID.rollout_vjp_batch, include/pdp_hip_sysid_vjp.h, include/pdp_hip_sysid_vjp_u.h).
 
 Limits.  Both layers: first order only (backward is once_differentiable).  oc_trajectory: no gradient with respect to ini_state; no finite state / control bounds (the
-bounded solve goes through a log-barrier model whose KKT system is not the one the unit differentiates).  sysid_trajectory: no gradient with respect to the inputs
-(SysID models do not generate df/du)."""
+bounded solve goes through a log-barrier model whose KKT system is not the one the unit differentiates).  sysid_trajectory: the gradient with respect to the inputs on
+request only (input_grad=True; without the keyword an `inputs` that requires a gradient is refused), and only THROUGH the dynamics; no models without parameters."""
 import warnings
 
 import torch
@@ -85,35 +89,47 @@ def oc_trajectory(oc, ini_state, horizon, theta, return_info=False, **solver_kwa
 
 class _SysIDTrajectory(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, theta, ini_state, sid, inputs):
+    def forward(ctx, theta, ini_state, inputs, sid, input_grad):
         with torch.no_grad():
-            x = sid.integrateDyn_batch(ini_state.detach(), inputs, theta.detach())
-        ctx.sid, ctx.shared, ctx.want_ini = sid, theta.dim() == 1, bool(ctx.needs_input_grad[1])
-        ctx.save_for_backward(x, inputs, theta.detach())
+            x = sid.integrateDyn_batch(ini_state.detach(), inputs.detach(), theta.detach())
+        need = ctx.needs_input_grad
+        # input_grad: exactly the outputs that are needed; without it the call the layer always made (grad_theta whatever theta requires)
+        ctx.sid, ctx.shared, ctx.want_ini = sid, theta.dim() == 1, bool(need[1])
+        ctx.want_theta, ctx.want_inputs = (bool(need[0]), bool(need[2])) if input_grad else (True, False)
+        ctx.save_for_backward(x, inputs.detach(), theta.detach())
         return x.clone()                     # (the saved rollout stays as the kernel wrote it whatever the caller does to the output)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_state):
         x, inputs, theta = ctx.saved_tensors
-        out = ctx.sid.rollout_vjp_batch(x, inputs, theta, grad_state.to(torch.float64).contiguous(), want_ini=ctx.want_ini)
-        g = out["grad_theta"]
-        return (g.sum(dim=0) if ctx.shared else g), (out["grad_x0"] if ctx.want_ini else None), None, None
+        g = grad_state.to(torch.float64).contiguous()
+        out = ctx.sid.rollout_vjp_batch(x, inputs, theta, g, want_ini=ctx.want_ini, want_theta=ctx.want_theta, want_inputs=ctx.want_inputs)
+        gt = out.get("grad_theta")
+        if gt is not None and ctx.shared:
+            gt = gt.sum(dim=0)
+        return gt, out.get("grad_x0"), out.get("grad_u"), None, None
 
 
-def sysid_trajectory(sid, ini_state, inputs, theta):
+def sysid_trajectory(sid, ini_state, inputs, theta, input_grad=False):
     """Rollouts of the PDP.SysID `sid` from ini_state [B, n] under inputs [B, T, m] at the parameter `theta`, differentiable in theta and ini_state: returns state
     [B, T+1, n].  theta: CUDA fp64 tensor, [p] (one parameter shared by the batch: theta.grad is the sum over the batch) or [B, p] (one per sample).  ini_state: an array
-    or a tensor; a CUDA fp64 tensor that requires a gradient gets one (dL/dx_0, state[:, 0]'s own cotangent included)."""
+    or a tensor; a CUDA fp64 tensor that requires a gradient gets one (dL/dx_0, state[:, 0]'s own cotangent included).
+    input_grad=True: differentiable in the inputs as well.  `inputs` must then be a CUDA fp64 tensor; when it requires a gradient it receives dL/dinputs THROUGH THE
+    DYNAMICS (a loss that also uses `inputs` directly gets that term from torch as usual).  Backward computes exactly the gradients that are needed, all in one launch:
+    a theta that does not require a gradient gets none computed."""
     if not (torch.is_tensor(theta) and theta.is_cuda and theta.dtype == torch.float64):
         raise TypeError("sysid_trajectory: theta must be a CUDA fp64 tensor ([p] shared, or [B, p] per sample)")
-    if torch.is_tensor(inputs) and inputs.requires_grad:
-        raise NotImplementedError("sysid_trajectory: the gradient with respect to the inputs is not implemented - SysID models do not generate df/du, and adding it "
-                                  "changes the content hash, and with it the name, of every SysID model library: a change of its own; pass inputs.detach()")
+    if input_grad:
+        if not (torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype == torch.float64):
+            raise TypeError("sysid_trajectory: with input_grad=True the inputs must be a CUDA fp64 tensor [B, T, m]")
+    elif torch.is_tensor(inputs) and inputs.requires_grad:
+        raise NotImplementedError("sysid_trajectory: the gradient with respect to the inputs (through df/du) is computed on request only - pass input_grad=True, or "
+                                  "inputs.detach()")
     if theta.dim() not in (1, 2) or theta.shape[-1] != sid.n_auxvar:
         raise ValueError("sysid_trajectory: theta must be [p] or [B, p] with p = %d, got %s" % (sid.n_auxvar, tuple(theta.shape)))
     if torch.is_tensor(ini_state) and ini_state.requires_grad and not (ini_state.is_cuda and ini_state.dtype == torch.float64):
         raise TypeError("sysid_trajectory: an ini_state that requires a gradient must be a CUDA fp64 tensor")
     from . import runtime
-    x0, u = (ini_state if torch.is_tensor(ini_state) else runtime.dev(ini_state)), runtime.dev(inputs)
-    return _SysIDTrajectory.apply(theta, x0, sid, u)
+    x0, u = (ini_state if torch.is_tensor(ini_state) else runtime.dev(ini_state)), (inputs if input_grad else runtime.dev(inputs))
+    return _SysIDTrajectory.apply(theta, x0, u, sid, bool(input_grad))

@@ -9,7 +9,8 @@ Generated interface (consumed by csrc/pdp_model_kernels.h):
   struct PdpModel { KIND, NX, NU, NP, NAME, CHUNK;
       dyn(x,u,th,out)  path_cost(x,u,th)  final_cost(x,th)  costate_step(x,u,lam,th,out)  dhx(x,th,out)
       group <g> in {path, fwd, fin}:  <G>_NVAR, <G>_NCONST, <g>_const(c), eval_<g>(x,u,lam,th,sink),
-                                      <g>_code(mat, i), <G>_MAT[k], <G>_OFF[k], <G>_ROWS[mat], <G>_COLS[mat] }
+                                      <g>_code(mat, i), <G>_MAT[k], <G>_OFF[k], <G>_ROWS[mat], <G>_COLS[mat]
+      SysID models also: group pathu (G = df/du) with NPCU, precompute_u(th, pc) - precompute's values and, behind them, those pathu alone reads }
 Matrix entries are classified at generation time: structural zero (code -1), constant (code -2-c, value in
 the constant pool) or variable (code k >= 0, written by eval_<g> through sink.put<k>(v)).  Only variable
 entries cost arithmetic and LDS space; the quadrotor's eight per-step matrices have ~200 of 728 entries non-zero.
@@ -353,14 +354,24 @@ def generate(problem):
         fe = sx.jacobian(dyn, th)
         groups["path"] = _Group("path", [("F", n, n, R(fx)), ("E", n, p, R(fe))])
         chunk = _pick_chunk(groups["path"].nvar, n)
+        # df/du for the rollout's gradient with respect to the inputs (sysid_vjp_u_kernel) in a group of its own, emitted behind `path`: every other SysID kernel
+        # reads `path` alone, which keeps its matrices, codes, PATH_NVAR and CHUNK
+        groups["pathu"] = _Group("pathu", [("G", n, m, R(fu))])
     else:
         raise ValueError("unknown problem kind")
     for _, _, outs, _ in funcs:
         opt.mark_hoisted(outs)
     for g in groups.values():
-        opt.mark_hoisted(g.var_nodes)
+        if g.gname != "pathu":
+            opt.mark_hoisted(g.var_nodes)
     repl = opt.replace_map()
     npc = len(opt.pc_nodes)
+    # SysID `pathu`: what it hoists beyond the values above goes BEHIND them, into precompute_u / pc[NPCU] of the one kernel that reads the group - precompute, NPC and
+    # every pc[] index of the other functions and groups stay what they are without the group
+    repl_u, npcu = repl, npc
+    if "pathu" in groups:
+        opt.mark_hoisted(groups["pathu"].var_nodes)
+        repl_u, npcu = opt.replace_map(), len(opt.pc_nodes)
     if chunk is None:
         # fused kernel (csrc/pdp_model_kernels.h fused_lds_bytes): Riccati scratch 608 + constants + dl_T + theta + pc + pad
         nconst = 1 + max(len(groups["patha"].consts) + len(groups["pathb"].consts), len(groups["fwd"].consts), len(groups["fin"].consts))
@@ -375,12 +386,19 @@ def generate(problem):
     L.append("    static constexpr int NPC = %d;" % max(1, npc))
     L.append("    PDP_HD static void precompute(const double* th, double* pc) {")
     L.append("        (void)th; (void)pc;")
-    L.extend(sx.emit(opt.pc_nodes, inputs, lang="c", result=lambda k, e: "pc[%d] = %s;" % (k, e), indent="        "))
+    L.extend(sx.emit(opt.pc_nodes[:npc], inputs, lang="c", result=lambda k, e: "pc[%d] = %s;" % (k, e), indent="        "))
     L.append("    }")
     for name, args, outs, scalar in funcs:
         _emit_vecfn(name, args + ["pc"], outs, inputs, L, scalar=scalar, replace=repl)
     for g in groups.values():
-        _emit_group(g, inputs, L, replace=repl)
+        if g.gname == "pathu":
+            L.append("    // ---- the values of precompute, then those that group 'pathu' alone reads (pc[NPCU]): eval_path and eval_pathu both take this array")
+            L.append("    static constexpr int NPCU = %d;" % max(1, npcu))
+            L.append("    PDP_HD static void precompute_u(const double* th, double* pc) {")
+            L.append("        (void)th; (void)pc;")
+            L.extend(sx.emit(opt.pc_nodes, inputs, lang="c", result=lambda k, e: "pc[%d] = %s;" % (k, e), indent="        "))
+            L.append("    }")
+        _emit_group(g, inputs, L, replace=repl_u if g.gname == "pathu" else repl)
     body = "\n".join(L)
     digest = hashlib.sha1(("%d|%d|%d|%d|" % (pb.kind, n, m, p) + body).encode()).hexdigest()[:10]
     name = "%s_%s_%s" % (pb.label, KIND_NAME[pb.kind], digest)

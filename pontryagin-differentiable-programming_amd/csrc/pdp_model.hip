@@ -9,6 +9,7 @@
 #include "../../include/pdp_hip_sysid_wls.h"
 #include "../../include/pdp_hip_oc_wls.h"
 #include "../../include/pdp_hip_sysid_vjp.h"
+#include "../../include/pdp_hip_sysid_vjp_u.h"
 #ifndef PDP_MODEL_HEADER
 #error "compile with -DPDP_MODEL_HEADER=\"generated/<model>.h\""
 #endif
@@ -672,6 +673,37 @@ int sysid_rollout_vjp(int B, int T, const double* x, const double* u, const doub
     }
 }
 
+// ... and with the gradient with respect to the inputs (pdp_sysid_rollout_vjp_u_batched, include/pdp_hip_sysid_vjp_u.h).  Without grad_u this is the launch above, the
+// same code object; with it sysid_vjp_u_kernel, whose lanes own the p + m columns of [E | G] (eight slots: p + m <= 512) and whose pool row is longer.
+template <class Mdl>
+int sysid_rollout_vjp_u(int B, int T, const double* x, const double* u, const double* th, int tb, const double* gx, double* grad_theta, double* grad_x0, double* grad_u,
+                        void* st) {
+    if (B <= 0 || T <= 0 || !x || !u || !th || !gx || (!grad_theta && !grad_x0 && !grad_u) || (tb != 0 && tb < Mdl::NP)) return PDP_E_ARG;
+    if constexpr (Mdl::KIND != PDP_KIND_SYSID) return PDP_E_MODE;
+    else if constexpr (Mdl::NX > 64) return PDP_E_SIZE;
+    else {
+        if (!grad_u) return sysid_rollout_vjp<Mdl>(B, T, x, u, th, tb, gx, grad_theta, grad_x0, st);
+        if constexpr (Mdl::NP + Mdl::NU > 512) return PDP_E_SIZE;
+        else {
+            const int rows = sysid_vjp_u_rows<Mdl>(B, device_cu_count());
+            const size_t lds = sizeof(double) * (size_t)sysid_vjp_u_slice<Mdl>(rows);
+            if (lds > 150 * 1024) return PDP_E_SIZE;
+            return launch(sysid_vjp_u_kernel<Mdl>, dim3(B), dim3(64), lds, S(st), B, T, x, u, th, tb, gx, grad_theta, grad_x0, grad_u, rows);
+        }
+    }
+}
+// pool rows of the launch above (pdp_sysid_rollout_vjp_u_rows)
+template <class Mdl>
+int sysid_rollout_vjp_u_rows(int B) {
+    if (B <= 0) return PDP_E_ARG;
+    if constexpr (Mdl::KIND != PDP_KIND_SYSID) return PDP_E_MODE;
+    else if constexpr (Mdl::NX > 64 || Mdl::NP + Mdl::NU > 512) return PDP_E_SIZE;
+    else {
+        const int rows = sysid_vjp_u_rows<Mdl>(B, device_cu_count());
+        return sizeof(double) * (size_t)sysid_vjp_u_slice<Mdl>(rows) > 150 * 1024 ? PDP_E_SIZE : rows;
+    }
+}
+
 template <class Mdl> int nnz_path() { return Mdl::PATH_NVAR; }
 
 // what the Gauss-Newton entry points of SysID.step check first: sizes, the pointers every one of them needs, no flag but PDP_GRAD_SKIP_MISSING
@@ -812,6 +844,11 @@ int pdp_sysid_rollout_vjp_batched(int B, int T, const double* x, const double* u
                                   double* grad_x0, void* stream) {
     return sysid_rollout_vjp<PdpModel>(B, T, x, u, theta, tb, grad_x, grad_theta, grad_x0, stream);
 }
+int pdp_sysid_rollout_vjp_u_batched(int B, int T, const double* x, const double* u, const double* theta, int tb, const double* grad_x, double* grad_theta,
+                                    double* grad_x0, double* grad_u, void* stream) {
+    return sysid_rollout_vjp_u<PdpModel>(B, T, x, u, theta, tb, grad_x, grad_theta, grad_x0, grad_u, stream);
+}
+int pdp_sysid_rollout_vjp_u_rows(int B) { return sysid_rollout_vjp_u_rows<PdpModel>(B); }
 int pdp_oc_pdp_grad_wls_batched(int B, int T, int flags, const double* x0, const double* u, const double* theta, int theta_bstride, const double* demo_x,
                                 const double* demo_u, const double* weights_x, int64_t weights_x_bstride, const double* weights_u, int64_t weights_u_bstride,
                                 double huber_delta, double* x, double* lam, double* loss, double* packed, int32_t* status, void* workspace, int64_t workspace_bytes,

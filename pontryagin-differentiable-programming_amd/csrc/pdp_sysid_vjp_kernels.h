@@ -3,6 +3,9 @@
 //     lam_T = g_T ;   t = T-1 .. 0 :   dL/dtheta += E_t' lam_{t+1} ,   lam_t = g_t + F_t' lam_{t+1} ;   dL/dx_0 = lam_0
 // (F_t = df/dx, E_t = df/dtheta at (x_t, u_t, theta): the models' `path` group).  O(T (n^2 + n p)) and nothing larger than a vector per step, where the forward
 // sensitivities X_{t+1} = F_t X_t + E_t of sysid_step_kernel cost O(T n^2 p) and serve one loss.  Instantiated for PDP_KIND_SYSID only (pdp_model.hip).
+// With the inputs (include/pdp_hip_sysid_vjp_u.h): the same sweep also gives dL/du_t = G_t' lam_{t+1} (G_t = df/du: the models' `pathu` group) - sysid_vjp_u_kernel,
+// a kernel of its own below sysid_vjp_kernel.  (One force-inlined body with a compile-time switch under both was built first: the wrapper did not compile to the
+// instructions sysid_vjp_kernel had - the scalar code of the chunk arithmetic came out in another order - so that kernel keeps its own text: DESIGN.md section 4.1k.)
 #pragma once
 #include "pdp_model_kernels.h"
 
@@ -17,12 +20,22 @@ __host__ __device__ inline int sysid_vjp_slice(int rows) { return (1 + Mdl::PATH
 // 2400 doubles (18.75 KB: with the constants and the allocation granularity an eighth of the CU's 160 KB), so that two workgroups per SIMD are resident and fill each
 // other's waits - the rule of sysid_rows.  The rule reads the row stride alone: runtime.ModelLib.sysid_vjp_rows restates it.  The result bits do not depend on it: the
 // sweep visits the steps in the same order whatever the pass they were evaluated in.
-template <class Mdl>
-__host__ inline int sysid_vjp_rows(int B, int cus) {
-    if (B <= 4 * cus) return Mdl::CHUNK;
-    const int fit = 2400 / sysid_vjp_stride<Mdl>();
-    return fit >= 4 ? (fit < Mdl::CHUNK ? fit : Mdl::CHUNK) : Mdl::CHUNK;
+inline int sysid_vjp_rows_of(int B, int cus, int stride, int chunk) {
+    if (B <= 4 * cus) return chunk;
+    const int fit = 2400 / stride;
+    return fit >= 4 ? (fit < chunk ? fit : chunk) : chunk;
 }
+template <class Mdl>
+__host__ inline int sysid_vjp_rows(int B, int cus) { return sysid_vjp_rows_of(B, cus, sysid_vjp_stride<Mdl>(), Mdl::CHUNK); }
+
+// The same three for sysid_vjp_u_kernel.  Its pool row: the packed entries of (F_t, E_t) | those of G_t | the NX cotangents | NU doubles in which the sweep leaves this
+// step's dL/du_t; the constants of both groups behind blk[0].  The rows are sysid_vjp_rows' rule on this stride (Mdl::CHUNK was picked for the shorter row: a pool of
+// CHUNK rows is (NVAR_G + NU) * CHUNK doubles larger here, which the host routine's 150 KB bound sees).
+template <class Mdl> constexpr int sysid_vjp_u_stride() { return (Mdl::PATH_NVAR + Mdl::PATHU_NVAR + Mdl::NX + Mdl::NU) | 1; }
+template <class Mdl>
+__host__ __device__ inline int sysid_vjp_u_slice(int rows) { return (1 + Mdl::PATH_NCONST + Mdl::PATHU_NCONST + rows * sysid_vjp_u_stride<Mdl>() + 1) & ~1; }
+template <class Mdl>
+__host__ inline int sysid_vjp_u_rows(int B, int cus) { return sysid_vjp_rows_of(B, cus, sysid_vjp_u_stride<Mdl>(), Mdl::CHUNK); }
 
 // One wavefront per trajectory on the GIVEN trajectory x (what sysid_integrate_kernel wrote): no rollout here.  The horizon is cut into chunks of equal length <= CH,
 // visited last to first (cp_step_adjoint_kernel's structure).  Per chunk: lane tl loads x_t, u_t, g_t of step t = t0 + tl and evaluates the model's path group through a
@@ -90,6 +103,104 @@ __global__ void __launch_bounds__(64) sysid_vjp_kernel(int B, int T, const doubl
                 for (int q = 0; q < NQ; ++q) acc[q] += blk[eo[q][k] + tl * em[q][k]] * lk;
             }
             lam = m_new;
+        }
+    }
+    if (grad_theta) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) { const int j = lane + 64 * q; if (j < NP) grad_theta[(int64_t)b * NP + j] = acc[q]; }
+    }
+    if (grad_x0 && lane < NX) grad_x0[(int64_t)b * NX + lane] = lam;
+}
+
+// sysid_vjp_kernel with the gradient with respect to the inputs.  The lane-per-step pass also evaluates the `pathu` group (G_t) behind the path entries of its row.  In
+// the sweep a lane owns the columns c = lane + 64 q of the n x (p + m) matrix [E_t | G_t]: c < p accumulates over the horizon as above (same products, same order),
+// p <= c < p + m is one step's G_t' lam_{t+1} - behind the k loop of step tl its lane stores the sum into the row's staging slot and restarts from 0.0 (a select: the
+// products run in every lane).  No read and no product more in the loop than a slot of E columns costs, and nothing on the recursion's chain.  After the chunk's sweep lane
+// tl copies its row's m values to grad_u[b][t0 + tl] (adjacent lanes, adjacent 8 m bytes); the sync at the top of the next chunk protects the rows.  Every grad_u[b][t]
+// is written exactly once and never read.  grad_u is never NULL here: without it the host routine launches the kernel above.
+template <class Mdl>
+__global__ void __launch_bounds__(64) sysid_vjp_u_kernel(int B, int T, const double* __restrict__ x, const double* __restrict__ u, const double* __restrict__ theta,
+                                                          int tb, const double* __restrict__ gx, double* __restrict__ grad_theta, double* __restrict__ grad_x0,
+                                                          double* __restrict__ grad_u, int CH) {
+    constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP, NQ = (NP + NU + 63) / 64;
+    constexpr int NC = 1 + Mdl::PATH_NCONST + Mdl::PATHU_NCONST, GX = Mdl::PATH_NVAR + Mdl::PATHU_NVAR, SU = GX + NX, STRIDE = sysid_vjp_u_stride<Mdl>();
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double* blk = lds;
+    double* pool = blk + NC;
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const double* th = theta + (int64_t)b * tb;
+    double pc[Mdl::NPCU];
+    Mdl::precompute_u(th, pc);                     // precompute's values and, behind them, those that `pathu` alone reads
+    const double* xb = x + (int64_t)b * (T + 1) * NX;
+    const double* ub = u + (int64_t)b * T * NU;
+    const double* gb = gx + (int64_t)b * (T + 1) * NX;
+    if (lane == 0) blk[0] = 0.0;
+    for (int i_ = lane; i_ < Mdl::PATH_NCONST; i_ += 64) blk[1 + i_] = Mdl::path_const(i_);
+    for (int i_ = lane; i_ < Mdl::PATHU_NCONST; i_ += 64) blk[1 + Mdl::PATH_NCONST + i_] = Mdl::pathu_const(i_);
+    // per-lane pool offsets (o) and row multipliers (m): column `lane` of F, g_t[lane], column lane + 64 q of [E | G]
+    int fo[NX], fm[NX], eo[NQ][NX], em[NQ][NX], go = 0, gm = 0;
+    auto enc = [&](int code, int& o, int& m) { if (code >= 0) { o = NC + code; m = STRIDE; } else { o = (code == -1) ? 0 : 1 + (-2 - code); m = 0; } };
+    // a G entry's variable sits behind the path entries of the row, its constant behind the path constants of the block
+    auto encu = [&](int code, int& o, int& m) { enc(code >= 0 ? Mdl::PATH_NVAR + code : (code == -1 ? -1 : code - Mdl::PATH_NCONST), o, m); };
+#pragma unroll
+    for (int k = 0; k < NX; ++k) {
+        enc(lane < NX ? Mdl::path_code(0, k * NX + lane) : -1, fo[k], fm[k]);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int c = lane + 64 * q;
+            if (c >= NP && c < NP + NU) encu(Mdl::pathu_code(0, k * NU + (c - NP)), eo[q][k], em[q][k]);
+            else enc(c < NP ? Mdl::path_code(1, k * NP + c) : -1, eo[q][k], em[q][k]);
+        }
+    }
+    if (lane < NX) { go = NC + GX + lane; gm = STRIDE; }
+    double acc[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
+    double lam = lane < NX ? gb[(int64_t)T * NX + lane] : 0.0;             // lam_T = g_T
+    const int nchunk = (T + CH - 1) / CH;
+    const int ch = (T + nchunk - 1) / nchunk;      // chunks of equal length
+    for (int c = nchunk - 1; c >= 0; --c) {
+        const int t0 = c * ch, cnt = min(ch, T - t0);
+        wave_lds_sync();
+        if (lane < cnt) {
+            const int t = t0 + lane;
+            double xc[NX], uc[NU];
+            double* row = pool + lane * STRIDE;
+#pragma unroll
+            for (int i = 0; i < NX; ++i) { xc[i] = xb[t * NX + i]; row[GX + i] = gb[t * NX + i]; }
+#pragma unroll
+            for (int i = 0; i < NU; ++i) uc[i] = ub[t * NU + i];
+            PackedSink s{row}, su{row + Mdl::PATH_NVAR};
+            Mdl::eval_path(xc, uc, nullptr, th, pc, s);
+            Mdl::eval_pathu(xc, uc, nullptr, th, pc, su);
+        }
+        wave_lds_sync();
+        for (int tl = cnt - 1; tl >= 0; --tl) {
+            double m_new = blk[go + tl * gm];
+#pragma unroll
+            for (int k = 0; k < NX; ++k) {
+                const double lk = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(lam), k), __builtin_amdgcn_readlane(__double2loint(lam), k));
+                m_new += blk[fo[k] + tl * fm[k]] * lk;
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) acc[q] += blk[eo[q][k] + tl * em[q][k]] * lk;
+            }
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                if (64 * q + 63 >= NP && 64 * q < NP + NU) {               // (known per slot once unrolled: some lane of it holds a G column)
+                    const int cu = lane + 64 * q - NP;
+                    const bool isu = cu >= 0 && cu < NU;
+                    if (isu) pool[tl * STRIDE + SU + cu] = acc[q];         // dL/du_t[cu] = column cu of G_t . lam_{t+1}
+                    acc[q] = isu ? 0.0 : acc[q];
+                }
+            }
+            lam = m_new;
+        }
+        wave_lds_sync();
+        if (lane < cnt) {
+            const double* stage = pool + lane * STRIDE + SU;
+            double* out = grad_u + ((int64_t)b * T + t0 + lane) * NU;
+#pragma unroll
+            for (int j = 0; j < NU; ++j) out[j] = stage[j];
         }
     }
     if (grad_theta) {

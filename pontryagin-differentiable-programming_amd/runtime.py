@@ -1104,11 +1104,12 @@ class ModelLib:
         check(self.lib.pdp_sysid_auxsys_batched(B, T, ptr(x), ptr(u), ptr(th), tb, ptr(F), ptr(E), current_stream_ptr()), "pdp_sysid_auxsys_batched")
         return F, E
 
-    def sysid_rollout_vjp(self, x, u, theta, grad_x, want_ini=True, want_theta=True):
+    def sysid_rollout_vjp(self, x, u, theta, grad_x, want_ini=True, want_theta=True, want_inputs=False):
         """The rollout as a vector-Jacobian product (pdp_sysid_rollout_vjp_batched, include/pdp_hip_sysid_vjp.h: the semantics): x [B, T+1, n] the rollout of
         sysid_integrate for u [B, T, m] and theta ([p] or [B, p]), grad_x [B, T+1, n] = dL/dx of any scalar loss L -> dict(grad_theta [B, p] = dL/dtheta per trajectory,
-        grad_x0 [B, n] = dL/dx_0), one launch of the adjoint sweep.  want_ini / want_theta = False: that output is not computed (not both).  Shape errors are
-        ValueErrors before any launch."""
+        grad_x0 [B, n] = dL/dx_0), one launch of the adjoint sweep.  want_ini / want_theta = False: that output is not computed.  want_inputs=True: also grad_u [B, T, m] =
+        dL/du through the dynamics, from the same launch (pdp_sysid_rollout_vjp_u_batched, include/pdp_hip_sysid_vjp_u.h); without it the call is the one it always was.
+        Not all three switches off.  Shape errors are ValueErrors before any launch."""
         shape = lambda a: tuple(int(k) for k in (a.shape if hasattr(a, "shape") else np.shape(a)))
         su = shape(u)
         if len(su) != 3 or su[2] != self.m or su[0] < 1 or su[1] < 1:
@@ -1119,8 +1120,8 @@ class ModelLib:
                 raise ValueError("sysid_rollout_vjp: %s must be [B, T+1, n] = %s, got %s" % (name, (B, T + 1, self.n), shape(a)))
         if shape(theta) not in ((self.p,), (1, self.p), (B, self.p)):
             raise ValueError("sysid_rollout_vjp: theta must be [p] or [B, p] with p = %d, B = %d, got %s" % (self.p, B, shape(theta)))
-        if not (want_ini or want_theta):
-            raise ValueError("sysid_rollout_vjp: want_theta and want_ini are both False - nothing to compute")
+        if not (want_ini or want_theta or want_inputs):
+            raise ValueError("sysid_rollout_vjp: want_theta, want_ini and want_inputs are all False - nothing to compute")
         torch = torch_cuda()
         x, u, g, th = dev(x), dev(u), dev(grad_x), dev(theta)
         tb = self.p if (th.dim() == 2 and th.shape[0] == B and B > 1) else 0
@@ -1129,9 +1130,24 @@ class ModelLib:
             out["grad_theta"] = torch.empty((B, self.p), dtype=torch.float64, device="cuda")
         if want_ini:
             out["grad_x0"] = torch.empty((B, self.n), dtype=torch.float64, device="cuda")
+        if want_inputs:
+            out["grad_u"] = torch.empty((B, T, self.m), dtype=torch.float64, device="cuda")       # (written exactly once per step: no need to clear it)
+            check(self.lib.pdp_sysid_rollout_vjp_u_batched(B, T, ptr(x), ptr(u), ptr(th), tb, ptr(g), ptr(out["grad_theta"]) if want_theta else None,
+                                                           ptr(out["grad_x0"]) if want_ini else None, ptr(out["grad_u"]), current_stream_ptr()),
+                  "pdp_sysid_rollout_vjp_u_batched")
+            return out
         check(self.lib.pdp_sysid_rollout_vjp_batched(B, T, ptr(x), ptr(u), ptr(th), tb, ptr(g), ptr(out["grad_theta"]) if want_theta else None,
                                                      ptr(out["grad_x0"]) if want_ini else None, current_stream_ptr()), "pdp_sysid_rollout_vjp_batched")
         return out
+
+    def sysid_vjp_u_rows(self, B):
+        """pool rows (time steps per Jacobian pass) of sysid_rollout_vjp's kernel with want_inputs=True for a batch of B on this device, as the library itself decides
+        them (pdp_sysid_rollout_vjp_u_rows): the row there also holds the entries of G = df/du and m staging doubles, so the rows beyond four trajectories per
+        compute unit are fewer than sysid_vjp_rows' - the chunk edges the tests aim at"""
+        rows = int(self.lib.pdp_sysid_rollout_vjp_u_rows(int(B)))
+        if rows <= 0:
+            raise RuntimeError("pdp_sysid_rollout_vjp_u_rows failed: %s" % PDP_E.get(rows, rows))
+        return rows
 
     def sysid_vjp_rows(self, B, cus):
         """pool rows (time steps per Jacobian pass) of sysid_rollout_vjp's kernel for a batch of B on a chip of `cus` compute units: the host's rule
