@@ -1,6 +1,6 @@
 // pdp_chain_rule.h - the chain rule of the sum-of-squares loss through the sensitivity tiles of a forward sweep, once, for the four fused units:
-// oc_pdp_fused_kernel (pdp_model_kernels.h), oc_pdp_fused3_kernel (pdp_fused3_kernels.h), sysid_step_kernel (pdp_model_kernels.h) and sysid_step2_kernel
-// (pdp_cp_pair_kernels.h).  With the residuals d_t = x_t - x_demo,t (OC: also u_t - u_demo,t) and the sensitivities X_t = dx_t/dtheta, U_t = du_t/dtheta:
+// oc_pdp_fused_kernel (pdp_model_kernels.h), oc_pdp_fused3_kernel (pdp_fused3_kernels.h), sysid_step_kernel and sysid_step2_kernel (both in
+// pdp_sysid_step_kernels.h).  With the residuals d_t = x_t - x_demo,t (OC: also u_t - u_demo,t) and the sensitivities X_t = dx_t/dtheta, U_t = du_t/dtheta:
 //     loss = sum_t |d_t|^2      grad = sum_t d_t' X_t (+ d_t' U_t)      G = sum_t X_t' X_t (+ U_t' U_t)   (Gauss-Newton, J'J)
 // A unit's lane-per-step pass leaves d_t in the DLX / DLU slots of its LDS pool row (residual_slot); its sensitivity loop gathers them as the tiles DX, DU - the
 // residual of a row broadcast over its columns, element-aligned with X_t, U_t - and contracts step by step (contract_step); the stage T, which no pool row
@@ -8,7 +8,8 @@
 // IS FORMED INSIDE A HELPER (no pointer parameter is indexed; a reference names one element the caller chose): an address formed in a helper is simplified on its
 // own before the helper is inlined and then no longer folds with the kernel's other addresses as its own text did.  That is why the terminal row's loop over
 // dlT[row] stays in the kernels - as terminal_row(dlT, ...) it changed the LDS addressing, and with it the instructions, of the frozen instantiations, which
-// are to compile to what they compiled to with the text in place (profiles/chain_rule_code_object_diff.txt).
+// are to compile to what they compiled to with the text in place (profiles/chain_rule_code_object_diff.txt).  The two SysID kernels stand side by side in
+// pdp_sysid_step_kernels.h behind what they share (layout, argument pack, rollout); its header says which parts of the step stayed in their text, by the same rule.
 //
 // The modes - a template parameter of the kernels, never a run-time branch; an instantiation contains only its own arms:
 //   PDP_FUSED_PLAIN  loss and gradient of the demonstration loss (the frozen default);
@@ -84,12 +85,11 @@ struct FusedMode {
     static constexpr bool MISS = MODE == PDP_FUSED_MISS || MODE == PDP_FUSED_GN_MISS;
     static constexpr Residual RES = MISS ? RES_MISS : RES_PLAIN;          // (COT forms no residual: the cotangent takes the slot as it is)
 };
-template <int MODE, int NT, int NINI>                      // NT parameter tiles, NINI trailing kernel arguments (the x0 of the Gauss-Newton modes; INI: x0 and the mask)
+template <int MODE, int NT>                                // NT parameter tiles.  The kernels' trailing pack follows from MODE: SysidArgs<MODE> (pdp_sysid_step_kernels.h)
 struct SysidMode {
     static constexpr bool WLS = MODE == PDP_SYSID_GN_W || MODE == PDP_SYSID_GN_W_INI;             // (its own observed-rule: never together with MISS)
     static constexpr bool INI = MODE == PDP_SYSID_GN_INI || MODE == PDP_SYSID_GN_INI_MISS || MODE == PDP_SYSID_GN_W_INI;
-    static_assert(MODE == PDP_SYSID_PLAIN || (NT == 1 && NINI == 1 && (MODE == PDP_SYSID_GN || MODE == PDP_SYSID_GN_MISS)) || (NT == 1 && NINI == 2 && INI && !WLS) ||
-                      (NT == 1 && NINI == 2 && MODE == PDP_SYSID_GN_W) || (NT == 1 && NINI == 3 && MODE == PDP_SYSID_GN_W_INI), "instantiation");
+    static_assert(MODE == PDP_SYSID_PLAIN || (NT == 1 && MODE >= PDP_SYSID_GN && MODE <= PDP_SYSID_GN_W_INI), "instantiation");
     static constexpr bool GN = MODE != PDP_SYSID_PLAIN, MISS = MODE == PDP_SYSID_GN_MISS || MODE == PDP_SYSID_GN_INI_MISS;
     static constexpr Residual RES = MISS ? RES_MISS_DIFF : RES_PLAIN;
 };
@@ -131,8 +131,9 @@ PDP_DEV d4 gram_add(const d4 X, d4 Gn) {
 // ---- one step of the sensitivity loop.  DX, DU: the residual tiles of the step; X, U: its sensitivity tiles.  NR: the registers of DX that carry residuals
 // (n <= 4: 1); U (m <= 4 rows) lives on register 0.  mask_step, once per step of the OC units: with MISS the residuals and the sensitivity rows selected to 0 where
 // the residual is NaN (the selects are spelled on the tile elements, not through observed(): the form the kernels compiled from).  The SysID units have no control
-// part - contract_step without DU, U and gram_add, not a zero tile that would cost an MFMA - and keep the three lines of their MISS arm in their own text: through
-// mask_step their skip-missing instantiations gained or lost one to three instructions (profiles/chain_rule_code_object_diff.txt).
+// part - contract_step without DU, U and gram_add, not a zero tile that would cost an MFMA - and keep the three lines of their MISS arm in their own text
+// (pdp_sysid_step_kernels.h): through mask_step their skip-missing instantiations gained or lost one to three instructions
+// (profiles/chain_rule_code_object_diff.txt).
 template <bool MISS, int NR>
 PDP_DEV void mask_step(d4& DX, d4& DU, const d4 X, const d4 U, d4& Xm, d4& Um) {      // Xm, Um: X, U with MISS' mask
     if constexpr (MISS) {

@@ -190,184 +190,4 @@ __global__ void __launch_bounds__(128 * TPW) cp_step_poly2_kernel(int B, int T, 
     }
 }
 
-// Fused SysID.step (reference PDP/PDP.py:1178-1296: integrateSys with the given controls, getAuxSys, integrateAuxSys X_{t+1} = F X_t + E, chain rule with the
-// prediction error) as the same two-wave pipeline: wave R rolls the model out along the recorded controls, wave S follows a chunk behind with the Jacobians, the
-// prediction errors and the sensitivity recursion.  Same arithmetic in the same order as sysid_step_kernel (bit-identical, tests/test_gpu_cp_pair.py).
-// MODE, Ini: as in sysid_step_kernel (pdp_chain_rule.h).
-template <class Mdl, int NT, int TPW, int MODE = PDP_SYSID_PLAIN, class... Ini>
-__global__ void __launch_bounds__(128 * TPW) sysid_step2_kernel(int B, int T, const double* __restrict__ u, const double* __restrict__ xobs,
-                                                                 const double* __restrict__ theta, int tb, double* __restrict__ loss, double* __restrict__ grad, int slice,
-                                                                 Ini... ini) {
-    using SM = SysidMode<MODE, NT, sizeof...(Ini)>;
-    constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP, CH = Mdl::CHUNK;
-    constexpr int NC = 1 + Mdl::PATH_NCONST, DLX = Mdl::PATH_NVAR, STRIDE = (Mdl::PATH_NVAR + (SM::WLS ? 2 : 1) * NX) | 1;      // (WLS: s in the slots DLX + NX ..)
-    static_assert(TPW == 1 || TPW == 2 || TPW == 4, "trajectories per workgroup");
-    extern __shared__ __attribute__((aligned(16))) double lds_all[];
-    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, slot = wid & (TPW - 1);
-    const bool roller = wid < TPW;
-    const int b = blockIdx.x * TPW + slot;
-    const int bb = b < B ? b : B - 1;
-    const bool mine = b < B;
-    double* blk = lds_all + (size_t)slot * slice;
-    double* pool = blk + NC;
-    double* xs = pool + CH * STRIDE;         // (T+1) x NX
-    double* dlT = xs + (T + 1) * NX;         // NX   (WLS: and the NX scales of the terminal row behind them, at dlT + NX + 1)
-    double* us = dlT + NX + 1 + (SM::WLS ? NX : 0);         // T x NU
-    double* dump = us + T * NU;              // 64 + NX
-    int* fl = (int*)(dump + 64 + NX);        // stages rolled out so far
-    const double* ub = u + (int64_t)bb * T * NU;
-    const double* ob = xobs + (int64_t)bb * (T + 1) * NX;
-    [[maybe_unused]] const double* wb = nullptr;           // WLS: this trajectory's weights
-    if constexpr (SM::WLS) wb = sysid_wls(ini...).w + (int64_t)bb * sysid_wls(ini...).bstride;
-    if (roller) {
-        if (lane == 0) { blk[0] = 0.0; fl[0] = 0; }
-        for (int i_ = lane; i_ < Mdl::PATH_NCONST; i_ += 64) blk[1 + i_] = Mdl::path_const(i_);
-        for (int q = lane; q < T * NU; q += 64) us[q] = ub[q];
-    }
-    __syncthreads();                                          // the only workgroup barrier: constants, controls and the zeroed counter
-    double th[NP];
-    load_theta<Mdl>(theta, bb, tb, th);
-    double pc[Mdl::NPC];
-    Mdl::precompute(th, pc);
-    if (roller) {
-        double xc[NX], xn[NX], uc[NU], un[NU];
-#pragma unroll
-        for (int i = 0; i < NX; ++i) xc[i] = ob[i];                       // ini_state = batch_states[i][0] (PDP.py:1269)
-        if constexpr (SM::GN) {
-            if (const double* x0 = sysid_ini(ini...)) {
-#pragma unroll
-                for (int i = 0; i < NX; ++i) xc[i] = x0[(int64_t)bb * NX + i];
-            }
-        }
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < NX; ++i) xs[i] = xc[i];
-        }
-#pragma unroll
-        for (int i = 0; i < NU; ++i) un[i] = us[i];
-        for (int t = 0; t < T; ++t) {
-            const int tn = t + 1 < T ? t + 1 : t;
-#pragma unroll
-            for (int i = 0; i < NU; ++i) { uc[i] = un[i]; un[i] = us[tn * NU + i]; }
-            Mdl::dyn(xc, uc, th, pc, xn);
-#pragma unroll
-            for (int i = 0; i < NX; ++i) xc[i] = xn[i];
-            double* dx_ = lane == 0 ? xs + (t + 1) * NX : dump + lane;
-#pragma unroll
-            for (int i = 0; i < NX; ++i) dx_[i] = xn[i];
-            asm volatile("" ::: "memory");                   // progress for wave S: a plain LDS store behind the staging stores (see cp_step_poly2_kernel)
-            __hip_atomic_store(fl, t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-    } else {
-        const d4 z = zero4();
-        Gather gFT, gDX, gE[NT];
-        make_gather(gFT, lane, NC, STRIDE, [](int r, int c) { return (r < NX && c < NX) ? Mdl::path_code(0, c * NX + r) : -1; });
-        make_gather(gDX, lane, NC, STRIDE, [](int r, int c) { return (r < NX) ? DLX + r : -1; });
-        [[maybe_unused]] Gather gS;                        // WLS: the scales s of the rows
-        if constexpr (SM::WLS) make_gather(gS, lane, NC, STRIDE, [](int r, int c) { return (r < NX) ? DLX + NX + r : -1; });
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-            make_gather(gE[j], lane, NC, STRIDE, [j](int r, int c) { return (r < NX && 16 * j + c < NP) ? Mdl::path_code(1, r * NP + 16 * j + c) : -1; });
-        d4 X[NT];
-        double acc[NT], lsum = 0.0;
-        [[maybe_unused]] d4 Gn = z;                        // GN: sum_t X_t' X_t
-#pragma unroll
-        for (int j = 0; j < NT; ++j) { X[j] = z; acc[j] = 0.0; }
-        if constexpr (SM::INI) X[0] = sysid_ini_tile<NX, NP>(lane, sysid_ini_mask(ini...));      // X_0: the unit columns of the estimated components of x0
-        const int nchunk = (T + CH - 1) / CH;
-        const int ch = (T + nchunk - 1) / nchunk;
-        for (int c = 0; c < nchunk; ++c) {
-            const int t0 = c * ch, cnt = min(ch, T - t0);
-            wg_wait_ge(fl, t0 + cnt);                        // x_t of the chunk's stages are in the staging (x_{t0+cnt-1} was stored by step t0+cnt-2; the counter is past it)
-            wave_lds_sync();
-            if (lane < cnt) {
-                const int t = t0 + lane;
-                double xc[NX], uc[NU];
-                double* row = pool + lane * STRIDE;
-#pragma unroll
-                for (int i = 0; i < NX; ++i) {
-                    xc[i] = xs[t * NX + i];
-                    if constexpr (SM::WLS) wls_slot(row[DLX + i], row[DLX + NX + i], xc[i], ob[t * NX + i], wb[t * NX + i], sysid_wls(ini...), lsum);
-                    else residual_slot<SM::RES>(row[DLX + i], xc[i], ob[t * NX + i], lsum);
-                }
-#pragma unroll
-                for (int i = 0; i < NU; ++i) uc[i] = us[t * NU + i];
-                PackedSink s{row};
-                Mdl::eval_path(xc, uc, nullptr, th, pc, s);
-            }
-            wave_lds_sync();
-            for (int tl = 0; tl < cnt; ++tl) {
-                d4 FT = gather_tile(blk, gFT, tl);
-                d4 DX = gather_tile(blk, gDX, tl);
-#pragma unroll
-                for (int j = 0; j < NT; ++j) {
-                    d4 E = gather_tile(blk, gE[j], tl);
-                    if constexpr (SM::WLS) {          // DX carries s d, Xm = s X: grad += (s d)' (s X), G += (s X)' (s X)
-                        const d4 Xm = wls_scale(gather_tile(blk, gS, tl), X[j]);
-                        acc[j] += contract_step(DX, Xm);
-                        Gn = gram_add<false>(Xm, Gn);
-                    } else
-                    if constexpr (SM::MISS) {         // (pdp_chain_rule.h: mask_step, in this kernel's own text; NT == 1)
-                        d4 Xm;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) { const bool obs = DX[r] == DX[r]; Xm[r] = obs ? X[j][r] : 0.0; DX[r] = obs ? DX[r] : 0.0; }
-                        acc[j] += contract_step(DX, Xm);
-                        Gn = gram_add<false>(Xm, Gn);
-                    } else {
-                    acc[j] += contract_step(DX, X[j]);
-                    if constexpr (SM::GN) Gn = gram_add<false>(X[j], Gn);
-                    }
-                    X[j] = mma_tn(FT, X[j], E);
-                }
-            }
-        }
-        wg_wait_ge(fl, T);                                   // x_T
-        wave_lds_sync();
-        if (lane < NX) {
-            if constexpr (SM::WLS) wls_slot(dlT[lane], dlT[NX + 1 + lane], xs[T * NX + lane], ob[T * NX + lane], wb[T * NX + lane], sysid_wls(ini...), lsum);
-            else
-            if constexpr (SM::MISS) { const double o = ob[T * NX + lane]; residual_slot<SM::RES>(dlT[lane], xs[T * NX + lane], o, lsum); }      // (x_obs first, as in sysid_step_kernel)
-            else residual_slot<SM::RES>(dlT[lane], xs[T * NX + lane], ob[T * NX + lane], lsum);
-        }
-        wave_lds_sync();
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = tile_row(lane, r);
-                if constexpr (SM::WLS) { if (row < NX) { const double sT = dlT[NX + 1 + row]; X[j][r] = sT != 0.0 ? sT * X[j][r] : 0.0; acc[j] += dlT[row] * X[j][r]; } }      // (X_T scaled in place)
-                else
-                if constexpr (SM::MISS) {              // (observed(), in this kernel's own text: through it two of the five models' instantiations lost an instruction; X_T is masked in place)
-                    if (row < NX) { const double d = dlT[row]; const bool obs = d == d; X[j][r] = obs ? X[j][r] : 0.0; acc[j] += (obs ? d : 0.0) * X[j][r]; }
-                } else {
-                if (row < NX) acc[j] += dlT[row] * X[j][r];
-                }
-            }
-            double a = sum_over_rowgroups(acc[j]);
-            if constexpr (SM::INI) {                       // the row of W = p + q unknowns: grad [W] | loss | G [W][W]
-                Gn = gram_add<false>(X[j], Gn);            // X_T
-                if (mine) {
-                    const int W = sysid_ini_width<NP>(sysid_ini_mask(ini...));
-                    double* row = grad + (int64_t)b * (W + 1 + W * W);
-                    if (lane < W) row[lane] = a;
-                    sysid_ini_store(row + W + 1, W, lane, Gn);
-                }
-            } else if constexpr (SM::GN) {
-                Gn = gram_add<false>(X[j], Gn);            // X_T
-                if (mine) {
-                    if (lane < NP) grad[(int64_t)b * (NP + 1 + NP * NP) + lane] = a;
-                    store_dense(grad + (int64_t)b * (NP + 1 + NP * NP) + NP + 1, NP, NP, NP, 0, 0, lane, Gn);
-                }
-            } else {
-            if (mine && lane < 16 && 16 * j + lane < NP) grad[(int64_t)b * NP + 16 * j + lane] = a;
-            }
-        }
-        lsum = wave_sum(lsum);
-        if (mine && lane == 0) loss[b] = lsum;
-        if constexpr (SM::INI) { const int W = sysid_ini_width<NP>(sysid_ini_mask(ini...)); if (mine && lane == 0) grad[(int64_t)b * (W + 1 + W * W) + W] = lsum; }
-        else
-        if constexpr (SM::GN) { if (mine && lane == 0) grad[(int64_t)b * (NP + 1 + NP * NP) + NP] = lsum; }
-    }
-}
-
 }  // namespace pdp

@@ -26,6 +26,7 @@ namespace pdp { extern __device__ long long g_rb_stamp[16]; }
 #include "pdp_cp_mlp_kernels.h"
 #include "pdp_fused3_kernels.h"
 #include "pdp_cp_pair_kernels.h"
+#include "pdp_sysid_step_kernels.h"
 #include "pdp_cp_generic_kernels.h"
 #include "pdp_sysid_vjp_kernels.h"
 #include "pdp_launch.h"
@@ -604,13 +605,11 @@ int64_t sysid_step_ws_bytes(int B, int T) {
 // exist for p <= 16.  PDP_SYSID_GN_INI / PDP_SYSID_GN_INI_MISS: the Gauss-Newton modes with the components of x0 that `ini_mask` names as further unknowns (the
 // kernels' second trailing argument; the row is grad | loss | G over W = p + popcount(ini_mask) <= 16 unknowns).  PDP_SYSID_GN_W / PDP_SYSID_GN_W_INI: weighted and
 // Huber-robust least squares on PDP_SYSID_GN / PDP_SYSID_GN_INI (`wls`, the kernels' last trailing argument; NX more words per pool row and behind dlT, and the
-// Gauss-Newton modes' eight workgroups per CU in the given-trajectory kernel).  Same dispatch, thresholds and switches in every mode.
+// Gauss-Newton modes' eight workgroups per CU in the given-trajectory kernel).  The LDS slice and the trailing pack follow from MODE: SysidLayout, SysidArgs.  Same dispatch, thresholds and switches in every mode.
 template <class Mdl, int MODE = PDP_SYSID_PLAIN>
 int sysid_step(int B, int T, const double* u, const double* xobs, const double* th, int tb, double* loss, double* grad, void* ws, int64_t wsb, void* st,
                const double* x0 = nullptr, [[maybe_unused]] unsigned ini_mask = 0, [[maybe_unused]] SysidWls wls = {}) {
-    constexpr bool WLS = MODE == PDP_SYSID_GN_W || MODE == PDP_SYSID_GN_W_INI;
-    constexpr bool INI = MODE == PDP_SYSID_GN_INI || MODE == PDP_SYSID_GN_INI_MISS || MODE == PDP_SYSID_GN_W_INI;
-    constexpr int EXTRA = WLS ? Mdl::NX : 0;                // further words per pool row (sysid_slice)
+    constexpr bool INI = SysidMode<MODE, 1>::INI;
     if constexpr (Mdl::KIND == PDP_KIND_SYSID && Mdl::NX <= 16 && Mdl::NP <= (MODE == PDP_SYSID_PLAIN ? 64 : (INI ? 15 : 16))) {
         if (B <= 0 || T <= 0 || !u || !xobs || !th || !loss || !grad) return PDP_E_ARG;
         if constexpr (INI) { if (Mdl::NP + __builtin_popcount(ini_mask) > 16) return PDP_E_SIZE; }
@@ -626,24 +625,18 @@ int sysid_step(int B, int T, const double* u, const double* xobs, const double* 
         static const int rows_env = env_int("PDP_SYSID_ROWS", 0), wgs_env = env_int("PDP_SYSID_GIVEN_WGS", 0);
         const int cus = device_cu_count();
         const int rows = rows_env > 0 ? (rows_env < Mdl::CHUNK ? rows_env : Mdl::CHUNK)
-                         : (xgiven ? sysid_rows_given<Mdl>(T, wgs_env > 0 ? wgs_env : SYSID_GIVEN_WGS<MODE>, EXTRA) : sysid_rows<Mdl>(B, T, cus, EXTRA));
-        const size_t lds = sizeof(double) * (size_t)sysid_slice<Mdl>(T, rows, xgiven != nullptr, EXTRA);
+                         : (xgiven ? sysid_rows_given<Mdl, MODE>(T, wgs_env > 0 ? wgs_env : SYSID_GIVEN_WGS<MODE>) : sysid_rows<Mdl, MODE>(B, T, cus));
+        const size_t lds = sizeof(double) * (size_t)sysid_slice<Mdl, MODE>(T, rows, xgiven != nullptr);
         if (lds > 150 * 1024) return PDP_E_SIZE;
-        // the kernels' trailing arguments, a tuple whose TYPE is fixed by MODE: the kernels' `Ini...` is spelled from its element types, never from a call's arguments
-        const auto trailing = [&] {
-            if constexpr (MODE == PDP_SYSID_PLAIN) return std::tuple<>{};
-            else if constexpr (WLS && INI) return std::tuple<const double*, unsigned, SysidWls>{x0, ini_mask, wls};
-            else if constexpr (WLS) return std::tuple<const double*, SysidWls>{x0, wls};
-            else if constexpr (INI) return std::tuple<const double*, unsigned>{x0, ini_mask};
-            else return std::tuple<const double*>{x0};
-        }();
-        // PDP_SYSID_VARIANT: 2 = rollout wave + sensitivity wave per trajectory (pdp_cp_pair_kernels.h), the default; 1 = one wavefront per trajectory
+        // the kernels' trailing arguments, a tuple whose TYPE is fixed by MODE (SysidArgs): the kernels' `Ini...` is spelled from its element types, never from a call's arguments
+        const SysidArgs<MODE> trailing = sysid_args<MODE>(x0, ini_mask, wls);
+        // PDP_SYSID_VARIANT: 2 = rollout wave + sensitivity wave per trajectory (sysid_step2_kernel), the default; 1 = one wavefront per trajectory
         static const int variant = env_int("PDP_SYSID_VARIANT", 2);
         return std::apply([&](auto... extra) {
             // the pair pays while SIMDs would idle (B = 256, T = 200: 0.105 -> 0.072 ms); once every SIMD has a trajectory the two waves only share what one had
             // (B = 1024: 0.0667 against 0.0685 ms, profiles/r03_pair_pipeline.txt) - the one-wave kernel stays for those batches
             if (variant == 2 && B <= 2 * cus && !xgiven) {
-                const int slice = sysid_slice<Mdl>(T, Mdl::CHUNK, false, EXTRA), tpw = traj_per_workgroup(B, cus, 2);
+                const int slice = sysid_slice<Mdl, MODE>(T, Mdl::CHUNK, false), tpw = traj_per_workgroup(B, cus, 2);
                 if (slice * tpw * (int)sizeof(double) <= 160 * 1024)
                     return with_int<1, 2>(tpw, [&](auto K) {
                         return launch(sysid_step2_kernel<Mdl, NT, K(), MODE, decltype(extra)...>, dim3((B + K() - 1) / K()), dim3(128 * K()), slice * K() * sizeof(double),

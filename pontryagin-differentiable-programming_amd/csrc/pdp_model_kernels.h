@@ -1740,207 +1740,4 @@ __global__ void __launch_bounds__(64) sysid_auxsys_kernel(int B, int T, const do
     Mdl::eval_path(xc, uc, nullptr, th, pc, s);
 }
 
-// doubles of LDS per trajectory of the fused SysID.step kernels (sysid_step_kernel below, sysid_step2_kernel in pdp_cp_pair_kernels.h):
-// [cpool | pool CH rows | x (T+1) x NX | dlT NX + 1 | u T x NU | dump 64 + NX | hand-over counter, padding]
-// extra: further words per pool row and behind dlT (PDP_SYSID_GN_W*: NX, the scales s beside the residuals; every other mode: 0)
-template <class Mdl>
-__host__ __device__ inline int sysid_slice(int T, int rows = Mdl::CHUNK, bool given = false, int extra = 0) {      // given: the trajectory and the controls stay in global memory (no staging)
-    const int n = 1 + Mdl::PATH_NCONST + rows * ((Mdl::PATH_NVAR + Mdl::NX + extra) | 1) + (given ? 0 : (T + 1) * Mdl::NX) + Mdl::NX + 1 + extra + (given ? 0 : T * Mdl::NU) + 64 + Mdl::NX + 8;
-    return (n + 1) & ~1;
-}
-// pool rows of the given-trajectory mode: what lets `wgs` workgroups (wavefronts) share a CU's 160 KB.  12 = three wavefronts per SIMD, what the 162 VGPRs of that
-// instantiation allow (forced to 128 registers for four waves it spills 28); measured 8 / 12 / 16: 0.316 / 0.293 / 0.298 ms at B = 8192 (profiles/r04_rollout_prepass.txt)
-template <class Mdl>
-__host__ inline int sysid_rows_given(int T, int wgs, int extra = 0) {
-    const int stride = (Mdl::PATH_NVAR + Mdl::NX + extra) | 1;
-    const int fit = (160 * 1024 / 8 / wgs - 64 - sysid_slice<Mdl>(T, 0, true, extra)) / stride;
-    return fit >= 4 ? (fit < Mdl::CHUNK ? fit : Mdl::CHUNK) : (Mdl::CHUNK < 4 ? Mdl::CHUNK : 4);
-}
-// Pool rows (stages per lane-parallel Jacobian pass) of sysid_step_kernel.  The generated CHUNK (a 17 KB pool for the quadrotor) makes a workgroup 31 KB: five
-// wavefronts per CU - fine while there is at most one trajectory per SIMD.  A batch with several trajectories per SIMD (C5's total of 8192 on one GPU: eight rounds)
-// is served better by TWO resident waves per SIMD that fill each other's latency gaps (two waves take 1.4x the time of one): the pool is
-// cut to what lets eight workgroups share the CU's 160 KB.
-template <class Mdl>
-__host__ inline int sysid_rows(int B, int T, int cus, int extra = 0) {
-    if (B <= 4 * cus) return Mdl::CHUNK;
-    const int stride = (Mdl::PATH_NVAR + Mdl::NX + extra) | 1;
-    const int fit = (160 * 1024 / 8 / 8 - 64 - sysid_slice<Mdl>(T, 0, false, extra)) / stride;      // (64 doubles of slack for the allocation granularity)
-    return fit >= 4 ? (fit < Mdl::CHUNK ? fit : Mdl::CHUNK) : Mdl::CHUNK;
-}
-PDP_DEV const double* sysid_ini() { return nullptr; }                     // the trailing x0 argument of the Gauss-Newton modes (PDP_SYSID_PLAIN has none)
-PDP_DEV const double* sysid_ini(const double* x0) { return x0; }
-PDP_DEV const double* sysid_ini(const double* x0, unsigned) { return x0; }      // PDP_SYSID_GN_INI*: x0 and the mask of its estimated components
-PDP_DEV unsigned sysid_ini_mask(const double*, unsigned mask) { return mask; }
-PDP_DEV const double* sysid_ini(const double* x0, SysidWls) { return x0; }                 // PDP_SYSID_GN_W: x0 and the weights' arguments
-PDP_DEV const double* sysid_ini(const double* x0, unsigned, SysidWls) { return x0; }       // PDP_SYSID_GN_W_INI: x0, the mask, the weights' arguments
-PDP_DEV unsigned sysid_ini_mask(const double*, unsigned mask, SysidWls) { return mask; }
-PDP_DEV SysidWls sysid_wls(const double*, SysidWls a) { return a; }
-PDP_DEV SysidWls sysid_wls(const double*, unsigned, SysidWls a) { return a; }
-
-// Fused SysID.step per trajectory: rollout (uniform, x kept in LDS) then X_{t+1} = F X_t + E on MFMA tiles.  MODE: one of PDP_SYSID_* (pdp_chain_rule.h;
-// pdp_sysid_step_gn_batched selects PDP_SYSID_GN / PDP_SYSID_GN_MISS, pdp_sysid_step_gn_ini_batched PDP_SYSID_GN_INI / PDP_SYSID_GN_INI_MISS,
-// pdp_sysid_step_wls_batched PDP_SYSID_GN_W / PDP_SYSID_GN_W_INI).
-template <class Mdl, int NT, bool GIVEN = false, int MODE = PDP_SYSID_PLAIN, class... Ini>
-__global__ void __launch_bounds__(64) sysid_step_kernel(int B, int T, const double* __restrict__ u, const double* __restrict__ xobs,
-                                                         const double* __restrict__ theta, int tb, double* __restrict__ loss, double* __restrict__ grad, int CH,
-                                                         const double* __restrict__ xgiven_, Ini... ini) {
-    using SM = SysidMode<MODE, NT, sizeof...(Ini)>;
-    const double* __restrict__ xgiven = GIVEN ? xgiven_ : nullptr;      // (a template parameter: each instantiation keeps its own register allocation)
-    // xgiven [B][T+1][NX] (GIVEN): the trajectory, rolled out beforehand by sysid_integrate_kernel with ONE LANE per trajectory - the mode for batches with several
-    // trajectories per SIMD: the rollout below runs one trajectory on all 64 lanes (the same value in every lane), which is the right thing while the SIMD has nothing
-    // else to do and 63/64 wasted once other trajectories wait for it (C5a's 8192 on one GPU: 8 rounds of a 26 us rollout against one 21 us pass for all of them)
-    constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP;
-    constexpr int NC = 1 + Mdl::PATH_NCONST, DLX = Mdl::PATH_NVAR, STRIDE = (Mdl::PATH_NVAR + (SM::WLS ? 2 : 1) * NX) | 1;      // (WLS: s in the slots DLX + NX ..)
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    double* blk = lds;
-    double* pool = blk + NC;
-    double* xs = pool + CH * STRIDE;         // (T+1) x NX   (not in the given-trajectory mode: stages are evaluated from global memory there)
-    double* dlT = xs + (xgiven ? 0 : (T + 1) * NX);         // NX   (WLS: and the NX scales of the terminal row behind them, at dlT + NX + 1)
-    double* us = dlT + NX + 1 + (SM::WLS ? NX : 0);         // T x NU: the given controls, staged once with coalesced loads (rollout mode only)
-    double* dump = us + (xgiven ? 0 : T * NU);              // 64 + NX words nobody reads (see the rollout)
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const d4 z = zero4();
-    double th[NP];
-    load_theta<Mdl>(theta, b, tb, th);
-    double pc[Mdl::NPC];
-    Mdl::precompute(th, pc);
-    const double* ub = u + (int64_t)b * T * NU;
-    const double* ob = xobs + (int64_t)b * (T + 1) * NX;
-    [[maybe_unused]] const double* wb = nullptr;           // WLS: this trajectory's weights
-    if constexpr (SM::WLS) wb = sysid_wls(ini...).w + (int64_t)b * sysid_wls(ini...).bstride;
-    if (lane == 0) blk[0] = 0.0;
-    for (int i_ = lane; i_ < Mdl::PATH_NCONST; i_ += 64) blk[1 + i_] = Mdl::path_const(i_);
-    const double* xg = xgiven ? xgiven + (int64_t)b * (T + 1) * NX : nullptr;
-    if (!xgiven) for (int q = lane; q < T * NU; q += 64) us[q] = ub[q];
-    __syncthreads();
-    if constexpr (!GIVEN) {
-        // rollout (uniform).  u_t comes from the LDS staging, requested one step ahead (read from global memory inside the loop every step waited for a round
-        // trip to memory); x_{t+1} goes to the staging from lane 0 without a conditional block (cp_step_poly_kernel)
-        double xc[NX], xn[NX], uc[NU], un[NU];
-#pragma unroll
-        for (int i = 0; i < NX; ++i) xc[i] = ob[i];                       // ini_state = batch_states[i][0] (PDP.py:1269)
-        if constexpr (SM::GN) {
-            if (const double* x0 = sysid_ini(ini...)) {
-#pragma unroll
-                for (int i = 0; i < NX; ++i) xc[i] = x0[(int64_t)b * NX + i];
-            }
-        }
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < NX; ++i) xs[i] = xc[i];
-        }
-#pragma unroll
-        for (int i = 0; i < NU; ++i) un[i] = us[i];
-        for (int t = 0; t < T; ++t) {
-            const int tn = t + 1 < T ? t + 1 : t;
-#pragma unroll
-            for (int i = 0; i < NU; ++i) { uc[i] = un[i]; un[i] = us[tn * NU + i]; }
-            Mdl::dyn(xc, uc, th, pc, xn);
-#pragma unroll
-            for (int i = 0; i < NX; ++i) xc[i] = xn[i];
-            double* dx_ = lane == 0 ? xs + (t + 1) * NX : dump + lane;
-#pragma unroll
-            for (int i = 0; i < NX; ++i) dx_[i] = xn[i];
-        }
-    }
-    __syncthreads();
-    Gather gFT, gDX, gE[NT];
-    make_gather(gFT, lane, NC, STRIDE, [](int r, int c) { return (r < NX && c < NX) ? Mdl::path_code(0, c * NX + r) : -1; });
-    make_gather(gDX, lane, NC, STRIDE, [](int r, int c) { return (r < NX) ? DLX + r : -1; });
-    [[maybe_unused]] Gather gS;                            // WLS: the scales s of the rows
-    if constexpr (SM::WLS) make_gather(gS, lane, NC, STRIDE, [](int r, int c) { return (r < NX) ? DLX + NX + r : -1; });
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-        make_gather(gE[j], lane, NC, STRIDE, [j](int r, int c) { return (r < NX && 16 * j + c < NP) ? Mdl::path_code(1, r * NP + 16 * j + c) : -1; });
-    d4 X[NT];
-    double acc[NT], lsum = 0.0;
-    [[maybe_unused]] d4 Gn = z;                            // GN: sum_t X_t' X_t
-#pragma unroll
-    for (int j = 0; j < NT; ++j) { X[j] = z; acc[j] = 0.0; }
-    if constexpr (SM::INI) X[0] = sysid_ini_tile<NX, NP>(lane, sysid_ini_mask(ini...));      // X_0: the unit columns of the estimated components of x0
-    const int nchunk = (T + CH - 1) / CH;
-    const int ch = (T + nchunk - 1) / nchunk;      // chunks of equal length
-    for (int c = 0; c < nchunk; ++c) {
-        const int t0 = c * ch, cnt = min(ch, T - t0);
-        __syncthreads();
-        if (lane < cnt) {
-            const int t = t0 + lane;
-            double xc[NX], uc[NU];
-            double* row = pool + lane * STRIDE;
-#pragma unroll
-            for (int i = 0; i < NX; ++i) {
-                xc[i] = xg ? xg[t * NX + i] : xs[t * NX + i];
-                if constexpr (SM::WLS) wls_slot(row[DLX + i], row[DLX + NX + i], xc[i], ob[t * NX + i], wb[t * NX + i], sysid_wls(ini...), lsum);
-                else residual_slot<SM::RES>(row[DLX + i], xc[i], ob[t * NX + i], lsum);
-            }
-#pragma unroll
-            for (int i = 0; i < NU; ++i) uc[i] = xg ? ub[t * NU + i] : us[t * NU + i];
-            PackedSink s{row};
-            Mdl::eval_path(xc, uc, nullptr, th, pc, s);
-        }
-        __syncthreads();
-        for (int tl = 0; tl < cnt; ++tl) {
-            d4 FT = gather_tile(blk, gFT, tl);
-            d4 DX = gather_tile(blk, gDX, tl);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                d4 E = gather_tile(blk, gE[j], tl);
-                if constexpr (SM::WLS) {          // DX carries s d, Xm = s X: grad += (s d)' (s X), G += (s X)' (s X)
-                    const d4 Xm = wls_scale(gather_tile(blk, gS, tl), X[j]);
-                    acc[j] += contract_step(DX, Xm);
-                    Gn = gram_add<false>(Xm, Gn);
-                } else
-                if constexpr (SM::MISS) {         // (pdp_chain_rule.h: mask_step, in this kernel's own text; NT == 1)
-                    d4 Xm;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { const bool obs = DX[r] == DX[r]; Xm[r] = obs ? X[j][r] : 0.0; DX[r] = obs ? DX[r] : 0.0; }
-                    acc[j] += contract_step(DX, Xm);
-                    Gn = gram_add<false>(Xm, Gn);
-                } else {
-                acc[j] += contract_step(DX, X[j]);
-                if constexpr (SM::GN) Gn = gram_add<false>(X[j], Gn);
-                }
-                X[j] = mma_tn(FT, X[j], E);
-            }
-        }
-    }
-    __syncthreads();
-    if (lane < NX) {
-        if constexpr (SM::WLS) wls_slot(dlT[lane], dlT[NX + 1 + lane], xg ? xg[T * NX + lane] : xs[T * NX + lane], ob[T * NX + lane], wb[T * NX + lane], sysid_wls(ini...), lsum);
-        else
-        if constexpr (SM::MISS) { const double o = ob[T * NX + lane]; residual_slot<SM::RES>(dlT[lane], xg ? xg[T * NX + lane] : xs[T * NX + lane], o, lsum); }      // (x_obs first, as it always was here)
-        else residual_slot<SM::RES>(dlT[lane], xg ? xg[T * NX + lane] : xs[T * NX + lane], ob[T * NX + lane], lsum);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = tile_row(lane, r);
-            if constexpr (SM::WLS) { if (row < NX) { const double sT = dlT[NX + 1 + row]; X[j][r] = sT != 0.0 ? sT * X[j][r] : 0.0; acc[j] += dlT[row] * X[j][r]; } }      // (X_T scaled in place)
-            else
-            if (row < NX) { const double d = dlT[row]; X[j][r] = observed<SM::MISS>(d, X[j][r]); acc[j] += observed<SM::MISS>(d, d) * X[j][r]; }      // (MISS: X_T masked in place)
-        }
-        double a = sum_over_rowgroups(acc[j]);
-        if constexpr (SM::INI) {                           // the row of W = p + q unknowns: grad [W] | loss | G [W][W]
-            const int W = sysid_ini_width<NP>(sysid_ini_mask(ini...));
-            double* row = grad + (int64_t)b * (W + 1 + W * W);
-            if (lane < W) row[lane] = a;
-            Gn = gram_add<false>(X[j], Gn);                // X_T
-            sysid_ini_store(row + W + 1, W, lane, Gn);
-        } else if constexpr (SM::GN) {
-            if (lane < NP) grad[(int64_t)b * (NP + 1 + NP * NP) + lane] = a;
-            Gn = gram_add<false>(X[j], Gn);                // X_T
-            store_dense(grad + (int64_t)b * (NP + 1 + NP * NP) + NP + 1, NP, NP, NP, 0, 0, lane, Gn);
-        } else {
-        if (lane < 16 && 16 * j + lane < NP) grad[(int64_t)b * NP + 16 * j + lane] = a;
-        }
-    }
-    lsum = wave_sum(lsum);
-    if (lane == 0) loss[b] = lsum;
-    if constexpr (SM::INI) { const int W = sysid_ini_width<NP>(sysid_ini_mask(ini...)); if (lane == 0) grad[(int64_t)b * (W + 1 + W * W) + W] = lsum; }
-    else
-    if constexpr (SM::GN) { if (lane == 0) grad[(int64_t)b * (NP + 1 + NP * NP) + NP] = lsum; }
-}
-
 }  // namespace pdp

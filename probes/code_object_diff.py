@@ -1,4 +1,5 @@
-"""Are the gfx950 code objects of two builds the same kernels?  python probes/code_object_diff.py <libdir A> <libdir B> [--rename REGEX REPL] [--allow-added]   (no GPU needed)
+"""Are the gfx950 code objects of two builds the same kernels?  python probes/code_object_diff.py <libdir A> <libdir B> [--rename REGEX REPL] [--allow-added] [--classify]
+(no GPU needed)
 
 For every library (*.so) of the two directories - e.g. pontryagin-differentiable-programming_amd/lib of a checkout of the parent commit and of the working tree,
 both after __graft_entry__.build() - the code object is unbundled (codegen.code_object_text) and compared:
@@ -14,7 +15,12 @@ failed - what a change that ADDS instantiations is checked with (profiles/sysid_
 disassembler's `...` for padding, the footer of the metadata) belongs to no kernel and is dropped: a kernel that is the last one in A need not be in B.
 --ignore-trailing-nops: the run of `s_nop 0` behind the last instruction of a symbol - the assembler's padding up to the alignment of the next function of the same
 section, behind an s_endpgm or an unconditional branch and never executed - is dropped on both sides: for a kernel that becomes a template instantiation, which gets a
-section of its own and with it no such padding (profiles/lm_prior_code_object_diff.txt)."""
+section of its own and with it no such padding (profiles/lm_prior_code_object_diff.txt).
+--classify: for every symbol whose instructions differ, one more line with generic counts - the instruction count of both sides, the number of changed lines of a
+sequence match, the difference of the opcode multisets (the first word of every instruction) and whether the metadata entry is the same text: what a change that
+moves kernel text into shared helpers is judged by (profiles/sysid_shared_body_code_object_diff.txt).  The exit status stays 1 on any difference."""
+import collections
+import difflib
 import glob
 import os
 import re
@@ -63,7 +69,17 @@ def metadata(notes):
     return out
 
 
-def main(dir_a, dir_b, allow_added=False):
+def classify(a, b):
+    """generic counts of two instruction lists that differ: 'n_a -> n_b instructions, k lines changed, opcodes: same multiset | {opcode: count in b - count in a}'"""
+    sm = difflib.SequenceMatcher(None, a, b, autojunk=False)
+    changed = sum(max(i2 - i1, j2 - j1) for tag, i1, i2, j1, j2 in sm.get_opcodes() if tag != "equal")
+    ca, cb = (collections.Counter(i.split()[0] for i in x) for x in (a, b))
+    delta = {k: cb[k] - ca[k] for k in sorted(set(ca) | set(cb)) if cb[k] != ca[k]}
+    ops = "same multiset" if not delta else " ".join("%s %+d" % kv for kv in delta.items())
+    return "%d -> %d instructions, %d lines changed, opcodes: %s" % (len(a), len(b), changed, ops)
+
+
+def main(dir_a, dir_b, allow_added=False, do_classify=False):
     names = [sorted(os.path.basename(p) for p in glob.glob(os.path.join(d, "*.so"))) for d in (dir_a, dir_b)]
     bad = int(names[0] != names[1])
     if bad:
@@ -86,6 +102,10 @@ def main(dir_a, dir_b, allow_added=False):
               % (lib, len(ma), len(sa), sum(len(v) for v in sa.values()), masked, "moved" if moved else "same ", ("DIFFERENT" if diffs else "identical") + extra))
         for d in diffs:
             print("    " + d)
+        if do_classify:
+            for sym in sa:
+                if sym in sb and sa[sym] != sb[sym]:
+                    print("    classify %s: %s, metadata %s" % (sym, classify(sa[sym], sb[sym]), "same" if ma.get(sym) == mb.get(sym) else "DIFFERENT"))
         bad += len(diffs)
     print("code objects %s" % ("DIFFER" if bad else "identical: same symbols, same instructions, same metadata in every library"))
     return 1 if bad else 0
@@ -99,5 +119,6 @@ if __name__ == "__main__":
         del argv[i:i + 3]
     allow = "--allow-added" in argv
     IGNORE_TRAILING_NOPS = "--ignore-trailing-nops" in argv
-    argv = [a for a in argv if a not in ("--allow-added", "--ignore-trailing-nops")]
-    sys.exit(main(argv[0], argv[1], allow))
+    do_classify = "--classify" in argv
+    argv = [a for a in argv if a not in ("--allow-added", "--ignore-trailing-nops", "--classify")]
+    sys.exit(main(argv[0], argv[1], allow, do_classify))
