@@ -778,6 +778,14 @@ class SysID(_CasadiFrontEnd):
         torch.autograd layer."""
         return self.model().sysid_rollout_vjp(state_traj, inputs, auxvar_value, grad_state, want_ini=want_ini, want_theta=want_theta, want_inputs=want_inputs)
 
+    def rollout_jvp_batch(self, state_traj, inputs, auxvar_value, d_auxvar=None, d_ini_state=None, d_inputs=None):
+        """The tangent of the rollouts state_traj = integrateDyn_batch(ini_state, inputs, auxvar_value) along a direction, for a batch: d_auxvar ([p]: shared by the
+        batch, or [B, p]), d_ini_state [B, n], d_inputs [B, T, m], each None for zero (not all of them) -> d_state [B, T+1, n] = J v by the tangent sweep
+        d_x[t+1] = F_t d_x[t] + E_t d_auxvar + G_t d_inputs[t] in one launch (include/pdp_hip_sysid_jvp.h) - the other half of rollout_vjp_batch: a Gauss-Newton product
+        J' J v of any residual of the rollout is this call followed by that one.  pdp_amd.autograd.sysid_trajectory uses it for torch.autograd.forward_ad,
+        pdp_amd.irl.MatrixFreeLM for Levenberg-Marquardt with a conjugate-gradient inner solve."""
+        return self.model().sysid_rollout_jvp(state_traj, inputs, auxvar_value, d_theta=d_auxvar, d_x0=d_ini_state, d_u=d_inputs)
+
     def getAuxSys(self, state_traj, control_traj, auxvar_value):                # PDP.py:1225-1239
         F, E = self.model().sysid_auxsys(np.asarray(state_traj, float)[None], np.asarray(control_traj, float).reshape(1, -1, self.n_control),
                                          _vec(auxvar_value))

@@ -130,6 +130,10 @@ ENTRY_POINTS = {
         "pdp_oc_pdp_grad_wls_batched": (_I, [_I, _I, _I, _V, _V, _V, _I, _V, _V, _V, _L, _V, _L, _D, _V, _V, _V, _V, _V, _V, _L, _V])}),),
     "pdp_hip_sysid_gn.h": (("model", {"pdp_sysid_step_gn_batched": (_I, [_I, _I, _V, _V, _V, _V, _I, _I, _V, _V, _V, _L, _V])}),),
     "pdp_hip_sysid_ini.h": (("model", {"pdp_sysid_step_gn_ini_batched": (_I, [_I, _I, _V, _V, _V, _I, _V, _I, _I, _V, _V, _V, _L, _V])}),),
+    "pdp_hip_sysid_jvp.h": (("model", {
+        "pdp_sysid_rollout_jvp_batched": (_I, [_I, _I, _V, _V, _V, _I, _V, _I, _V, _V, _V, _V]),
+        "pdp_sysid_rollout_jvp_rows": (_I, [_I]),
+    }),),
     "pdp_hip_sysid_vjp.h": (("model", {"pdp_sysid_rollout_vjp_batched": (_I, [_I, _I, _V, _V, _V, _I, _V, _V, _V, _V])}),),
     "pdp_hip_sysid_vjp_u.h": (("model", {
         "pdp_sysid_rollout_vjp_u_batched": (_I, [_I, _I, _V, _V, _V, _I, _V, _V, _V, _V, _V]),

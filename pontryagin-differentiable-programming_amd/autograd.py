@@ -23,6 +23,10 @@ measurement h(x), a regulariser on the rollout, a learned term - trains the mode
     loss = ((state[:, -1] - goal) ** 2).sum() + 0.01 * (inputs ** 2).sum()
     loss.backward()                                                      # inputs.grad (and theta.grad, ini_state.grad where they require one)
 
+Forward mode works through sysid_trajectory as well: with torch.autograd.forward_ad dual tensors for theta, ini_state and (with input_grad=True) inputs, the tangent
+of the rollout is one launch of the tangent sweep d_x[t+1] = F_t d_x[t] + E_t d_theta + G_t d_u[t] (SysID.rollout_jvp_batch, include/pdp_hip_sysid_jvp.h).
+torch.func transforms are out of scope.
+
 Forward: SysID.integrateDyn_batch.  Backward: the adjoint sweep lam_t = dL/dx_t + F_t' lam_{t+1}, dL/dtheta += E_t' lam_{t+1}, dL/dx_0 = lam_0 - and, with input_grad,
 dL/du_t = G_t' lam_{t+1} - in one launch (SysID.rollout_vjp_batch, include/pdp_hip_sysid_vjp.h, include/pdp_hip_sysid_vjp_u.h).
 
@@ -97,18 +101,30 @@ class _SysIDTrajectory(torch.autograd.Function):
         ctx.sid, ctx.shared, ctx.want_ini = sid, theta.dim() == 1, bool(need[1])
         ctx.want_theta, ctx.want_inputs = (bool(need[0]), bool(need[2])) if input_grad else (True, False)
         ctx.save_for_backward(x, inputs.detach(), theta.detach())
+        ctx.save_for_forward(x, inputs.detach(), theta.detach())        # (what jvp reads: forward-mode differentiation)
+        ctx.input_grad = bool(input_grad)
+        ctx.set_materialize_grads(False)     # (jvp: an input without a tangent arrives as None, not as a tensor of zeros - a theta-only tangent does not pay for df/du)
         return x.clone()                     # (the saved rollout stays as the kernel wrote it whatever the caller does to the output)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_state):
         x, inputs, theta = ctx.saved_tensors
-        g = grad_state.to(torch.float64).contiguous()
+        g = (torch.zeros_like(x) if grad_state is None else grad_state).to(torch.float64).contiguous()
         out = ctx.sid.rollout_vjp_batch(x, inputs, theta, g, want_ini=ctx.want_ini, want_theta=ctx.want_theta, want_inputs=ctx.want_inputs)
         gt = out.get("grad_theta")
         if gt is not None and ctx.shared:
             gt = gt.sum(dim=0)
         return gt, out.get("grad_x0"), out.get("grad_u"), None, None
+
+    @staticmethod
+    def jvp(ctx, d_theta, d_ini_state, d_inputs, _sid, _input_grad):
+        """forward mode (torch.autograd.forward_ad): the tangent of the rollout along the tangents of theta ([p] or [B, p]), ini_state and - with input_grad - inputs,
+        None where an input carries none: one launch of the tangent sweep"""
+        x, inputs, theta = ctx.saved_tensors
+        if d_inputs is not None and not ctx.input_grad:
+            raise NotImplementedError("sysid_trajectory: the tangent with respect to the inputs (through df/du) is computed on request only - pass input_grad=True")
+        return ctx.sid.rollout_jvp_batch(x, inputs, theta, d_auxvar=d_theta, d_ini_state=d_ini_state, d_inputs=d_inputs)
 
 
 def sysid_trajectory(sid, ini_state, inputs, theta, input_grad=False):

@@ -10,6 +10,7 @@
 #include "../../include/pdp_hip_oc_wls.h"
 #include "../../include/pdp_hip_sysid_vjp.h"
 #include "../../include/pdp_hip_sysid_vjp_u.h"
+#include "../../include/pdp_hip_sysid_jvp.h"
 #ifndef PDP_MODEL_HEADER
 #error "compile with -DPDP_MODEL_HEADER=\"generated/<model>.h\""
 #endif
@@ -29,6 +30,7 @@ namespace pdp { extern __device__ long long g_rb_stamp[16]; }
 #include "pdp_sysid_step_kernels.h"
 #include "pdp_cp_generic_kernels.h"
 #include "pdp_sysid_vjp_kernels.h"
+#include "pdp_sysid_jvp_kernels.h"
 #include "pdp_launch.h"
 
 using namespace pdp;
@@ -697,6 +699,36 @@ int sysid_rollout_vjp_u_rows(int B) {
     }
 }
 
+// The rollout's Jacobian-vector product (pdp_sysid_rollout_jvp_batched, include/pdp_hip_sysid_jvp.h): one launch of sysid_jvp_kernel on the given trajectory, the
+// instantiation with `pathu` when d_u is given.  The pool row and the row rule are sysid_vjp_kernel's; the limits are those of the vjp pair.
+template <class Mdl>
+int sysid_rollout_jvp(int B, int T, const double* x, const double* u, const double* th, int tb, const double* dth, int dtb, const double* dx0, const double* du,
+                      double* dx, void* st) {
+    if (B <= 0 || T <= 0 || !x || !u || !th || !dx || (!dth && !dx0 && !du) || (tb != 0 && tb < Mdl::NP) || (dtb != 0 && dtb < Mdl::NP)) return PDP_E_ARG;
+    if constexpr (Mdl::KIND != PDP_KIND_SYSID) return PDP_E_MODE;
+    else if constexpr (Mdl::NX > 64 || Mdl::NP > 512) return PDP_E_SIZE;
+    else {
+        const int rows = sysid_vjp_rows<Mdl>(B, device_cu_count());
+        const size_t lds = sizeof(double) * (size_t)sysid_vjp_slice<Mdl>(rows);
+        if (lds > 150 * 1024) return PDP_E_SIZE;
+        return with_bool(du != nullptr, [&](auto WU) {
+            if constexpr (WU() && Mdl::NP + Mdl::NU > 512) return (int)PDP_E_SIZE;
+            else return launch(sysid_jvp_kernel<Mdl, WU()>, dim3(B), dim3(64), lds, S(st), B, T, x, u, th, tb, dth, dtb, dx0, du, dx, rows);
+        });
+    }
+}
+// pool rows of the launch above (pdp_sysid_rollout_jvp_rows)
+template <class Mdl>
+int sysid_rollout_jvp_rows(int B) {
+    if (B <= 0) return PDP_E_ARG;
+    if constexpr (Mdl::KIND != PDP_KIND_SYSID) return PDP_E_MODE;
+    else if constexpr (Mdl::NX > 64 || Mdl::NP > 512) return PDP_E_SIZE;
+    else {
+        const int rows = sysid_vjp_rows<Mdl>(B, device_cu_count());
+        return sizeof(double) * (size_t)sysid_vjp_slice<Mdl>(rows) > 150 * 1024 ? PDP_E_SIZE : rows;
+    }
+}
+
 template <class Mdl> int nnz_path() { return Mdl::PATH_NVAR; }
 
 // what the Gauss-Newton entry points of SysID.step check first: sizes, the pointers every one of them needs, no flag but PDP_GRAD_SKIP_MISSING
@@ -842,6 +874,11 @@ int pdp_sysid_rollout_vjp_u_batched(int B, int T, const double* x, const double*
     return sysid_rollout_vjp_u<PdpModel>(B, T, x, u, theta, tb, grad_x, grad_theta, grad_x0, grad_u, stream);
 }
 int pdp_sysid_rollout_vjp_u_rows(int B) { return sysid_rollout_vjp_u_rows<PdpModel>(B); }
+int pdp_sysid_rollout_jvp_batched(int B, int T, const double* x, const double* u, const double* theta, int tb, const double* d_theta, int d_theta_bstride,
+                                  const double* d_x0, const double* d_u, double* d_x, void* stream) {
+    return sysid_rollout_jvp<PdpModel>(B, T, x, u, theta, tb, d_theta, d_theta_bstride, d_x0, d_u, d_x, stream);
+}
+int pdp_sysid_rollout_jvp_rows(int B) { return sysid_rollout_jvp_rows<PdpModel>(B); }
 int pdp_oc_pdp_grad_wls_batched(int B, int T, int flags, const double* x0, const double* u, const double* theta, int theta_bstride, const double* demo_x,
                                 const double* demo_u, const double* weights_x, int64_t weights_x_bstride, const double* weights_u, int64_t weights_u_bstride,
                                 double huber_delta, double* x, double* lam, double* loss, double* packed, int32_t* status, void* workspace, int64_t workspace_bytes,

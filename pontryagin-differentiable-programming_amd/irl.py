@@ -859,3 +859,159 @@ class BatchedLMLoop:
                 sols["accepted"] = tuple(torch.where(now, t, a) for t, a in zip(sols["trial"], sols["accepted"]))
         loop.after_update = keep_accepted
         return loop
+
+
+class MatrixFreeLM:
+    """Levenberg-Marquardt for ONE shared parameter theta [p] (p <= 512) of a PDP.SysID `sid`, on ANY residual of its rollouts written in torch, without ever forming
+    the Gauss-Newton matrix: the models LMLoop.for_sysid has no route for - wide ones (the fused Gauss-Newton row is p <= 16) and any measurement function h(x).
+    residual(state [B, T+1, n]) -> r (a tensor of any shape) is a pure torch function; its own J_h v / J_h' w come from torch.func.jvp / vjp.  One evaluation is a
+    rollout (SysID.integrateDyn_batch from ini_state [B, n] under inputs [B, T, m]) plus r, with loss = sum r^2 / B.  A Gauss-Newton product G v = J' J v / B is
+    rollout_jvp_batch -> J_h -> J_h' -> rollout_vjp_batch summed over the batch: two launches of the model library whatever p is.  The step solves
+    (G + lam I) s = J' r / B by conjugate gradients, written in torch on the device, from s = 0 to a relative residual of cg_tol or cg_max iterations (None: 2 p).
+    Plain lam I damping: matrix-free there is no diag G, so Marquardt's scaling (lm_step's lam diag G) is not available - scale the parameters where their
+    magnitudes differ by orders.  The accept / reject / lam schedule and the keys of run() are LMLoop's, and `cg_iterations` (all inner iterations so far).
+    Out of scope: per-recording initial states, priors, covariance, process groups, Huber."""
+
+    def __init__(self, sid, ini_state, inputs, theta0, residual, lam0=1e-3, up=10.0, down=10.0, lam_min=1e-12, lam_max=1e8, cg_tol=1e-8, cg_max=None):
+        shape = lambda a: tuple(int(k) for k in (a.shape if hasattr(a, "shape") else np.shape(a)))
+        p, su = int(sid.n_auxvar), shape(inputs)
+        if len(su) != 3 or su[2] != sid.n_control or su[0] < 1 or su[1] < 1:
+            raise ValueError("MatrixFreeLM: inputs must be [B, T, m] with m = %d and B, T >= 1, got %s" % (sid.n_control, su))
+        if shape(ini_state) != (su[0], sid.n_state):
+            raise ValueError("MatrixFreeLM: ini_state must be [B, n] = %s, got %s" % ((su[0], sid.n_state), shape(ini_state)))
+        if int(np.prod(shape(theta0))) != p:
+            raise ValueError("MatrixFreeLM: theta0 must be [p] with p = %d (one parameter shared by the batch), got %s" % (p, shape(theta0)))
+        if p > 512:
+            raise ValueError("MatrixFreeLM: p = %d is beyond the rollout's jvp / vjp kernels (p <= 512)" % p)
+        if not callable(residual):
+            raise ValueError("MatrixFreeLM: residual must be a function of the rollouts [B, T+1, n]")
+        self.sid, self.residual, self.B, self.p = sid, residual, su[0], p
+        self.x0, self.u = rt.dev(ini_state), rt.dev(inputs)
+        self.theta = rt.dev(theta0).reshape(p).clone()
+        self.lam, self.up, self.down, self.lam_min, self.lam_max = float(lam0), float(up), float(down), float(lam_min), float(lam_max)
+        self.cg_tol, self.cg_max = float(cg_tol), int(2 * p if cg_max is None else cg_max)
+        self.current = None                     # (loss, g = J'r / B, the rollout, residual's vjp at it) at self.theta
+        self.evaluations = self.rejected = self.cg_iterations = 0
+        self.stalled = False
+        self.loss_trace, self.parameter_trace, self.lambda_trace = [], [], []
+
+    def _eval(self, theta):
+        """(loss, g, x, vjp of the residual at x), or None where the loss is not finite"""
+        import torch
+        self.evaluations += 1
+        with torch.no_grad():
+            x = self.sid.integrateDyn_batch(self.x0, self.u, theta)
+        r, back = torch.func.vjp(self.residual, x)
+        loss = float((r.detach() ** 2).sum()) / self.B
+        if not np.isfinite(loss):
+            return None
+        g = self._jt(x, theta, back(r.detach())[0])
+        return loss, g, x, back
+
+    def _jt(self, x, theta, w):
+        """J' of the rollout on a cotangent of the states, summed over the batch, / B"""
+        return self.sid.rollout_vjp_batch(x, self.u, theta, w.detach().contiguous(), want_ini=False)["grad_theta"].sum(dim=0) / self.B
+
+    def gauss_newton_product(self, v):
+        """G v = J' J v / B at the accepted point, v [p] on the device: rollout_jvp -> J_h -> J_h' -> rollout_vjp"""
+        import torch
+        if self.current is None:
+            self.start()
+        _, _, x, back = self.current
+        dx = self.sid.rollout_jvp_batch(x, self.u, self.theta, d_auxvar=v)
+        jv = torch.func.jvp(self.residual, (x,), (dx,))[1]
+        return self._jt(x, self.theta, back(jv.detach())[0])
+
+    def _cg(self, g):
+        """(G + lam I) s = g by conjugate gradients from s = 0"""
+        s, r = g.new_zeros(g.shape), g.clone()
+        d, rr = r.clone(), float(r @ r)
+        stop = (self.cg_tol ** 2) * rr
+        for _ in range(self.cg_max):
+            if not rr > stop:
+                break
+            q = self.gauss_newton_product(d) + self.lam * d
+            dq = float(d @ q)
+            self.cg_iterations += 1
+            if not dq > 0.0:                    # (a non-finite product, or no curvature left in fp64)
+                break
+            a = rr / dq
+            s, r = s + a * d, r - a * q
+            rr_new = float(r @ r)
+            d, rr = r + (rr_new / rr) * d, rr_new
+        return s
+
+    def start(self):
+        """the evaluation at theta0 (the first accepted point)"""
+        r = self._eval(self.theta)
+        if r is None:
+            raise RuntimeError("MatrixFreeLM: the initial parameter could not be evaluated")
+        self.current = r
+        self._record()
+
+    def _record(self):
+        self.loss_trace.append(self.current[0])
+        self.parameter_trace.append(self.theta.detach().cpu().numpy().copy())
+        self.lambda_trace.append(self.lam)
+
+    def step(self):
+        """one trial: True if it was accepted"""
+        import torch
+        loss, g = self.current[:2]
+        trial = self.theta - self._cg(g)
+        if bool(torch.isfinite(trial).all()):
+            r = self._eval(trial)
+        else:
+            r, self.evaluations = None, self.evaluations + 1        # (a trial that cannot be formed still counts against the budget)
+        if r is not None and r[0] < loss:
+            self.theta, self.current = trial, r
+            self.lam = max(self.lam / self.down, self.lam_min)
+            self._record()
+            return True
+        self.rejected += 1
+        self.lam *= self.up
+        return False
+
+    def run(self, max_evals=50, loss_tol=0.0):
+        if self.current is None:
+            self.start()
+        while self.evaluations < max_evals and self.current[0] > loss_tol:
+            if self.lam > self.lam_max:
+                self.stalled = True
+                break
+            self.step()
+        return self.results()
+
+    def results(self):
+        """LMLoop.results()'s fields over the ACCEPTED points, and cg_iterations"""
+        return {"loss_trace": np.array(self.loss_trace), "parameter_trace": np.array(self.parameter_trace).reshape(len(self.parameter_trace), self.p),
+                "lambda_trace": np.array(self.lambda_trace), "evaluations": self.evaluations, "rejected": self.rejected, "stalled": self.stalled,
+                "iterations": len(self.loss_trace), "cg_iterations": self.cg_iterations}
+
+    @classmethod
+    def for_sysid(cls, sid, inputs, states, theta0, ini_state=None, weights=None, skip_missing=False, **kw):
+        """The recorded-state residual of the SysID drivers: r = sqrt(weights) (state - states) over inputs [B, T, m] and recorded states [B, T+1, n], rolled out from
+        ini_state [B, n] (None: states[:, 0]).  weights ([n], [T+1, n] or [B, T+1, n], >= 0, 0 = not observed) and, with skip_missing, the NaN entries of `states` (not
+        observed) are applied elementwise in torch.  With skip_missing a NaN in the initial state that would be used is a ValueError before any launch."""
+        import torch
+        shape = lambda a: tuple(int(k) for k in (a.shape if hasattr(a, "shape") else np.shape(a)))
+        su = shape(inputs)
+        if len(su) != 3 or shape(states) != (su[0], su[1] + 1, sid.n_state):
+            raise ValueError("MatrixFreeLM.for_sysid: inputs must be [B, T, m] and states [B, T+1, n] with n = %d, got %s and %s" % (sid.n_state, su, shape(states)))
+        if skip_missing:
+            rt.refuse_nan_initial_state("MatrixFreeLM.for_sysid", states, ini_state, "states")
+        xobs = rt.dev(states)
+        scale = torch.ones_like(xobs)
+        if weights is not None:
+            w = rt.dev(weights)
+            if tuple(w.shape) not in ((sid.n_state,), tuple(xobs.shape[1:]), tuple(xobs.shape)) or bool((w < 0).any()) or not bool(torch.isfinite(w).all()):
+                raise ValueError("MatrixFreeLM.for_sysid: weights must be [n], [T+1, n] or [B, T+1, n], finite and >= 0, got %s" % (tuple(w.shape),))
+            scale = scale * torch.sqrt(w)
+        missing = torch.isnan(xobs)
+        if bool(missing.any()):
+            if not skip_missing:
+                raise ValueError("MatrixFreeLM.for_sysid: `states` holds a NaN - pass skip_missing=True to treat NaN entries as not observed")
+            scale = torch.where(missing, torch.zeros_like(scale), scale)
+        x0 = (xobs[:, 0] if ini_state is None else rt.dev(ini_state)).contiguous().clone()
+        target = torch.where(missing, torch.zeros_like(xobs), xobs)
+        return cls(sid, x0, inputs, theta0, lambda state: (state - target) * scale, **kw)

@@ -1157,6 +1157,47 @@ class ModelLib:
         fit = 2400 // ((self.nnz_path + self.n) | 1)
         return min(fit, self.chunk) if fit >= 4 else self.chunk
 
+    def sysid_rollout_jvp(self, x, u, theta, d_theta=None, d_x0=None, d_u=None):
+        """The rollout as a Jacobian-vector product (pdp_sysid_rollout_jvp_batched, include/pdp_hip_sysid_jvp.h: the semantics): x [B, T+1, n] the rollout of
+        sysid_integrate for u [B, T, m] and theta ([p] or [B, p]); the direction d_theta ([p]: shared by the batch, or [B, p]), d_x0 [B, n], d_u [B, T, m], each None
+        for zero, not all of them -> d_x [B, T+1, n], the tangent of the rollout along it: d_x[t+1] = F_t d_x[t] + E_t d_theta + G_t d_u[t], one launch of the tangent
+        sweep.  Without d_u the kernel does not evaluate G = df/du.  Shape errors are ValueErrors before any launch."""
+        shape = lambda a: tuple(int(k) for k in (a.shape if hasattr(a, "shape") else np.shape(a)))
+        su = shape(u)
+        if len(su) != 3 or su[2] != self.m or su[0] < 1 or su[1] < 1:
+            raise ValueError("sysid_rollout_jvp: inputs must be [B, T, %d] with B, T >= 1, got %s" % (self.m, su))
+        B, T = su[0], su[1]
+        if shape(x) != (B, T + 1, self.n):
+            raise ValueError("sysid_rollout_jvp: state_traj must be [B, T+1, n] = %s, got %s" % ((B, T + 1, self.n), shape(x)))
+        if shape(theta) not in ((self.p,), (1, self.p), (B, self.p)):
+            raise ValueError("sysid_rollout_jvp: theta must be [p] or [B, p] with p = %d, B = %d, got %s" % (self.p, B, shape(theta)))
+        if d_theta is None and d_x0 is None and d_u is None:
+            raise ValueError("sysid_rollout_jvp: d_theta, d_x0 and d_u are all None - nothing to compute")
+        if d_theta is not None and shape(d_theta) not in ((self.p,), (1, self.p), (B, self.p)):
+            raise ValueError("sysid_rollout_jvp: d_theta must be [p] or [B, p] with p = %d, B = %d, got %s" % (self.p, B, shape(d_theta)))
+        if d_x0 is not None and shape(d_x0) != (B, self.n):
+            raise ValueError("sysid_rollout_jvp: d_x0 must be [B, n] = %s, got %s" % ((B, self.n), shape(d_x0)))
+        if d_u is not None and shape(d_u) != su:
+            raise ValueError("sysid_rollout_jvp: d_u must be [B, T, m] = %s, got %s" % (su, shape(d_u)))
+        torch = torch_cuda()
+        x, u, th = dev(x), dev(u), dev(theta)
+        dth, dx0, du = (None if a is None else dev(a) for a in (d_theta, d_x0, d_u))
+        tb = self.p if (th.dim() == 2 and th.shape[0] == B and B > 1) else 0
+        dtb = self.p if (dth is not None and dth.dim() == 2 and dth.shape[0] == B and B > 1) else 0
+        d_x = torch.empty((B, T + 1, self.n), dtype=torch.float64, device="cuda")                # (every row is written exactly once: no need to clear it)
+        opt = lambda t: None if t is None else ptr(t)
+        check(self.lib.pdp_sysid_rollout_jvp_batched(B, T, ptr(x), ptr(u), ptr(th), tb, opt(dth), dtb, opt(dx0), opt(du), ptr(d_x), current_stream_ptr()),
+              "pdp_sysid_rollout_jvp_batched")
+        return d_x
+
+    def sysid_jvp_rows(self, B):
+        """pool rows (time steps per Jacobian pass) of sysid_rollout_jvp's kernel for a batch of B on this device, as the library itself decides them
+        (pdp_sysid_rollout_jvp_rows): sysid_vjp_rows' rule on the same row, with or without d_u - the chunk edges the tests aim at"""
+        rows = int(self.lib.pdp_sysid_rollout_jvp_rows(int(B)))
+        if rows <= 0:
+            raise RuntimeError("pdp_sysid_rollout_jvp_rows failed: %s" % PDP_E.get(rows, rows))
+        return rows
+
     def _sysid_workspace(self, B, T):
         """(workspace tensor or None, its bytes) of the fused SysID.step entry points"""
         torch = torch_cuda()
