@@ -318,7 +318,8 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
 #ifdef PDP_PHASE_TIMING_FINE
                     if (blockIdx.x == 0 && threadIdx.x == 0) g_rb_stamp[9] = __builtin_readcyclecounter();
 #endif
-                    d4 Hxx = row_read(rHxx, imm), HX2 = row_read(rHX, imm), HU2 = row_read<1>(rHU, imm), Grep = row_read(rGr, imm), Hux = row_read<1>(rHux, imm);
+                    __builtin_amdgcn_sched_barrier(0);            // the step's requests open a scheduling region of their own: riccati_backward<.., SCHED> places them
+                    d4 HU2 = row_read<1>(rHU, imm), Grep = row_read(rGr, imm), Hux = row_read<1>(rHux, imm), Hxx = row_read(rHxx, imm), HX2 = row_read(rHX, imm);      // (in the order the step needs them)
                     if (tl > 0) { Fn = row_read(rF, imm - RB); Yn = row_read(rY, imm - RB); }
                     RiccatiGains gn;
                     d4 P_old;
@@ -326,7 +327,7 @@ __global__ void __launch_bounds__(128 * TPW) oc_pdp_fused3_kernel(int B, int T, 
                         if (riccati) { buf_store(rsR, (unsigned)(t * RSZ) * 8u, mRP, P); buf_store(rsR, (unsigned)(t * RSZ + NX * NX) * 8u, mRW, W2); }
                         if (precPW) { pred_store(rsPR, (unsigned)(t * PredRec<Mdl>::SIZE) * 4u, pm.P, P); pred_store(rsPR, (unsigned)(t * PredRec<Mdl>::SIZE) * 4u, pm.W, W2); }
                     }
-                    ok = riccati_backward<M, false>(P, W2, Fc, Yc, Grep, Hxx, HX2, HU2, Hux[0], scratch, lane, NP, gn, P_old) && ok;
+                    ok = riccati_backward<M, false, false, false, true>(P, W2, Fc, Yc, Grep, Hxx, HX2, HU2, Hux[0], scratch, lane, NP, gn, P_old) && ok;
                     store_all<1>(gw + t * GSZ, mK, gn.K);
                     store_all<1>(gw + t * GSZ + NX * NU, mIK, gn.IK);
 #ifdef PDP_PHASE_TIMING_FINE

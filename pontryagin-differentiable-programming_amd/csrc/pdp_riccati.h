@@ -77,9 +77,116 @@ PDP_DEV bool posdef_small(const double* a) {
 #ifndef PDP_RB_T
 #define PDP_RB_T(i)      // timing builds (probes/phase_timing3.py) define it to take a cycle stamp
 #endif
-template <int M, bool WANT_KT = true, bool HUX_FROM_HX2 = false, bool WANT_PD = false>
+// The same step with its instruction order fixed by hand (M = 4, no K^T; the runner of oc_pdp_fused3_kernel): the same MFMAs and the same VALU operations on the
+// same values as riccati_backward below - every result keeps every bit - issued so that the matrix pipe works where the wave would otherwise wait:
+//   - only PY2 -> Q2 feeds the 4 x 4 solve: they go first, Quu goes to LDS and the nine minor reads follow it at once (wave_lds_order: the wave does not wait for
+//     its own write); PF (4 x 64 cycles) runs under that round trip;
+//   - the reciprocal of the determinant and its Newton step are issued AHEAD of the guard's branch, Qux (4 four-row MFMAs) behind the v_rcp_f64; the pivoted
+//     fallback drops the value and is itself unchanged;
+//   - P- goes to LDS and its transposed reads follow at once; FY (4 x 64 cycles, needed by Wn alone) and Wn run under that round trip.
+// Source order is not enough - the machine scheduler moves MFMAs freely inside a basic block - so the groups are separated by __builtin_amdgcn_sched_barrier(0).
+// No cycle stamps inside (PDP_RB_T): their branches would end the scheduling regions.
+PDP_DEV bool riccati_backward_sched4(d4& P, d4& W0, const d4 Ft, const d4 Y2, const d4 Grep, const d4 Hxx, const d4 HX2, const d4 HU2, const double Hux0,
+                                     double* scratch, int lane, int p0, RiccatiGains& g, d4& P_old_out) {
+    const d4 z = zero4();
+    const int row = lane >> 4, col = lane & 15;
+    P_old_out = P;
+    d4 PY2 = mma_tn(P, Y2, W0);           // [P G | P E + W]
+    // the step's operand reads (the caller has just asked for them, what Q2 needs first) go out between these four MFMAs, not behind them
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    d4 PF = __builtin_amdgcn_mfma_f64_16x16x4f64(P[0], Ft[0], z, 0, 0, 0);      // P F, first of four: while PY2 leaves the pipe (Q2 reads it as an operand)
+    __builtin_amdgcn_sched_barrier(0);
+    d4 Q2 = z;
+    Q2[0] = mma4_tn(Grep, PY2, HU2[0]);   // [Quu | Que]
+    __builtin_amdgcn_sched_barrier(0);
+    PF = __builtin_amdgcn_mfma_f64_16x16x4f64(P[1], Ft[1], PF, 0, 0, 0);        // second: while Quu leaves the pipe
+    __builtin_amdgcn_sched_barrier(0);
+    scratch[544 + lane] = Q2[0];
+    wave_lds_order();
+    const int i = row, j = col & 3;
+    const int r0 = (i == 0) ? 1 : 0, r1 = (i <= 1) ? 2 : 1, r2 = (i <= 2) ? 3 : 2;
+    const int c0 = (j == 0) ? 1 : 0, c1 = (j <= 1) ? 2 : 1, c2 = (j <= 2) ? 3 : 2;
+    const double* q = scratch + 544;
+    const double m00 = q[r0 * 16 + c0], m01 = q[r0 * 16 + c1], m02 = q[r0 * 16 + c2];
+    const double m10 = q[r1 * 16 + c0], m11 = q[r1 * 16 + c1], m12 = q[r1 * 16 + c2];
+    const double m20 = q[r2 * 16 + c0], m21 = q[r2 * 16 + c1], m22 = q[r2 * 16 + c2];
+    __builtin_amdgcn_sched_barrier(0);
+    PF = __builtin_amdgcn_mfma_f64_16x16x4f64(P[2], Ft[2], PF, 0, 0, 0);        // the rest of P F: under the Quu round trip
+    PF = __builtin_amdgcn_mfma_f64_16x16x4f64(P[3], Ft[3], PF, 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    double cof = m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20);
+    cof = ((i + j) & 1) ? -cof : cof;
+    const double ac = Q2[0] * cof;
+    const double t0 = readlane_f64(ac, 0), t1 = readlane_f64(ac, 1), t2 = readlane_f64(ac, 2), t3 = readlane_f64(ac, 3);
+    const double det = (t0 + t1) + (t2 + t3), mag = (fabs(t0) + fabs(t1)) + (fabs(t2) + fabs(t3));
+    double rdet = __builtin_amdgcn_rcp(det);
+    __builtin_amdgcn_sched_barrier(0);
+    d4 Qux = z;
+    Qux[0] = mma4_tn(Grep, PF, Hux0);     // Qux = Hux + G'PF: under the reciprocal
+    __builtin_amdgcn_sched_barrier(0);
+    rdet = fma(fma(-det, rdet, 1.0), rdet, rdet);
+    asm volatile("" : "+v"(rdet));        // stays in front of the branch (used on one side only, it would be sunk into it)
+    d4 Pn = mma_tn(Ft, PF, Hxx);          // Hxx + F'PF
+    double Zrep = cof * rdet;
+    bool ok = true;
+    if (__builtin_expect(!(fabs(det) > COFACTOR4_GUARD * mag && fabs(det) <= 1.7e308), 0)) {      // uniform branch, off the straight line
+        // ill-conditioned / singular: pivoted Gauss-Jordan, uniform over the wave (the product above is dropped)
+        double a[16], ai[16];
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) a[ii * 4 + jj] = readlane_f64(Q2[0], 16 * ii + jj);
+        ok = inverse_small<4>(a, ai);
+        double zz = 0.0;
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) zz = (row == ii && (col & 3) == jj) ? ai[jj * 4 + ii] : zz;
+        Zrep = zz;
+    }
+    d4 Z = z;
+    Z[0] = (col < 4) ? Zrep : 0.0;
+    d4 K = z;
+    K[0] = mma4_blk(Zrep, Qux[0], 0.0);   // Quu^-1 Qux
+    g.IK = z;
+    g.IK[0] = mma4_blk(Zrep, Q2[0], 0.0); // [I | k]
+    g.K = K;
+    g.Z = Z;
+    g.Zrep = Zrep;
+    g.Qux = Qux;
+    P = mms_tn_r0(Qux, K, Pn);            // Hxx + F'PF - Qux'K
+    __builtin_amdgcn_sched_barrier(0);
+    d4 FY = __builtin_amdgcn_mfma_f64_16x16x4f64(Ft[0], PY2[0], HX2, 0, 0, 0);  // [Qux' | Wn], first of four: while P- leaves the pipe
+    __builtin_amdgcn_sched_barrier(0);
+    tile_to_lds17(scratch + 272, P, lane);
+    wave_lds_order();
+    const d4 Pt = tile_from_lds17_transposed(scratch + 272, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    FY = __builtin_amdgcn_mfma_f64_16x16x4f64(Ft[1], PY2[1], FY, 0, 0, 0);      // the rest: under the transposition's round trip
+    FY = __builtin_amdgcn_mfma_f64_16x16x4f64(Ft[2], PY2[2], FY, 0, 0, 0);
+    FY = __builtin_amdgcn_mfma_f64_16x16x4f64(Ft[3], PY2[3], FY, 0, 0, 0);
+    d4 Wn = mms_tn_r0(Qux, g.IK, FY);
+    __builtin_amdgcn_sched_barrier(0);
+    P = 0.5 * (P + Pt);                   // (VALU that does not read Wn: while Wn leaves the pipe)
+    __builtin_amdgcn_sched_barrier(0);
+    W0 = keep_cols(Wn, 4, 4 + p0, lane);
+    g.IK = keep_cols(g.IK, 4, 4 + p0, lane);
+    return ok;
+}
+
+// SCHED: the hand-scheduled form above where it exists (M = 4, plain options); everything else about the step is the same
+template <int M, bool WANT_KT = true, bool HUX_FROM_HX2 = false, bool WANT_PD = false, bool SCHED = false>
 PDP_DEV bool riccati_backward(d4& P, d4& W0, const d4 Ft, const d4 Y2, const d4 Grep, const d4 Hxx, const d4 HX2, const d4 HU2, double Hux0,
                               double* scratch, int lane, int p0, RiccatiGains& g, d4& P_old_out) {
+    if constexpr (SCHED && M == 4 && !WANT_KT && !HUX_FROM_HX2 && !WANT_PD)
+        return riccati_backward_sched4(P, W0, Ft, Y2, Grep, Hxx, HX2, HU2, Hux0, scratch, lane, p0, g, P_old_out);
     const d4 z = zero4();
     if constexpr (HUX_FROM_HX2) tile_to_lds17(scratch, HX2, lane);
     PDP_RB_T(0);

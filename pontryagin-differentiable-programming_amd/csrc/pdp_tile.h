@@ -193,6 +193,10 @@ PDP_DEV bool tile_finite(const d4 v) {
 // needed is (a) the compiler must not reorder the accesses (it reasons per thread) and (b) outstanding DS results are
 // waited for.  No s_barrier, and - unlike __syncthreads() - no vmcnt(0): pending global stores keep draining.
 PDP_DEV void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// Half (a) alone, for a round trip in which the SAME wave is writer and reader and no other wave touches the words: the in-order LDS unit already serves the
+// ds_read after the ds_write, so the wave need not wait for its own write - the compiler places the wait for the read where the data is first used, and whatever
+// is issued in between runs under the round trip.  Wherever another wave writes or reads the words, wave_lds_sync() (after the hand-over counter) stays.
+PDP_DEV void wave_lds_order() { asm volatile("" ::: "memory"); }
 
 // tanh for the policy networks (PDP.py:733-751): sign(x) (1 - 2 / (exp(2 |x|) + 1)), the reciprocal by v_rcp_f64 + two Newton steps.  ABSOLUTE error <= 2e-16 (the
 // subtraction from 1 loses relative accuracy for |x| << 1, where the value itself is that small) - far inside the 1e-10 parity tolerance, and what the activations, their
