@@ -336,12 +336,22 @@ int64_t pdp_oc_riccati_doubles(void);
 /* Optional outputs of pdp_oc_pdp_grad_sens_batched; any pointer may be NULL.  predict_record [B][T][pdp_oc_predict_record_floats()]: what the prediction of the
  * next starting point needs, packed and in single precision per stage - X_{t+1} [n][p] | U_t [m][p] | upper triangle of P_{t+1} (row-major packed) | W_{t+1} [n][p]
  * (a starting point is first-order accurate in dtheta at best: fp32 factors are far below that error, and the record stays in the Infinity Cache where the fp64
- * outputs are read at HBM speed). */
+ * outputs are read at HBM speed).
+ * grad_x0 [B][n] (NULL = not computed): the gradient with respect to the INITIAL STATE through the solution, by an adjoint sweep that is launched on the same stream
+ * behind the unit (mu_T = g_T; v_t = gu_t + G_t' mu_{t+1}, mu_t = gx_t + F_t' mu_{t+1} - K_t' v_t with the unit's own Riccati gains K_t; grad_x0 = mu_0).  With
+ * PDP_OC_COTANGENT: grad_x0[b] = dL/dx_0 of the caller's loss, gx[b][0] included - the sweep reads it, the theta gradient still does not - and this field is the one
+ * the mode allows (the other four stay PDP_E_ARG).  In the default mode, with or without PDP_OC_PACKED and beside the other fields: half the gradient of the
+ * demonstration loss with respect to x_0, the convention of `grad`.  With PDP_OC_GIVEN_TRAJ as without.  With PDP_GRAD_GAUSS_NEWTON or PDP_GRAD_SKIP_MISSING:
+ * PDP_E_ARG before anything is launched.  The unit's launch, its workspace, its limits (PDP_E_SIZE) and every other output are what they are without the field; a
+ * trajectory whose gains are not finite (see status) gets a non-finite row here, and no other row is affected.
+ * The field is the last one: a caller compiled against the four-field struct must be rebuilt (it would hand over an uninitialised pointer), one that initialises
+ * the struct with four values or zeroes it keeps its meaning. */
 typedef struct pdp_oc_sens_out {
     double* dxdp;
     double* dudp;
     double* riccati;
     float* predict_record;
+    double* grad_x0;
 } pdp_oc_sens_out;
 int64_t pdp_oc_predict_record_floats(void);
 int pdp_oc_pdp_grad_sens_batched(int B, int T, int flags, const double* x0, const double* u, const double* theta,

@@ -186,7 +186,7 @@ class OCSys(_CasadiFrontEnd):
 
     def pdp_grad_batch(self, control_traj, auxvar_value, demo_state, demo_control, ini_state=None, state_traj=None, costate_traj=None,
                        want_sens=False, buffers=None, want_riccati=False, want_predict_record=False, want_gauss_newton=False, skip_missing=False, weights_state=None,
-                       weights_control=None, huber_delta=None):
+                       weights_control=None, huber_delta=None, want_ini=False):
         """Fused forward + Riccati + PDP gradient for a batch (the body of the IRL drivers' demo loop,
         Examples/IRL/cartpole/cartpole_PDP.py:45-74): returns dict(loss [B], grad [B,p], x, lam, status[, dxdp, dudp][, riccati]).
         want_predict_record (or want_sens + want_riccati, the same in fp64): everything the next OC solve's predicted start needs
@@ -197,7 +197,12 @@ class OCSys(_CasadiFrontEnd):
         gradient and G (PDP_GRAD_SKIP_MISSING); demo_state[:, 0] may be all NaN when ini_state is given.
         weights_state ([n], [T+1, n] or [B, T+1, n]), weights_control ([m], [T, m] or [B, T, m]), huber_delta (> 0): a weight per demonstration entry (>= 0, 0 = not
         observed, 1 / sigma^2 the usual choice) and Huber's loss on the standardised residual (include/pdp_hip_oc_wls.h).  Any of the three implies the packed
-        Gauss-Newton dict of the weighted / robust loss; not together with want_sens, want_riccati or want_predict_record (ValueError)."""
+        Gauss-Newton dict of the weighted / robust loss; not together with want_sens, want_riccati or want_predict_record (ValueError).
+        want_ini: also out["grad_x0"] [B,n], half the gradient of the loss with respect to the initial state through the solution (the convention of grad; an adjoint
+        sweep behind the same launch, pdp_oc_sens_out.grad_x0).  Not with want_gauss_newton, skip_missing or the weights (ValueError)."""
+        if want_ini and (want_gauss_newton or skip_missing or weights_state is not None or weights_control is not None or huber_delta is not None):
+            raise ValueError("pdp_grad_batch: want_ini goes with the plain gradient and the sensitivity outputs only - not with want_gauss_newton, skip_missing, "
+                             "weights_state, weights_control or huber_delta")
         if weights_state is not None or weights_control is not None or huber_delta is not None:
             for name, on in (("want_sens", want_sens), ("want_riccati", want_riccati), ("want_predict_record", want_predict_record)):
                 if on:
@@ -212,18 +217,22 @@ class OCSys(_CasadiFrontEnd):
         return self.model().oc_pdp_grad(u, self._theta(auxvar_value, u.shape[0]), demo_state, demo_control, x0=ini_state, x=state_traj,
                                         lam=costate_traj, want_sens=want_sens, buffers=buffers, want_riccati=want_riccati, want_predict_record=want_predict_record,
                                         gauss_newton=want_gauss_newton, skip_missing=skip_missing, weights_x=weights_state, weights_u=weights_control,
-                                        huber_delta=huber_delta)
+                                        huber_delta=huber_delta, **(dict(want_ini=True) if want_ini else {}))
 
-    def pdp_vjp_batch(self, control_traj, auxvar_value, grad_state, grad_control, ini_state=None, state_traj=None, costate_traj=None, buffers=None):
+    def pdp_vjp_batch(self, control_traj, auxvar_value, grad_state, grad_control, ini_state=None, state_traj=None, costate_traj=None, buffers=None,
+                      want_ini=False):
         """The gradient of ANY scalar loss L(state, control) through the OC solution, for a batch: grad_state [B,T+1,n] = dL/dstate and grad_control [B,T,m] = dL/dcontrol
         (cotangents, e.g. from torch.autograd.grad) -> dict(grad [B,p] = sum_t dL/dx_t' X_t + dL/du_t' U_t, x, lam, status), the sensitivities X_t, U_t of the auxiliary
         control system (PDP.py:582-608) contracted inside the fused kernel instead of being written out (PDP_OC_COTANGENT, include/pdp_hip.h).  pdp_grad_batch is the special
         case grad_state = x - demo_state, grad_control = u - demo_control (half the gradient of its own loss, Examples/IRL/cartpole/cartpole_PDP.py:63-74).
         grad_state[:, 0] is not read: the initial state does not depend on the parameter.  Trajectory arguments as in pdp_grad_batch; auxvar_value may be a tensor.
+        want_ini: also out["grad_x0"] [B,n] = dL/dx_0 through the solution, from an adjoint sweep behind the same launch (pdp_oc_sens_out.grad_x0); grad_state[:, 0]
+        then enters grad_x0, and nothing else.
         pdp_amd.autograd.oc_trajectory wraps solve + this call as a torch.autograd layer."""
         u = runtime.dev(control_traj)
         th = auxvar_value if hasattr(auxvar_value, "data_ptr") else self._theta(auxvar_value, u.shape[0])
-        return self.model().oc_pdp_vjp(u, th, grad_state, grad_control, x0=ini_state, x=state_traj, lam=costate_traj, buffers=buffers)
+        return self.model().oc_pdp_vjp(u, th, grad_state, grad_control, x0=ini_state, x=state_traj, lam=costate_traj, buffers=buffers,
+                                       **(dict(want_ini=True) if want_ini else {}))
 
     # ---- PDP.py:272-314 ----------------------------------------------------------------------------------------
     def getAuxSys(self, state_traj_opt, control_traj_opt, costate_traj_opt, auxvar_value=1):

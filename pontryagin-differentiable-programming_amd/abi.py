@@ -35,7 +35,7 @@ class PdpOcMsOpts(C.Structure):
 
 
 class PdpOcSensOut(C.Structure):
-    _fields_ = [("dxdp", C.c_void_p), ("dudp", C.c_void_p), ("riccati", C.c_void_p), ("predict_record", C.c_void_p)]
+    _fields_ = [("dxdp", C.c_void_p), ("dudp", C.c_void_p), ("riccati", C.c_void_p), ("predict_record", C.c_void_p), ("grad_x0", C.c_void_p)]
 
 
 class PdpLmSchedule(C.Structure):                  # include/pdp_hip_lm.h

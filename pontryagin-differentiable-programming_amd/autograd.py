@@ -9,7 +9,14 @@
 Forward: OCSys.ocSolver_batch (the reference's OCSys.ocSolver, PDP.py:121-220, for a batch).  Backward: the gradient of a scalar L(x, u) through the solution is
 sum_t (dL/dx_t)' X_t + (dL/du_t)' U_t with X_t = dx_t/dtheta, U_t = du_t/dtheta the solution of the auxiliary control system (PDP.py:582-608) at the optimal
 trajectory - one launch of the fused unit in its cotangent mode (OCSys.pdp_vjp_batch, PDP_OC_COTANGENT in include/pdp_hip.h): the sensitivities are contracted with
-the incoming gradients on the chip and never written out.
+the incoming gradients on the chip and never written out.  With ini_grad=True the layer is differentiable in the initial state as well - the input of an MPC layer,
+what a state estimator or an encoder in front of the controller trains through:
+
+    state, control = oc_trajectory(oc, ini_state, horizon, theta, ini_grad=True)      # ini_state: CUDA fp64 [B, n], requires_grad
+    loss = ((state[:, -1] - goal) ** 2).sum()
+    loss.backward()                                                      # ini_state.grad = dL/dx_0 (and theta.grad where theta requires one)
+
+dL/dx_0 comes from an adjoint sweep with the Riccati gains of the same backward launch (pdp_oc_sens_out.grad_x0 in include/pdp_hip.h).
 
 `sysid_trajectory` is the same for the rollouts of a PDP.SysID: it maps (ini_state, theta) to the states of x_{t+1} = f(x_t, u_t, theta) for given inputs and is
 differentiable in theta and ini_state - and, with input_grad=True, in the inputs - so that a loss that is not "state minus recorded state" - a bearing or camera
@@ -30,7 +37,8 @@ torch.func transforms are out of scope.
 Forward: SysID.integrateDyn_batch.  Backward: the adjoint sweep lam_t = dL/dx_t + F_t' lam_{t+1}, dL/dtheta += E_t' lam_{t+1}, dL/dx_0 = lam_0 - and, with input_grad,
 dL/du_t = G_t' lam_{t+1} - in one launch (SysID.rollout_vjp_batch, include/pdp_hip_sysid_vjp.h, include/pdp_hip_sysid_vjp_u.h).
 
-Limits.  Both layers: first order only (backward is once_differentiable).  oc_trajectory: no gradient with respect to ini_state; no finite state / control bounds (the
+Limits.  Both layers: first order only (backward is once_differentiable).  oc_trajectory: no gradient with respect to ini_state unless it is asked for (ini_grad=True;
+without the keyword an ini_state that requires a gradient is refused); no finite state / control bounds (the
 bounded solve goes through a log-barrier model whose KKT system is not the one the unit differentiates).  sysid_trajectory: the gradient with respect to the inputs on
 request only (input_grad=True; without the keyword an `inputs` that requires a gradient is refused), and only THROUGH the dynamics; no models without parameters."""
 import warnings
@@ -69,15 +77,47 @@ class _OCTrajectory(torch.autograd.Function):
         return (g.sum(dim=0) if ctx.shared else g.clone()), None, None, None, None, None
 
 
-def oc_trajectory(oc, ini_state, horizon, theta, return_info=False, **solver_kwargs):
+class _OCTrajectoryIni(torch.autograd.Function):
+    """_OCTrajectory with the initial state as an input of the function (oc_trajectory(..., ini_grad=True)): the same forward, and a backward that computes exactly
+    the gradients that are needed - dL/dx_0 from the adjoint sweep behind the one launch that also gives dL/dtheta"""
+
+    @staticmethod
+    def forward(ctx, theta, ini_state, oc, horizon, info_out, solver_kwargs):
+        out = _OCTrajectory.forward(ctx, theta, oc, ini_state.detach(), horizon, info_out, solver_kwargs)
+        ctx.want_theta, ctx.want_ini = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_state, grad_control):
+        x, u, lam, theta = ctx.saved_tensors
+        gx = torch.zeros_like(x) if grad_state is None else grad_state.to(torch.float64).contiguous()
+        gu = torch.zeros_like(u) if grad_control is None else grad_control.to(torch.float64).contiguous()
+        out = ctx.oc.pdp_vjp_batch(u, theta, gx, gu, state_traj=x, costate_traj=lam, want_ini=ctx.want_ini)
+        bad = int((out["status"] != 0).sum())
+        if bad:
+            warnings.warn("oc_trajectory: the Riccati sweep of the backward pass reported numerical trouble on %d trajectories (status bits of "
+                          "pdp_oc_pdp_grad_batched, include/pdp_hip.h)" % bad, RuntimeWarning)
+        g = None
+        if ctx.want_theta:
+            g = out["grad"].sum(dim=0) if ctx.shared else out["grad"].clone()
+        return g, (out["grad_x0"].clone() if ctx.want_ini else None), None, None, None, None
+
+
+def oc_trajectory(oc, ini_state, horizon, theta, return_info=False, ini_grad=False, **solver_kwargs):
     """Optimal trajectory of the PDP.OCSys `oc` from ini_state [B, n] over `horizon` steps at the parameter `theta`, differentiable in theta.
     theta: CUDA fp64 tensor, [p] (one parameter shared by the batch: theta.grad is the sum over the batch) or [B, p] (one per sample).
     Returns (state [B, T+1, n], control [B, T, m]) - with return_info=True also the solver's dict (cost, converged, iterations, ...).
     solver_kwargs go to OCSys.ocSolver_batch (tol, max_iter, u_init, warm_start, ...).  Samples that did not converge give one RuntimeWarning per call and are
-    differentiated at their last iterate."""
+    differentiated at their last iterate.
+    ini_grad=True: differentiable in ini_state as well.  ini_state must then be a CUDA fp64 tensor [B, n]; when it requires a gradient it receives dL/dx_0 through the
+    solution (state[:, 0]'s own cotangent included) from the one backward launch that also gives theta.grad.  A theta that requires no gradient is allowed then."""
     if not (torch.is_tensor(theta) and theta.is_cuda and theta.dtype == torch.float64):
         raise TypeError("oc_trajectory: theta must be a CUDA fp64 tensor ([p] shared, or [B, p] per sample)")
-    if torch.is_tensor(ini_state) and ini_state.requires_grad:
+    if ini_grad:
+        if not (torch.is_tensor(ini_state) and ini_state.is_cuda and ini_state.dtype == torch.float64 and ini_state.dim() == 2):
+            raise TypeError("oc_trajectory: with ini_grad=True ini_state must be a CUDA fp64 tensor [B, n]")
+    elif torch.is_tensor(ini_state) and ini_state.requires_grad:
         raise NotImplementedError("oc_trajectory: the gradient with respect to ini_state is not implemented (the auxiliary control system is solved with X_0 = 0); "
                                   "pass ini_state.detach()")
     if oc.has_bounds():
@@ -85,8 +125,13 @@ def oc_trajectory(oc, ini_state, horizon, theta, return_info=False, **solver_kwa
                                   "not the one the gradient unit differentiates")
     if theta.dim() not in (1, 2) or theta.shape[-1] != oc.n_auxvar:
         raise ValueError("oc_trajectory: theta must be [p] or [B, p] with p = %d, got %s" % (oc.n_auxvar, tuple(theta.shape)))
-    x0 = ini_state.detach() if torch.is_tensor(ini_state) else ini_state
     info = {}
+    if ini_grad:
+        if ini_state.shape[-1] != oc.n_state:
+            raise ValueError("oc_trajectory: ini_state must be [B, n] with n = %d, got %s" % (oc.n_state, tuple(ini_state.shape)))
+        state, control = _OCTrajectoryIni.apply(theta, ini_state, oc, int(horizon), info, solver_kwargs)
+        return (state, control, info) if return_info else (state, control)
+    x0 = ini_state.detach() if torch.is_tensor(ini_state) else ini_state
     state, control = _OCTrajectory.apply(theta, oc, x0, int(horizon), info, solver_kwargs)
     return (state, control, info) if return_info else (state, control)
 

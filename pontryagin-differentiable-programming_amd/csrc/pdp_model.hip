@@ -31,6 +31,7 @@ namespace pdp { extern __device__ long long g_rb_stamp[16]; }
 #include "pdp_cp_generic_kernels.h"
 #include "pdp_sysid_vjp_kernels.h"
 #include "pdp_sysid_jvp_kernels.h"
+#include "pdp_oc_x0_vjp_kernels.h"
 #include "pdp_launch.h"
 
 using namespace pdp;
@@ -160,6 +161,25 @@ int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const dou
                                      [&](auto K, auto&& go) { return with_fused_mode(mode(sens), [&](auto MODE) { return go(oc_pdp_fused3_kernel<Mdl, K(), MODE()>); }); },
                                      [&](auto&& go) { return with_fused_mode(mode(records), [&](auto MODE) { return go(oc_pdp_fused_kernel<Mdl, MODE()>); }); });
     } else { return Mdl::KIND == PDP_KIND_OC ? PDP_E_SIZE : PDP_E_MODE; }
+}
+
+// pdp_oc_sens_out.grad_x0: the fused unit's launch as it is, and behind it on the same stream the adjoint sweep of pdp_oc_x0_vjp_kernels.h on what that launch left in
+// x and in the gain workspace.  Refused with the Gauss-Newton row and with missing observations before anything is launched; every other check, and PDP_E_SIZE, are
+// the fused launch's own (the sweep's pool is at most 2400 doubles: it never adds a size limit).
+template <class Mdl>
+int oc_pdp_x0(int B, int T, int flags, const double* x0, const double* u, const double* th, int tb, const double* dx, const double* du, double* x, double* lam,
+              double* loss, double* grad, const pdp_oc_sens_out& so, int32_t* status, void* ws, int64_t wsb, void* st) {
+    if (flags & (PDP_GRAD_GAUSS_NEWTON | PDP_GRAD_SKIP_MISSING)) return PDP_E_ARG;
+    const int rc = oc_pdp<Mdl>(B, T, flags, x0, u, th, tb, dx, du, x, lam, loss, grad, so.dxdp, so.dudp, so.riccati, so.predict_record, status, ws, wsb, st);
+    if (rc != 0) return rc;
+    if constexpr (fused_oc_ok<Mdl>()) {
+        if (wsb < oc_ws_bytes<Mdl>(B, T)) return PDP_E_ARG;        // (the gains the sweep reads)
+        constexpr int rows = oc_x0_vjp_rows<Mdl>();
+        return with_bool((flags & PDP_OC_COTANGENT) != 0, [&](auto COT) {
+            return launch(oc_x0_vjp_kernel<Mdl, COT()>, dim3(B), dim3(64), sizeof(double) * (size_t)oc_x0_vjp_slice<Mdl>(rows), S(st), B, T, (const double*)x, u, th, tb,
+                          dx, du, (const double*)ws, so.grad_x0, rows);
+        });
+    } else { return rc; }
 }
 
 // pdp_oc_pdp_grad_wls_batched (include/pdp_hip_oc_wls.h): the PDP_FUSED_GN_W instantiations, chosen by oc_pdp_launch with the mode's own (longer) layout.  The checks
@@ -795,8 +815,10 @@ int64_t pdp_oc_predict_record_floats(void) {
 int pdp_oc_pdp_grad_sens_batched(int B, int T, int flags, const double* x0, const double* u, const double* theta, int tb, const double* demo_x,
                                  const double* demo_u, double* x, double* lam, double* loss, double* grad, const pdp_oc_sens_out* sens,
                                  int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
-    const pdp_oc_sens_out none = {nullptr, nullptr, nullptr, nullptr};
+    const pdp_oc_sens_out none = {nullptr, nullptr, nullptr, nullptr, nullptr};
     const pdp_oc_sens_out& so = sens ? *sens : none;
+    if (so.grad_x0)
+        return oc_pdp_x0<PdpModel>(B, T, flags, x0, u, theta, tb, demo_x, demo_u, x, lam, loss, grad, so, status, workspace, workspace_bytes, stream);
     return oc_pdp<PdpModel>(B, T, flags, x0, u, theta, tb, demo_x, demo_u, x, lam, loss, grad, so.dxdp, so.dudp, so.riccati, so.predict_record, status, workspace,
                             workspace_bytes, stream);
 }

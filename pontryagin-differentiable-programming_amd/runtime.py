@@ -663,7 +663,7 @@ class ModelLib:
         return out
 
     def oc_pdp_grad(self, u, theta, demo_x, demo_u, x0=None, x=None, lam=None, want_sens=False, buffers=None, packed=False, want_riccati=False,
-                    want_predict_record=False, gauss_newton=False, skip_missing=False, weights_x=None, weights_u=None, huber_delta=None):
+                    want_predict_record=False, gauss_newton=False, skip_missing=False, weights_x=None, weights_u=None, huber_delta=None, want_ini=False):
         """Fused forward + Riccati + PDP gradient.  Give (x, lam) to use an optimal trajectory (PDP_OC_GIVEN_TRAJ),
         else x0 and the kernel integrates u and the costates itself.  Returns dict(loss, grad, x, lam, status[, dxdp, dudp][, riccati]).
         packed: the kernel writes gradient and loss as one [B, p+1] tensor (PDP_OC_PACKED; out["packed"], out["grad"] is a view of it).
@@ -684,8 +684,14 @@ class ModelLib:
         a weight per demonstration entry (0: not observed) and Huber's loss on the standardised residual.  Any of the three implies the packed Gauss-Newton dict
         (packed_gn, grad, loss, gn as views) of the weighted / robust loss; they combine with skip_missing, x0, a given (x, lam) and buffers={"packed_gn": ...}; with
         want_sens, want_riccati, want_predict_record or packed: ValueError.  Beyond the fused kernels' limits the same row comes from scaled residuals and row-scaled
-        materialised sensitivities."""
+        materialised sensitivities.
+        want_ini (pdp_oc_sens_out.grad_x0): also out["grad_x0"] [B, n], half the gradient of the loss with respect to the initial state through the solution (the
+        convention of out["grad"]), from an adjoint sweep behind the unit's launch; every other output keeps its bits.  Alone, with packed, want_sens, want_riccati or
+        want_predict_record; with gauss_newton, skip_missing or the weights: ValueError.  Beyond the fused kernels' limits: the materialised route with n further columns."""
         weighted = weights_x is not None or weights_u is not None or huber_delta is not None
+        if want_ini and (weighted or gauss_newton or skip_missing):
+            raise ValueError("oc_pdp_grad: want_ini=True (the gradient with respect to the initial state) goes with the plain gradient, packed and the sensitivity "
+                             "outputs - not with gauss_newton, skip_missing, weights_x, weights_u or huber_delta")
         if weighted:
             for name, on in (("want_sens", want_sens), ("want_riccati", want_riccati), ("want_predict_record", want_predict_record), ("packed", packed)):
                 if on:
@@ -736,12 +742,13 @@ class ModelLib:
             flags |= PDP_GRAD_SKIP_MISSING
         nbytes = self.lib.pdp_oc_pdp_workspace_bytes(B, T)
         ws = _buffer(bufs, "ws", (max(nbytes, 8) // 8,))
-        if want_riccati or want_predict_record:
+        gx0 = _buffer(bufs, "grad_x0", (B, n)) if want_ini else None
+        if want_riccati or want_predict_record or want_ini:
             so = PdpOcSensOut(dxdp.data_ptr() if dxdp is not None else None, dudp.data_ptr() if dudp is not None else None,
-                              ric.data_ptr() if ric is not None else None, prec.data_ptr() if prec is not None else None)
+                              ric.data_ptr() if ric is not None else None, prec.data_ptr() if prec is not None else None, *((gx0.data_ptr(),) if want_ini else ()))
             rc = self.lib.pdp_oc_pdp_grad_sens_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(demo_x), ptr(demo_u), ptr(x), ptr(lam), ptr(loss),
                                                        ptr(pk), C.byref(so), ptr(status), ptr(ws), nbytes, current_stream_ptr())
-            if rc == PDP_E_SIZE:
+            if rc == PDP_E_SIZE and (want_riccati or want_predict_record):
                 raise RuntimeError("pdp_oc_pdp_grad_sens_batched: the Riccati / prediction records are outputs of the fused kernels (n <= 16, m <= 4, m + p <= 16)")
         else:
             rc = self.lib.pdp_oc_pdp_grad_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(demo_x), ptr(demo_u), ptr(x), ptr(lam), ptr(loss),
@@ -755,7 +762,7 @@ class ModelLib:
                 self._oc_rows_materialised(u, th, demo_x, demo_u, x0, x, lam, flags, loss, row, status, "missing_data")
                 grad.copy_(row[:, :p])
             else:
-                self._oc_pdp_grad_materialised(u, theta, demo_x, demo_u, x0, x, lam, flags, loss, grad, status, dxdp, dudp)
+                self._oc_pdp_grad_materialised(u, theta, demo_x, demo_u, x0, x, lam, flags, loss, grad, status, dxdp, dudp, grad_x0=gx0)
             if packed:
                 pk[:, p].copy_(loss)
             rc = 0
@@ -769,6 +776,8 @@ class ModelLib:
             out["riccati"] = ric
         if want_predict_record:
             out["predict_record"] = prec
+        if want_ini:
+            out["grad_x0"] = gx0
         return out
 
     def _oc_rows_materialised(self, u, th, demo_x, demo_u, x0, x, lam, flags, loss, pk, status, rule, wxd=None, wud=None, delta=float("inf")):
@@ -850,12 +859,15 @@ class ModelLib:
             return self._oc_rows(u, th, tb, demo_x, demo_u, x0, x, lam, bufs, skip_missing, wls)
         return rows, dict(demo_x=demo_x, demo_u=demo_u)
 
-    def oc_pdp_vjp(self, u, theta, gx, gu, x0=None, x=None, lam=None, buffers=None):
+    def oc_pdp_vjp(self, u, theta, gx, gu, x0=None, x=None, lam=None, buffers=None, want_ini=False):
         """The fused unit as a vector-Jacobian product of the OC solution (PDP_OC_COTANGENT, include/pdp_hip.h): gx [B, T+1, n] = dL/dx and gu [B, T, m] = dL/du are the
         cotangents of a caller's scalar loss L(x, u); grad [B, p] = sum_t gx_t' X_t + gu_t' U_t is dL/dtheta through the solution, X_t, U_t never leaving the chip.
         gx[:, 0] is not read (X_0 = 0).  Trajectory arguments as in oc_pdp_grad: (x, lam) given (PDP_OC_GIVEN_TRAJ), else x0 and the kernel integrates u and the costates.
         No loss is formed.  Returns dict(grad, x, lam, status); `buffers` (a dict the caller keeps) reuses the output tensors and the workspace between calls.
-        Problems beyond the fused kernels' limits take the kernel-by-kernel route, as in oc_pdp_grad."""
+        Problems beyond the fused kernels' limits take the kernel-by-kernel route, as in oc_pdp_grad.
+        want_ini (pdp_oc_sens_out.grad_x0 of pdp_oc_pdp_grad_sens_batched): also grad_x0 [B, n] = dL/dx_0 through the solution - the adjoint sweep mu_T = gx_T,
+        v_t = gu_t + G_t' mu_{t+1}, mu_t = gx_t + F_t' mu_{t+1} - K_t' v_t, grad_x0 = mu_0 with the unit's own gains K_t, launched behind the unit on the same stream.
+        gx[:, 0] is then read by the sweep and enters grad_x0 only; grad, x, lam and status keep their bits."""
         n, m, p = self.n, self.m, self.p
         u_shape, gx_shape, gu_shape = tuple(np.shape(u)), tuple(np.shape(gx)), tuple(np.shape(gu))
         if len(u_shape) != 3 or u_shape[2] != m:                # (shapes are judged before anything is converted or launched)
@@ -884,14 +896,34 @@ class ModelLib:
         status = _buffer(bufs, "status", (B,), torch.int32)
         nbytes = self.lib.pdp_oc_pdp_workspace_bytes(B, T)
         ws = _buffer(bufs, "ws", (max(nbytes, 8) // 8,))
-        rc = self.lib.pdp_oc_pdp_grad_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(gx), ptr(gu), ptr(x), ptr(lam), ptr(None),
-                                              ptr(grad), ptr(None), ptr(None), ptr(status), ptr(ws), nbytes, current_stream_ptr())
+        gx0 = _buffer(bufs, "grad_x0", (B, n)) if want_ini else None
+        if want_ini:
+            so = PdpOcSensOut(None, None, None, None, gx0.data_ptr())
+            rc = self.lib.pdp_oc_pdp_grad_sens_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(gx), ptr(gu), ptr(x), ptr(lam), ptr(None),
+                                                       ptr(grad), C.byref(so), ptr(status), ptr(ws), nbytes, current_stream_ptr())
+        else:
+            rc = self.lib.pdp_oc_pdp_grad_batched(B, T, flags, ptr(x0), ptr(u), ptr(th), tb, ptr(gx), ptr(gu), ptr(x), ptr(lam), ptr(None),
+                                                  ptr(grad), ptr(None), ptr(None), ptr(status), ptr(ws), nbytes, current_stream_ptr())
         if rc == PDP_E_SIZE:
             self._warn_materialised(T)
-            self._oc_pdp_grad_materialised(u, theta, gx, gu, x0, x, lam, flags, None, grad, status)
+            self._oc_pdp_grad_materialised(u, theta, gx, gu, x0, x, lam, flags, None, grad, status, grad_x0=gx0)
             rc = 0
         check(rc, "pdp_oc_pdp_grad_batched (PDP_OC_COTANGENT)")
-        return dict(grad=grad, x=x, lam=lam, status=status)
+        out = dict(grad=grad, x=x, lam=lam, status=status)
+        if want_ini:
+            out["grad_x0"] = gx0
+        return out
+
+    def oc_x0_vjp_rows(self):
+        """Pool rows (time steps per lane-parallel pass) of the initial-state adjoint sweep, oc_x0_vjp_kernel: csrc/pdp_oc_x0_vjp_kernels.h's rule restated (no entry
+        point reports it) - what a 2400-double pool holds of rows of SOLF_NVAR + n m + n + m doubles, made odd, at least 4 and at most 64.  SOLF_NVAR, the number of
+        variable entries of (F, G), is read from the model's generated header.  The result bits do not depend on the rows: tests place their chunk edges by them."""
+        import re
+        from . import codegen
+        src = open(os.path.join(codegen.GEN_DIR, self.name + ".h")).read()
+        nvar = int(re.search(r"\bSOLF_NVAR\s*=\s*(\d+)", src).group(1))
+        stride = (nvar + self.n * self.m + self.n + self.m) | 1
+        return min(64, max(4, 2400 // stride))
 
     def _warn_materialised(self, T):
         """once per model: the problem is outside the fused kernel's limits and takes the kernel-by-kernel route"""
@@ -960,11 +992,12 @@ class ModelLib:
                                               current_stream_ptr()), "pdp_oc_predict_batched")
         return x, u, lam
 
-    def _oc_pdp_grad_materialised(self, u, theta, demo_x, demo_u, x0, x, lam, flags, loss, grad, status, dxdp=None, dudp=None):
+    def _oc_pdp_grad_materialised(self, u, theta, demo_x, demo_u, x0, x, lam, flags, loss, grad, status, dxdp=None, dudp=None, grad_x0=None):
         """The PDP gradient unit by the reference's own route (PDP.py:272-314, 557-608 and the chain rule of cartpole_PDP.py:63-74), one
         kernel per stage: trajectory and costates (unless given), aux matrices to HBM, lqrSolver (column blocks for any p), contraction
         with (x - x_demo, u - u_demo) - or, with flags & PDP_OC_COTANGENT, with the cotangents that demo_x / demo_u then carry (row 0 of demo_x unread; no loss).
-        Fills the given output tensors."""
+        Fills the given output tensors.  grad_x0 [B, n]: the initial state as n further parameters of the LQ system - zero columns in E, Hxe, Hue, hxe and
+        X_0 = [0 | I] - whose columns of the sensitivities are contracted with the same cotangents (row 0 of demo_x included)."""
         torch = torch_cuda()
         B, T = u.shape[0], u.shape[1]
         n, m, p = self.n, self.m, self.p
@@ -972,14 +1005,24 @@ class ModelLib:
             x.copy_(self.oc_rollout(x0, u, theta, want_cost=False)[0])
             lam.copy_(self.oc_costate(x, u, theta))
         aux = self.oc_auxsys(x, u, lam, theta)
-        X, U, _, st = lqr_solve(aux["dynF"], aux["dynG"], aux["Hxx"], aux["Huu"], aux["hxx"], aux["hxe"], E=aux["dynE"], Hxu=aux["Hxu"], Hxe=aux["Hxe"],
-                                Hue=aux["Hue"], want_costate=False)
+        if grad_x0 is None:
+            X, U, _, st = lqr_solve(aux["dynF"], aux["dynG"], aux["Hxx"], aux["Huu"], aux["hxx"], aux["hxe"], E=aux["dynE"], Hxu=aux["Hxu"], Hxe=aux["Hxe"],
+                                    Hue=aux["Hue"], want_costate=False)
+        else:
+            wide = lambda a: torch.cat([a, a.new_zeros(a.shape[:-1] + (n,))], dim=-1)
+            X0 = torch.cat([u.new_zeros((n, p)), torch.eye(n, dtype=torch.float64, device="cuda")], dim=1)
+            Xw, Uw, _, st = lqr_solve(aux["dynF"], aux["dynG"], aux["Hxx"], aux["Huu"], aux["hxx"], wide(aux["hxe"]), E=wide(aux["dynE"]), Hxu=aux["Hxu"],
+                                      Hxe=wide(aux["Hxe"]), Hue=wide(aux["Hue"]), X0=X0, want_costate=False)
+            X, U = Xw[..., :p].contiguous(), Uw[..., :p].contiguous()
         if flags & PDP_OC_COTANGENT:
             ex, eu = demo_x.clone(), demo_u
             ex[:, 0] = 0.0
         else:
             ex, eu = x - demo_x, u - demo_u
             loss.copy_((ex ** 2).sum(dim=(1, 2)) + (eu ** 2).sum(dim=(1, 2)))
+        if grad_x0 is not None:
+            ex_all = demo_x if flags & PDP_OC_COTANGENT else ex
+            grad_x0.copy_(torch.einsum("bti,btik->bk", ex_all, Xw[..., p:]) + torch.einsum("bti,btik->bk", eu, Uw[..., p:]))
         g = torch.empty((B, p), dtype=torch.float64, device="cuda")
         core = load_core()
         ex_path, ex_fin, eu_c = ex[:, :T].contiguous(), ex[:, T].contiguous(), eu.contiguous()      # (named: they must outlive the launch)
