@@ -165,7 +165,7 @@ int oc_pdp(int B, int T, int flags, const double* x0, const double* u, const dou
 
 // pdp_oc_sens_out.grad_x0: the fused unit's launch as it is, and behind it on the same stream the adjoint sweep of pdp_oc_x0_vjp_kernels.h on what that launch left in
 // x and in the gain workspace.  Refused with the Gauss-Newton row and with missing observations before anything is launched; every other check, and PDP_E_SIZE, are
-// the fused launch's own (the sweep's pool is at most 2400 doubles: it never adds a size limit).
+// the fused launch's own (the sweep's pool is at most SWEEP_POOL_DOUBLES: it never adds a size limit).
 template <class Mdl>
 int oc_pdp_x0(int B, int T, int flags, const double* x0, const double* u, const double* th, int tb, const double* dx, const double* du, double* x, double* lam,
               double* loss, double* grad, const pdp_oc_sens_out& so, int32_t* status, void* ws, int64_t wsb, void* st) {
@@ -174,9 +174,9 @@ int oc_pdp_x0(int B, int T, int flags, const double* x0, const double* u, const 
     if (rc != 0) return rc;
     if constexpr (fused_oc_ok<Mdl>()) {
         if (wsb < oc_ws_bytes<Mdl>(B, T)) return PDP_E_ARG;        // (the gains the sweep reads)
-        constexpr int rows = oc_x0_vjp_rows<Mdl>();
+        constexpr int rows = oc_x0_vjp_rows_of(OcX0VjpPool<Mdl>::STRIDE);
         return with_bool((flags & PDP_OC_COTANGENT) != 0, [&](auto COT) {
-            return launch(oc_x0_vjp_kernel<Mdl, COT()>, dim3(B), dim3(64), sizeof(double) * (size_t)oc_x0_vjp_slice<Mdl>(rows), S(st), B, T, (const double*)x, u, th, tb,
+            return launch(oc_x0_vjp_kernel<Mdl, COT()>, dim3(B), dim3(64), sizeof(double) * (size_t)OcX0VjpPool<Mdl>::slice(rows), S(st), B, T, (const double*)x, u, th, tb,
                           dx, du, (const double*)ws, so.grad_x0, rows);
         });
     } else { return rc; }
@@ -673,81 +673,62 @@ int sysid_step(int B, int T, const double* u, const double* xobs, const double* 
     } else { return Mdl::KIND == PDP_KIND_SYSID ? PDP_E_SIZE : PDP_E_MODE; }
 }
 
-// The rollout's vector-Jacobian product (pdp_sysid_rollout_vjp_batched, include/pdp_hip_sysid_vjp.h): one launch of sysid_vjp_kernel on the given trajectory.  The
-// argument checks come first, whatever the model; the kernel exists for n <= 64 and p <= 512 (eight parameter slots per lane).
+// The plan of a SysID sweep launch (pdp_sweep_pool.h) for a batch of B: the pool rows and the bytes of dynamic LDS, or in `rows` the error - PDP_E_MODE for another
+// model kind, PDP_E_SIZE where the kernel is not built for the model (FITS, known at compile time: `ok` tells the caller whether to name the kernel at all) or its
+// block exceeds 150 KB.  The argument checks come before it, whatever the model.
+template <bool OK> struct SweepPlan { static constexpr bool ok = OK; int rows; size_t lds; };
+template <class Mdl, template <class> class PoolOf, bool FITS>
+auto sweep_plan(int B) {
+    if constexpr (Mdl::KIND != PDP_KIND_SYSID) return SweepPlan<false>{PDP_E_MODE, 0};
+    else if constexpr (!FITS) return SweepPlan<false>{PDP_E_SIZE, 0};
+    else {
+        const int rows = sysid_vjp_rows_of(B, device_cu_count(), PoolOf<Mdl>::STRIDE, Mdl::CHUNK);
+        const size_t lds = sizeof(double) * (size_t)PoolOf<Mdl>::slice(rows);
+        return lds > 150 * 1024 ? SweepPlan<true>{PDP_E_SIZE, 0} : SweepPlan<true>{rows, lds};
+    }
+}
+// the kernels exist for n <= 64 and eight slots of 64 columns per lane: p <= 512 parameters, p + m <= 512 where a lane also owns the columns of G
+template <class Mdl> constexpr bool sweep_fits_p = Mdl::NX <= 64 && Mdl::NP <= 512;
+template <class Mdl> constexpr bool sweep_fits_pm = Mdl::NX <= 64 && Mdl::NP + Mdl::NU <= 512;
+
+// The rollout's vector-Jacobian product (pdp_sysid_rollout_vjp_batched, include/pdp_hip_sysid_vjp.h): one launch of sysid_vjp_kernel on the given trajectory.
 template <class Mdl>
 int sysid_rollout_vjp(int B, int T, const double* x, const double* u, const double* th, int tb, const double* gx, double* grad_theta, double* grad_x0, void* st) {
     if (B <= 0 || T <= 0 || !x || !u || !th || !gx || (!grad_theta && !grad_x0) || (tb != 0 && tb < Mdl::NP)) return PDP_E_ARG;
-    if constexpr (Mdl::KIND != PDP_KIND_SYSID) return PDP_E_MODE;
-    else if constexpr (Mdl::NX > 64 || Mdl::NP > 512) return PDP_E_SIZE;
-    else {
-        const int rows = sysid_vjp_rows<Mdl>(B, device_cu_count());
-        const size_t lds = sizeof(double) * (size_t)sysid_vjp_slice<Mdl>(rows);
-        if (lds > 150 * 1024) return PDP_E_SIZE;
-        return launch(sysid_vjp_kernel<Mdl>, dim3(B), dim3(64), lds, S(st), B, T, x, u, th, tb, gx, grad_theta, grad_x0, rows);
-    }
+    const auto pl = sweep_plan<Mdl, SysidVjpPool, sweep_fits_p<Mdl>>(B);
+    if constexpr (!pl.ok) return pl.rows;
+    else return pl.rows < 0 ? pl.rows : launch(sysid_vjp_kernel<Mdl>, dim3(B), dim3(64), pl.lds, S(st), B, T, x, u, th, tb, gx, grad_theta, grad_x0, pl.rows);
 }
 
 // ... and with the gradient with respect to the inputs (pdp_sysid_rollout_vjp_u_batched, include/pdp_hip_sysid_vjp_u.h).  Without grad_u this is the launch above, the
-// same code object; with it sysid_vjp_u_kernel, whose lanes own the p + m columns of [E | G] (eight slots: p + m <= 512) and whose pool row is longer.
+// same code object; with it sysid_vjp_u_kernel, whose lanes own the p + m columns of [E | G] and whose pool row is longer.
 template <class Mdl>
 int sysid_rollout_vjp_u(int B, int T, const double* x, const double* u, const double* th, int tb, const double* gx, double* grad_theta, double* grad_x0, double* grad_u,
                         void* st) {
     if (B <= 0 || T <= 0 || !x || !u || !th || !gx || (!grad_theta && !grad_x0 && !grad_u) || (tb != 0 && tb < Mdl::NP)) return PDP_E_ARG;
-    if constexpr (Mdl::KIND != PDP_KIND_SYSID) return PDP_E_MODE;
-    else if constexpr (Mdl::NX > 64) return PDP_E_SIZE;
-    else {
-        if (!grad_u) return sysid_rollout_vjp<Mdl>(B, T, x, u, th, tb, gx, grad_theta, grad_x0, st);
-        if constexpr (Mdl::NP + Mdl::NU > 512) return PDP_E_SIZE;
-        else {
-            const int rows = sysid_vjp_u_rows<Mdl>(B, device_cu_count());
-            const size_t lds = sizeof(double) * (size_t)sysid_vjp_u_slice<Mdl>(rows);
-            if (lds > 150 * 1024) return PDP_E_SIZE;
-            return launch(sysid_vjp_u_kernel<Mdl>, dim3(B), dim3(64), lds, S(st), B, T, x, u, th, tb, gx, grad_theta, grad_x0, grad_u, rows);
-        }
-    }
+    if (!grad_u) return sysid_rollout_vjp<Mdl>(B, T, x, u, th, tb, gx, grad_theta, grad_x0, st);
+    const auto pl = sweep_plan<Mdl, SysidVjpUPool, sweep_fits_pm<Mdl>>(B);
+    if constexpr (!pl.ok) return pl.rows;
+    else return pl.rows < 0 ? pl.rows : launch(sysid_vjp_u_kernel<Mdl>, dim3(B), dim3(64), pl.lds, S(st), B, T, x, u, th, tb, gx, grad_theta, grad_x0, grad_u, pl.rows);
 }
 // pool rows of the launch above (pdp_sysid_rollout_vjp_u_rows)
-template <class Mdl>
-int sysid_rollout_vjp_u_rows(int B) {
-    if (B <= 0) return PDP_E_ARG;
-    if constexpr (Mdl::KIND != PDP_KIND_SYSID) return PDP_E_MODE;
-    else if constexpr (Mdl::NX > 64 || Mdl::NP + Mdl::NU > 512) return PDP_E_SIZE;
-    else {
-        const int rows = sysid_vjp_u_rows<Mdl>(B, device_cu_count());
-        return sizeof(double) * (size_t)sysid_vjp_u_slice<Mdl>(rows) > 150 * 1024 ? PDP_E_SIZE : rows;
-    }
-}
+template <class Mdl> int sysid_rollout_vjp_u_rows(int B) { return B <= 0 ? PDP_E_ARG : sweep_plan<Mdl, SysidVjpUPool, sweep_fits_pm<Mdl>>(B).rows; }
 
 // The rollout's Jacobian-vector product (pdp_sysid_rollout_jvp_batched, include/pdp_hip_sysid_jvp.h): one launch of sysid_jvp_kernel on the given trajectory, the
-// instantiation with `pathu` when d_u is given.  The pool row and the row rule are sysid_vjp_kernel's; the limits are those of the vjp pair.
+// instantiation with `pathu` when d_u is given.  The pool and the plan are sysid_vjp_kernel's; with d_u the limit is p + m <= 512 as for sysid_vjp_u_kernel.
 template <class Mdl>
 int sysid_rollout_jvp(int B, int T, const double* x, const double* u, const double* th, int tb, const double* dth, int dtb, const double* dx0, const double* du,
                       double* dx, void* st) {
     if (B <= 0 || T <= 0 || !x || !u || !th || !dx || (!dth && !dx0 && !du) || (tb != 0 && tb < Mdl::NP) || (dtb != 0 && dtb < Mdl::NP)) return PDP_E_ARG;
-    if constexpr (Mdl::KIND != PDP_KIND_SYSID) return PDP_E_MODE;
-    else if constexpr (Mdl::NX > 64 || Mdl::NP > 512) return PDP_E_SIZE;
-    else {
-        const int rows = sysid_vjp_rows<Mdl>(B, device_cu_count());
-        const size_t lds = sizeof(double) * (size_t)sysid_vjp_slice<Mdl>(rows);
-        if (lds > 150 * 1024) return PDP_E_SIZE;
-        return with_bool(du != nullptr, [&](auto WU) {
-            if constexpr (WU() && Mdl::NP + Mdl::NU > 512) return (int)PDP_E_SIZE;
-            else return launch(sysid_jvp_kernel<Mdl, WU()>, dim3(B), dim3(64), lds, S(st), B, T, x, u, th, tb, dth, dtb, dx0, du, dx, rows);
-        });
-    }
+    const auto pl = sweep_plan<Mdl, SysidVjpPool, sweep_fits_p<Mdl>>(B);
+    if constexpr (!pl.ok) return pl.rows;
+    else return pl.rows < 0 ? pl.rows : with_bool(du != nullptr, [&](auto WU) {
+        if constexpr (WU() && !sweep_fits_pm<Mdl>) return (int)PDP_E_SIZE;
+        else return launch(sysid_jvp_kernel<Mdl, WU()>, dim3(B), dim3(64), pl.lds, S(st), B, T, x, u, th, tb, dth, dtb, dx0, du, dx, pl.rows);
+    });
 }
 // pool rows of the launch above (pdp_sysid_rollout_jvp_rows)
-template <class Mdl>
-int sysid_rollout_jvp_rows(int B) {
-    if (B <= 0) return PDP_E_ARG;
-    if constexpr (Mdl::KIND != PDP_KIND_SYSID) return PDP_E_MODE;
-    else if constexpr (Mdl::NX > 64 || Mdl::NP > 512) return PDP_E_SIZE;
-    else {
-        const int rows = sysid_vjp_rows<Mdl>(B, device_cu_count());
-        return sizeof(double) * (size_t)sysid_vjp_slice<Mdl>(rows) > 150 * 1024 ? PDP_E_SIZE : rows;
-    }
-}
+template <class Mdl> int sysid_rollout_jvp_rows(int B) { return B <= 0 ? PDP_E_ARG : sweep_plan<Mdl, SysidVjpPool, sweep_fits_p<Mdl>>(B).rows; }
 
 template <class Mdl> int nnz_path() { return Mdl::PATH_NVAR; }
 

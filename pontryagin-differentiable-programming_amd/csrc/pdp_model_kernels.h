@@ -19,6 +19,7 @@
 #include "pdp_policy.h"
 #include "pdp_wave.h"
 #include "pdp_chain_rule.h"
+#include "pdp_sweep_pool.h"
 
 namespace pdp {
 
@@ -1588,14 +1589,13 @@ __global__ void __launch_bounds__(64) cp_step_adjoint_kernel(int B, int T, pdp_p
     for (int q = 0; q < 8; ++q) gacc[q] = 0.0;
     // per-lane pool offsets: column `lane` of F (lane < NX) and of G (lane < NU), entries c_x[lane], c_u[lane]
     int fo[NX], fm[NX], go[NX], gm[NX], cxo = 0, cxm = 0, cuo = 0, cum = 0;
-    auto enc = [&](int code, int& o, int& m) { if (code >= 0) { o = NC + code; m = STRIDE; } else { o = (code == -1) ? 0 : 1 + (-2 - code); m = 0; } };
 #pragma unroll
     for (int k = 0; k < NX; ++k) {
-        enc(lane < NX ? Mdl::path_code(0, k * NX + lane) : -1, fo[k], fm[k]);
-        enc(lane < NU ? Mdl::path_code(1, k * NU + lane) : -1, go[k], gm[k]);
+        pool_enc<NC, STRIDE>(lane < NX ? Mdl::path_code(0, k * NX + lane) : -1, fo[k], fm[k]);
+        pool_enc<NC, STRIDE>(lane < NU ? Mdl::path_code(1, k * NU + lane) : -1, go[k], gm[k]);
     }
-    enc(lane < NX ? Mdl::path_code(2, lane) : -1, cxo, cxm);
-    enc(lane < NU ? Mdl::path_code(3, lane) : -1, cuo, cum);
+    pool_enc<NC, STRIDE>(lane < NX ? Mdl::path_code(2, lane) : -1, cxo, cxm);
+    pool_enc<NC, STRIDE>(lane < NU ? Mdl::path_code(3, lane) : -1, cuo, cum);
     // offloaded activations of step t are requested from the workspace one step ahead (the sweep visits t = T-1 .. 0 in order)
     double apre[8];
     auto request_acts = [&](int t, double (&a)[8]) {

@@ -10,25 +10,14 @@
 // F_t, G_t are the models' `solf` group.  The fused kernels are not touched.  DESIGN.md section 4.1m.
 #pragma once
 #include "pdp_model_kernels.h"
+#include "pdp_sweep_pool.h"
 
 namespace pdp {
 
-// a pool row of the kernel below: the packed variable entries of (F_t, G_t) | K_t [NU][NX] | gx_t [NX] | gu_t [NU]
-template <class Mdl> constexpr int oc_x0_vjp_stride() { return (Mdl::SOLF_NVAR + Mdl::NX * Mdl::NU + Mdl::NX + Mdl::NU) | 1; }
-// Pool rows (time steps per lane-parallel pass): what the 2400-double pool of sysid_vjp_rows_of holds of them, at least 4 and at most 64 (a lane per step).  The rule
-// reads the row stride alone - runtime.ModelLib.oc_x0_vjp_rows restates it - and the result bits do not depend on it: the sweep visits the steps in the same order
-// whatever the pass they were evaluated in.
-constexpr int oc_x0_vjp_rows_of(int stride) { return 2400 / stride < 4 ? 4 : (2400 / stride > 64 ? 64 : 2400 / stride); }
-template <class Mdl> constexpr int oc_x0_vjp_rows() { return oc_x0_vjp_rows_of(oc_x0_vjp_stride<Mdl>()); }
-// doubles of dynamic LDS: [0.0 | constants | rows x stride], rounded up to 16 bytes
-template <class Mdl>
-__host__ __device__ inline int oc_x0_vjp_slice(int rows) { return (1 + Mdl::SOLF_NCONST + rows * oc_x0_vjp_stride<Mdl>() + 1) & ~1; }
-
-// One wavefront per trajectory on the trajectory and the gains the fused launch left behind (sysid_vjp_kernel's structure).  The horizon is cut into chunks of equal
-// length <= CH, visited last to first.  Per chunk: lane tl loads x_t, u_t of step t = t0 + tl, evaluates the `solf` group through a PackedSink into pool row tl
-// (structural zeros read blk[0] = 0.0, constants the block behind it), copies K_t from the gain workspace behind it and puts the step's cotangents behind that - COT:
-// gx_t, gu_t as the caller gave them (gx_0 included: it enters grad_x0 and nothing else); else the default mode's residuals x_t - demo_x_t, u_t - demo_u_t, which gives
-// half the gradient of the demonstration loss, the convention of `grad`.  Then the serial sweep over the chunk's steps: lane i < NX owns mu[i] and reads column i of F_t
+// A sweep kernel on OcX0VjpPool (pdp_sweep_pool.h: the block, the rows, the structure), on the trajectory and the gains the fused launch left behind.  The chunks are
+// visited last to first.  Per chunk: lane tl loads x_t, u_t of step t = t0 + tl, evaluates the `solf` group through a PackedSink into pool row tl, copies K_t from
+// the gain workspace behind it and puts the step's cotangents behind that - COT: gx_t, gu_t as the caller gave them (gx_0 included: it enters grad_x0 and nothing
+// else); else the default mode's residuals x_t - demo_x_t, u_t - demo_u_t, which gives half the gradient of the demonstration loss, the convention of `grad`.  Then the serial sweep over the chunk's steps: lane i < NX owns mu[i] and reads column i of F_t
 // and of K_t, lane NX + j (j < NU) owns v[j] and reads column j of G_t.  mu_{t+1}[k] reaches all of them as a scalar (v_readlane of its owner's register), then v_t[j]
 // reaches the mu lanes the same way: two broadcast rounds per step, no LDS write / read pair and no global read on the recursion's chain - the pool reads of a step do
 // not depend on mu.  The lanes behind NX + NU read blk[0] throughout.  No masking, no status word: a trajectory whose gains (or x, u, theta, cotangents) are not finite
@@ -38,7 +27,8 @@ __global__ void __launch_bounds__(64) oc_x0_vjp_kernel(int B, int T, const doubl
                                                         const double* __restrict__ gx, const double* __restrict__ gu, const double* __restrict__ ws_gain,
                                                         double* __restrict__ grad_x0, int CH) {
     constexpr int NX = Mdl::NX, NU = Mdl::NU, GSZ = fused_gain_doubles<Mdl>();
-    constexpr int NC = 1 + Mdl::SOLF_NCONST, KO = Mdl::SOLF_NVAR, GXO = KO + NX * NU, GUO = GXO + NX, STRIDE = oc_x0_vjp_stride<Mdl>();
+    using Pool = OcX0VjpPool<Mdl>;
+    constexpr int NC = Pool::NC, KO = Pool::KO, GXO = Pool::GXO, GUO = Pool::GUO, STRIDE = Pool::STRIDE;
     static_assert(NX + NU <= 64, "a lane per component of (mu, v)");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double* blk = lds;
@@ -57,9 +47,8 @@ __global__ void __launch_bounds__(64) oc_x0_vjp_kernel(int B, int T, const doubl
     // per-lane pool offsets (o) and row multipliers (m): column `lane` of F / column lane - NX of G, this lane's cotangent, column `lane` of K
     const bool isx = lane < NX, isu = lane >= NX && lane < NX + NU;
     int ao[NX], am[NX], ko[NU], km[NU], go = 0, gm = 0;
-    auto enc = [&](int code, int& o, int& m) { if (code >= 0) { o = NC + code; m = STRIDE; } else { o = (code == -1) ? 0 : 1 + (-2 - code); m = 0; } };
 #pragma unroll
-    for (int k = 0; k < NX; ++k) enc(isx ? Mdl::solf_code(0, k * NX + lane) : (isu ? Mdl::solf_code(1, k * NU + (lane - NX)) : -1), ao[k], am[k]);
+    for (int k = 0; k < NX; ++k) pool_enc<NC, STRIDE>(isx ? Mdl::solf_code(0, k * NX + lane) : (isu ? Mdl::solf_code(1, k * NU + (lane - NX)) : -1), ao[k], am[k]);
 #pragma unroll
     for (int j = 0; j < NU; ++j) { ko[j] = isx ? NC + KO + j * NX + lane : 0; km[j] = isx ? STRIDE : 0; }
     if (isx) { go = NC + GXO + lane; gm = STRIDE; }
@@ -89,12 +78,13 @@ __global__ void __launch_bounds__(64) oc_x0_vjp_kernel(int B, int T, const doubl
             double a = blk[go + tl * gm];                                  // lanes of mu: gx_t + F_t' mu_{t+1}; lanes of v: gu_t + G_t' mu_{t+1}
 #pragma unroll
             for (int k = 0; k < NX; ++k) {
-                const double mk = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(mu), k), __builtin_amdgcn_readlane(__double2loint(mu), k));
+                const double mk = readlane_f64(mu, k);
                 a += blk[ao[k] + tl * am[k]] * mk;
             }
             double m_new = a;
 #pragma unroll
             for (int j = 0; j < NU; ++j) {
+                // (readlane_f64 spelled out, high half first: with the helper's order the v_fma below comes out with its two factors swapped - DESIGN.md section 4.1n)
                 const double vj = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(a), NX + j), __builtin_amdgcn_readlane(__double2loint(a), NX + j));
                 m_new -= blk[ko[j] + tl * km[j]] * vj;
             }

@@ -35,10 +35,9 @@ template <class Mdl> struct JvpPathuSink {
     }
 };
 
-// One wavefront per trajectory on the GIVEN trajectory x, sysid_vjp_kernel's structure run forwards: the horizon is cut into chunks of equal length <= CH, visited first
-// to last.  Per chunk lane tl evaluates the model's groups at step t = t0 + tl: the entries of F_t go to pool row tl, and the forcing term w_t = E_t d_theta + G_t du_t -
+// sysid_vjp_kernel's structure and pool (SysidVjpPool, pdp_sweep_pool.h) run forwards on the GIVEN trajectory x: the chunks are visited first to last.  Per chunk lane tl evaluates the model's groups at step t = t0 + tl: the entries of F_t go to pool row tl, and the forcing term w_t = E_t d_theta + G_t du_t -
 // which does not depend on the recursion - is summed there and then, entry by entry as eval_path produces it (constant entries from a compile-time loop over the codes),
-// and stored in the row's n slots behind the packed entries (where the vjp kernel keeps the cotangents: the same stride, the same row rule).  Its cost is the number of
+// and stored in the row's n slots behind the packed entries (where the vjp kernel keeps the cotangents).  Its cost is the number of
 // structurally non-zero entries of E and G.  Then the serial sweep: lane i < NX owns dx[i] and reads ROW i of F_t through offset / multiplier pairs formed once;
 // dx_t[k] reaches it as a scalar (v_readlane of its owner's register), so the chain holds no LDS write / read pair, no wait on a store and no global read.  Each step's
 // dx_{t+1} is stored directly to d_x[b][t+1] (n adjacent doubles, one store; nothing waits for it).  WU: with d_u (never NULL then) - `pathu` is evaluated only there.
@@ -48,7 +47,8 @@ __global__ void __launch_bounds__(64) sysid_jvp_kernel(int B, int T, const doubl
                                                         int tb, const double* __restrict__ d_theta, int dtb, const double* __restrict__ d_x0,
                                                         const double* __restrict__ d_u, double* __restrict__ d_x, int CH) {
     constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP;
-    constexpr int NC = 1 + Mdl::PATH_NCONST, GX = Mdl::PATH_NVAR, STRIDE = sysid_vjp_stride<Mdl>();
+    using Pool = SysidVjpPool<Mdl>;
+    constexpr int NC = Pool::NC, GX = Pool::GX, STRIDE = Pool::STRIDE;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double* blk = lds;
     double* pool = blk + NC;
@@ -66,9 +66,8 @@ __global__ void __launch_bounds__(64) sysid_jvp_kernel(int B, int T, const doubl
     for (int i_ = lane; i_ < Mdl::PATH_NCONST; i_ += 64) blk[1 + i_] = Mdl::path_const(i_);
     // per-lane pool offsets (o) and row multipliers (m): row `lane` of F, w_t[lane]
     int fo[NX], fm[NX], wo = 0, wm = 0;
-    auto enc = [&](int code, int& o, int& m) { if (code >= 0) { o = NC + code; m = STRIDE; } else { o = (code == -1) ? 0 : 1 + (-2 - code); m = 0; } };
 #pragma unroll
-    for (int k = 0; k < NX; ++k) enc(lane < NX ? Mdl::path_code(0, lane * NX + k) : -1, fo[k], fm[k]);
+    for (int k = 0; k < NX; ++k) pool_enc<NC, STRIDE>(lane < NX ? Mdl::path_code(0, lane * NX + k) : -1, fo[k], fm[k]);
     if (lane < NX) { wo = NC + GX + lane; wm = STRIDE; }
     double dx = (d_x0 && lane < NX) ? d_x0[(int64_t)b * NX + lane] : 0.0;  // dx_0
     if (lane < NX) ob[lane] = dx;
@@ -118,7 +117,7 @@ __global__ void __launch_bounds__(64) sysid_jvp_kernel(int B, int T, const doubl
             double x_new = blk[wo + tl * wm];
 #pragma unroll
             for (int k = 0; k < NX; ++k) {
-                const double xk = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(dx), k), __builtin_amdgcn_readlane(__double2loint(dx), k));
+                const double xk = readlane_f64(dx, k);
                 x_new += blk[fo[k] + tl * fm[k]] * xk;
             }
             dx = x_new;

@@ -8,39 +8,13 @@
 // instructions sysid_vjp_kernel had - the scalar code of the chunk arithmetic came out in another order - so that kernel keeps its own text: DESIGN.md section 4.1k.)
 #pragma once
 #include "pdp_model_kernels.h"
+#include "pdp_sweep_pool.h"
 
 namespace pdp {
 
-// a pool row of the kernel below: the packed variable entries of (F_t, E_t), then the NX cotangents g_t
-template <class Mdl> constexpr int sysid_vjp_stride() { return (Mdl::PATH_NVAR + Mdl::NX) | 1; }
-// doubles of dynamic LDS: [0.0 | constants | rows x stride], rounded up to 16 bytes
-template <class Mdl>
-__host__ __device__ inline int sysid_vjp_slice(int rows) { return (1 + Mdl::PATH_NCONST + rows * sysid_vjp_stride<Mdl>() + 1) & ~1; }
-// Pool rows (time steps per lane-parallel Jacobian pass).  The generated CHUNK while a CU holds at most one trajectory per SIMD; a larger batch gets a pool of at most
-// 2400 doubles (18.75 KB: with the constants and the allocation granularity an eighth of the CU's 160 KB), so that two workgroups per SIMD are resident and fill each
-// other's waits - the rule of sysid_rows.  The rule reads the row stride alone: runtime.ModelLib.sysid_vjp_rows restates it.  The result bits do not depend on it: the
-// sweep visits the steps in the same order whatever the pass they were evaluated in.
-inline int sysid_vjp_rows_of(int B, int cus, int stride, int chunk) {
-    if (B <= 4 * cus) return chunk;
-    const int fit = 2400 / stride;
-    return fit >= 4 ? (fit < chunk ? fit : chunk) : chunk;
-}
-template <class Mdl>
-__host__ inline int sysid_vjp_rows(int B, int cus) { return sysid_vjp_rows_of(B, cus, sysid_vjp_stride<Mdl>(), Mdl::CHUNK); }
-
-// The same three for sysid_vjp_u_kernel.  Its pool row: the packed entries of (F_t, E_t) | those of G_t | the NX cotangents | NU doubles in which the sweep leaves this
-// step's dL/du_t; the constants of both groups behind blk[0].  The rows are sysid_vjp_rows' rule on this stride (Mdl::CHUNK was picked for the shorter row: a pool of
-// CHUNK rows is (NVAR_G + NU) * CHUNK doubles larger here, which the host routine's 150 KB bound sees).
-template <class Mdl> constexpr int sysid_vjp_u_stride() { return (Mdl::PATH_NVAR + Mdl::PATHU_NVAR + Mdl::NX + Mdl::NU) | 1; }
-template <class Mdl>
-__host__ __device__ inline int sysid_vjp_u_slice(int rows) { return (1 + Mdl::PATH_NCONST + Mdl::PATHU_NCONST + rows * sysid_vjp_u_stride<Mdl>() + 1) & ~1; }
-template <class Mdl>
-__host__ inline int sysid_vjp_u_rows(int B, int cus) { return sysid_vjp_rows_of(B, cus, sysid_vjp_u_stride<Mdl>(), Mdl::CHUNK); }
-
-// One wavefront per trajectory on the GIVEN trajectory x (what sysid_integrate_kernel wrote): no rollout here.  The horizon is cut into chunks of equal length <= CH,
-// visited last to first (cp_step_adjoint_kernel's structure).  Per chunk: lane tl loads x_t, u_t, g_t of step t = t0 + tl and evaluates the model's path group through a
-// PackedSink into pool row tl (structural zeros read blk[0] = 0.0, constants the block behind it); then the serial sweep over the chunk's steps.  In the sweep lane
-// i < NX owns lam[i] and reads column i of F_t, the lane of parameter j = lane + 64 q owns its accumulator and reads column j of E_t; lam_{t+1}[k] reaches all of them
+// A sweep kernel on SysidVjpPool (pdp_sweep_pool.h: the block, the rows, the structure), on the GIVEN trajectory x (what sysid_integrate_kernel wrote): no rollout
+// here.  The chunks are visited last to first.  Per chunk: lane tl loads x_t, u_t, g_t of step t = t0 + tl and evaluates the model's path group through a PackedSink
+// into pool row tl; then the serial sweep over the chunk's steps.  In the sweep lane i < NX owns lam[i] and reads column i of F_t, the lane of parameter j = lane + 64 q owns its accumulator and reads column j of E_t; lam_{t+1}[k] reaches all of them
 // as a scalar (v_readlane of its owner's register), so the recursion's chain holds no LDS write / read pair and no global read: the pool reads of a step do not depend
 // on lam.  The E_t' lam_{t+1} accumulation stays in the step loop (it shares the broadcast lam_{t+1}[k] with the recursion and does not feed it).
 // theta is read through its (uniform) pointer - scalar loads, no register per parameter, whatever p.  No masking, no status word: a NaN anywhere in this trajectory's
@@ -49,7 +23,8 @@ template <class Mdl>
 __global__ void __launch_bounds__(64) sysid_vjp_kernel(int B, int T, const double* __restrict__ x, const double* __restrict__ u, const double* __restrict__ theta,
                                                         int tb, const double* __restrict__ gx, double* __restrict__ grad_theta, double* __restrict__ grad_x0, int CH) {
     constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP, NQ = NP > 0 ? (NP + 63) / 64 : 1;
-    constexpr int NC = 1 + Mdl::PATH_NCONST, GX = Mdl::PATH_NVAR, STRIDE = sysid_vjp_stride<Mdl>();
+    using Pool = SysidVjpPool<Mdl>;
+    constexpr int NC = Pool::NC, GX = Pool::GX, STRIDE = Pool::STRIDE;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double* blk = lds;
     double* pool = blk + NC;
@@ -64,12 +39,11 @@ __global__ void __launch_bounds__(64) sysid_vjp_kernel(int B, int T, const doubl
     for (int i_ = lane; i_ < Mdl::PATH_NCONST; i_ += 64) blk[1 + i_] = Mdl::path_const(i_);
     // per-lane pool offsets (o) and row multipliers (m): column `lane` of F, g_t[lane], column lane + 64 q of E
     int fo[NX], fm[NX], eo[NQ][NX], em[NQ][NX], go = 0, gm = 0;
-    auto enc = [&](int code, int& o, int& m) { if (code >= 0) { o = NC + code; m = STRIDE; } else { o = (code == -1) ? 0 : 1 + (-2 - code); m = 0; } };
 #pragma unroll
     for (int k = 0; k < NX; ++k) {
-        enc(lane < NX ? Mdl::path_code(0, k * NX + lane) : -1, fo[k], fm[k]);
+        pool_enc<NC, STRIDE>(lane < NX ? Mdl::path_code(0, k * NX + lane) : -1, fo[k], fm[k]);
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) enc(lane + 64 * q < NP ? Mdl::path_code(1, k * NP + lane + 64 * q) : -1, eo[q][k], em[q][k]);
+        for (int q = 0; q < NQ; ++q) pool_enc<NC, STRIDE>(lane + 64 * q < NP ? Mdl::path_code(1, k * NP + lane + 64 * q) : -1, eo[q][k], em[q][k]);
     }
     if (lane < NX) { go = NC + GX + lane; gm = STRIDE; }
     double acc[NQ];
@@ -97,7 +71,7 @@ __global__ void __launch_bounds__(64) sysid_vjp_kernel(int B, int T, const doubl
             double m_new = blk[go + tl * gm];
 #pragma unroll
             for (int k = 0; k < NX; ++k) {
-                const double lk = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(lam), k), __builtin_amdgcn_readlane(__double2loint(lam), k));
+                const double lk = readlane_f64(lam, k);
                 m_new += blk[fo[k] + tl * fm[k]] * lk;
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) acc[q] += blk[eo[q][k] + tl * em[q][k]] * lk;
@@ -112,7 +86,7 @@ __global__ void __launch_bounds__(64) sysid_vjp_kernel(int B, int T, const doubl
     if (grad_x0 && lane < NX) grad_x0[(int64_t)b * NX + lane] = lam;
 }
 
-// sysid_vjp_kernel with the gradient with respect to the inputs.  The lane-per-step pass also evaluates the `pathu` group (G_t) behind the path entries of its row.  In
+// sysid_vjp_kernel with the gradient with respect to the inputs, on SysidVjpUPool.  The lane-per-step pass also evaluates the `pathu` group (G_t) behind the path entries of its row.  In
 // the sweep a lane owns the columns c = lane + 64 q of the n x (p + m) matrix [E_t | G_t]: c < p accumulates over the horizon as above (same products, same order),
 // p <= c < p + m is one step's G_t' lam_{t+1} - behind the k loop of step tl its lane stores the sum into the row's staging slot and restarts from 0.0 (a select: the
 // products run in every lane).  No read and no product more in the loop than a slot of E columns costs, and nothing on the recursion's chain.  After the chunk's sweep lane
@@ -123,7 +97,8 @@ __global__ void __launch_bounds__(64) sysid_vjp_u_kernel(int B, int T, const dou
                                                           int tb, const double* __restrict__ gx, double* __restrict__ grad_theta, double* __restrict__ grad_x0,
                                                           double* __restrict__ grad_u, int CH) {
     constexpr int NX = Mdl::NX, NU = Mdl::NU, NP = Mdl::NP, NQ = (NP + NU + 63) / 64;
-    constexpr int NC = 1 + Mdl::PATH_NCONST + Mdl::PATHU_NCONST, GX = Mdl::PATH_NVAR + Mdl::PATHU_NVAR, SU = GX + NX, STRIDE = sysid_vjp_u_stride<Mdl>();
+    using Pool = SysidVjpUPool<Mdl>;
+    constexpr int NC = Pool::NC, GX = Pool::GX, SU = Pool::SU, STRIDE = Pool::STRIDE;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double* blk = lds;
     double* pool = blk + NC;
@@ -139,17 +114,16 @@ __global__ void __launch_bounds__(64) sysid_vjp_u_kernel(int B, int T, const dou
     for (int i_ = lane; i_ < Mdl::PATHU_NCONST; i_ += 64) blk[1 + Mdl::PATH_NCONST + i_] = Mdl::pathu_const(i_);
     // per-lane pool offsets (o) and row multipliers (m): column `lane` of F, g_t[lane], column lane + 64 q of [E | G]
     int fo[NX], fm[NX], eo[NQ][NX], em[NQ][NX], go = 0, gm = 0;
-    auto enc = [&](int code, int& o, int& m) { if (code >= 0) { o = NC + code; m = STRIDE; } else { o = (code == -1) ? 0 : 1 + (-2 - code); m = 0; } };
     // a G entry's variable sits behind the path entries of the row, its constant behind the path constants of the block
-    auto encu = [&](int code, int& o, int& m) { enc(code >= 0 ? Mdl::PATH_NVAR + code : (code == -1 ? -1 : code - Mdl::PATH_NCONST), o, m); };
+    auto encu = [&](int code, int& o, int& m) { pool_enc<NC, STRIDE>(code >= 0 ? Mdl::PATH_NVAR + code : (code == -1 ? -1 : code - Mdl::PATH_NCONST), o, m); };
 #pragma unroll
     for (int k = 0; k < NX; ++k) {
-        enc(lane < NX ? Mdl::path_code(0, k * NX + lane) : -1, fo[k], fm[k]);
+        pool_enc<NC, STRIDE>(lane < NX ? Mdl::path_code(0, k * NX + lane) : -1, fo[k], fm[k]);
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int c = lane + 64 * q;
             if (c >= NP && c < NP + NU) encu(Mdl::pathu_code(0, k * NU + (c - NP)), eo[q][k], em[q][k]);
-            else enc(c < NP ? Mdl::path_code(1, k * NP + c) : -1, eo[q][k], em[q][k]);
+            else pool_enc<NC, STRIDE>(c < NP ? Mdl::path_code(1, k * NP + c) : -1, eo[q][k], em[q][k]);
         }
     }
     if (lane < NX) { go = NC + GX + lane; gm = STRIDE; }
@@ -179,7 +153,7 @@ __global__ void __launch_bounds__(64) sysid_vjp_u_kernel(int B, int T, const dou
             double m_new = blk[go + tl * gm];
 #pragma unroll
             for (int k = 0; k < NX; ++k) {
-                const double lk = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(lam), k), __builtin_amdgcn_readlane(__double2loint(lam), k));
+                const double lk = readlane_f64(lam, k);
                 m_new += blk[fo[k] + tl * fm[k]] * lk;
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) acc[q] += blk[eo[q][k] + tl * em[q][k]] * lk;

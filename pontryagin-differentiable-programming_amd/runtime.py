@@ -214,6 +214,13 @@ def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
 
 
+def _shape_of(a):
+    return tuple(int(k) for k in (a.shape if hasattr(a, "shape") else np.shape(a)))
+
+
+SWEEP_POOL_DOUBLES = 2400       # csrc/pdp_sweep_pool.h: the pool of the sweep kernels beyond four trajectories per compute unit
+
+
 def _mat(t, B, time_varying):
     """tensor [B?,T?,r,c] -> PdpMat with zero strides on broadcast axes."""
     if t is None:
@@ -915,15 +922,15 @@ class ModelLib:
         return out
 
     def oc_x0_vjp_rows(self):
-        """Pool rows (time steps per lane-parallel pass) of the initial-state adjoint sweep, oc_x0_vjp_kernel: csrc/pdp_oc_x0_vjp_kernels.h's rule restated (no entry
-        point reports it) - what a 2400-double pool holds of rows of SOLF_NVAR + n m + n + m doubles, made odd, at least 4 and at most 64.  SOLF_NVAR, the number of
+        """Pool rows (time steps per lane-parallel pass) of the initial-state adjoint sweep, oc_x0_vjp_kernel: csrc/pdp_sweep_pool.h's rule restated (no entry
+        point reports it) - what a pool of SWEEP_POOL_DOUBLES holds of rows of SOLF_NVAR + n m + n + m doubles, made odd, at least 4 and at most 64.  SOLF_NVAR, the number of
         variable entries of (F, G), is read from the model's generated header.  The result bits do not depend on the rows: tests place their chunk edges by them."""
         import re
         from . import codegen
         src = open(os.path.join(codegen.GEN_DIR, self.name + ".h")).read()
         nvar = int(re.search(r"\bSOLF_NVAR\s*=\s*(\d+)", src).group(1))
         stride = (nvar + self.n * self.m + self.n + self.m) | 1
-        return min(64, max(4, 2400 // stride))
+        return min(64, max(4, SWEEP_POOL_DOUBLES // stride))
 
     def _warn_materialised(self, T):
         """once per model: the problem is outside the fused kernel's limits and takes the kernel-by-kernel route"""
@@ -1147,22 +1154,34 @@ class ModelLib:
         check(self.lib.pdp_sysid_auxsys_batched(B, T, ptr(x), ptr(u), ptr(th), tb, ptr(F), ptr(E), current_stream_ptr()), "pdp_sysid_auxsys_batched")
         return F, E
 
+    def _check_rollout_shapes(self, who, u, theta, **trajs):
+        """(B, T) of the inputs u [B, T, m] of `who` (sysid_rollout_vjp / sysid_rollout_jvp), after checking them, the [B, T+1, n] arrays `trajs` (by the name the
+        message gives them) and theta; a ValueError otherwise"""
+        su = _shape_of(u)
+        if len(su) != 3 or su[2] != self.m or su[0] < 1 or su[1] < 1:
+            raise ValueError("%s: inputs must be [B, T, %d] with B, T >= 1, got %s" % (who, self.m, su))
+        B, T = su[0], su[1]
+        for name, a in trajs.items():
+            if _shape_of(a) != (B, T + 1, self.n):
+                raise ValueError("%s: %s must be [B, T+1, n] = %s, got %s" % (who, name, (B, T + 1, self.n), _shape_of(a)))
+        if _shape_of(theta) not in ((self.p,), (1, self.p), (B, self.p)):
+            raise ValueError("%s: theta must be [p] or [B, p] with p = %d, B = %d, got %s" % (who, self.p, B, _shape_of(theta)))
+        return B, T
+
+    def _sweep_rows(self, entry, B):
+        """pool rows of a sweep launch for a batch of B on this device, as the library's entry point `entry` reports them"""
+        rows = int(getattr(self.lib, entry)(int(B)))
+        if rows <= 0:
+            raise RuntimeError("%s failed: %s" % (entry, PDP_E.get(rows, rows)))
+        return rows
+
     def sysid_rollout_vjp(self, x, u, theta, grad_x, want_ini=True, want_theta=True, want_inputs=False):
         """The rollout as a vector-Jacobian product (pdp_sysid_rollout_vjp_batched, include/pdp_hip_sysid_vjp.h: the semantics): x [B, T+1, n] the rollout of
         sysid_integrate for u [B, T, m] and theta ([p] or [B, p]), grad_x [B, T+1, n] = dL/dx of any scalar loss L -> dict(grad_theta [B, p] = dL/dtheta per trajectory,
         grad_x0 [B, n] = dL/dx_0), one launch of the adjoint sweep.  want_ini / want_theta = False: that output is not computed.  want_inputs=True: also grad_u [B, T, m] =
         dL/du through the dynamics, from the same launch (pdp_sysid_rollout_vjp_u_batched, include/pdp_hip_sysid_vjp_u.h); without it the call is the one it always was.
         Not all three switches off.  Shape errors are ValueErrors before any launch."""
-        shape = lambda a: tuple(int(k) for k in (a.shape if hasattr(a, "shape") else np.shape(a)))
-        su = shape(u)
-        if len(su) != 3 or su[2] != self.m or su[0] < 1 or su[1] < 1:
-            raise ValueError("sysid_rollout_vjp: inputs must be [B, T, %d] with B, T >= 1, got %s" % (self.m, su))
-        B, T = su[0], su[1]
-        for name, a in (("state_traj", x), ("grad_state", grad_x)):
-            if shape(a) != (B, T + 1, self.n):
-                raise ValueError("sysid_rollout_vjp: %s must be [B, T+1, n] = %s, got %s" % (name, (B, T + 1, self.n), shape(a)))
-        if shape(theta) not in ((self.p,), (1, self.p), (B, self.p)):
-            raise ValueError("sysid_rollout_vjp: theta must be [p] or [B, p] with p = %d, B = %d, got %s" % (self.p, B, shape(theta)))
+        B, T = self._check_rollout_shapes("sysid_rollout_vjp", u, theta, state_traj=x, grad_state=grad_x)
         if not (want_ini or want_theta or want_inputs):
             raise ValueError("sysid_rollout_vjp: want_theta, want_ini and want_inputs are all False - nothing to compute")
         torch = torch_cuda()
@@ -1187,17 +1206,14 @@ class ModelLib:
         """pool rows (time steps per Jacobian pass) of sysid_rollout_vjp's kernel with want_inputs=True for a batch of B on this device, as the library itself decides
         them (pdp_sysid_rollout_vjp_u_rows): the row there also holds the entries of G = df/du and m staging doubles, so the rows beyond four trajectories per
         compute unit are fewer than sysid_vjp_rows' - the chunk edges the tests aim at"""
-        rows = int(self.lib.pdp_sysid_rollout_vjp_u_rows(int(B)))
-        if rows <= 0:
-            raise RuntimeError("pdp_sysid_rollout_vjp_u_rows failed: %s" % PDP_E.get(rows, rows))
-        return rows
+        return self._sweep_rows("pdp_sysid_rollout_vjp_u_rows", B)
 
     def sysid_vjp_rows(self, B, cus):
         """pool rows (time steps per Jacobian pass) of sysid_rollout_vjp's kernel for a batch of B on a chip of `cus` compute units: the host's rule
-        (sysid_vjp_rows, csrc/pdp_sysid_vjp_kernels.h) restated - the chunk edges the tests aim at"""
+        (sysid_vjp_rows_of, csrc/pdp_sweep_pool.h) restated - the chunk edges the tests aim at"""
         if B <= 4 * cus:
             return self.chunk
-        fit = 2400 // ((self.nnz_path + self.n) | 1)
+        fit = SWEEP_POOL_DOUBLES // ((self.nnz_path + self.n) | 1)
         return min(fit, self.chunk) if fit >= 4 else self.chunk
 
     def sysid_rollout_jvp(self, x, u, theta, d_theta=None, d_x0=None, d_u=None):
@@ -1205,23 +1221,15 @@ class ModelLib:
         sysid_integrate for u [B, T, m] and theta ([p] or [B, p]); the direction d_theta ([p]: shared by the batch, or [B, p]), d_x0 [B, n], d_u [B, T, m], each None
         for zero, not all of them -> d_x [B, T+1, n], the tangent of the rollout along it: d_x[t+1] = F_t d_x[t] + E_t d_theta + G_t d_u[t], one launch of the tangent
         sweep.  Without d_u the kernel does not evaluate G = df/du.  Shape errors are ValueErrors before any launch."""
-        shape = lambda a: tuple(int(k) for k in (a.shape if hasattr(a, "shape") else np.shape(a)))
-        su = shape(u)
-        if len(su) != 3 or su[2] != self.m or su[0] < 1 or su[1] < 1:
-            raise ValueError("sysid_rollout_jvp: inputs must be [B, T, %d] with B, T >= 1, got %s" % (self.m, su))
-        B, T = su[0], su[1]
-        if shape(x) != (B, T + 1, self.n):
-            raise ValueError("sysid_rollout_jvp: state_traj must be [B, T+1, n] = %s, got %s" % ((B, T + 1, self.n), shape(x)))
-        if shape(theta) not in ((self.p,), (1, self.p), (B, self.p)):
-            raise ValueError("sysid_rollout_jvp: theta must be [p] or [B, p] with p = %d, B = %d, got %s" % (self.p, B, shape(theta)))
+        B, T = self._check_rollout_shapes("sysid_rollout_jvp", u, theta, state_traj=x)
         if d_theta is None and d_x0 is None and d_u is None:
             raise ValueError("sysid_rollout_jvp: d_theta, d_x0 and d_u are all None - nothing to compute")
-        if d_theta is not None and shape(d_theta) not in ((self.p,), (1, self.p), (B, self.p)):
-            raise ValueError("sysid_rollout_jvp: d_theta must be [p] or [B, p] with p = %d, B = %d, got %s" % (self.p, B, shape(d_theta)))
-        if d_x0 is not None and shape(d_x0) != (B, self.n):
-            raise ValueError("sysid_rollout_jvp: d_x0 must be [B, n] = %s, got %s" % ((B, self.n), shape(d_x0)))
-        if d_u is not None and shape(d_u) != su:
-            raise ValueError("sysid_rollout_jvp: d_u must be [B, T, m] = %s, got %s" % (su, shape(d_u)))
+        if d_theta is not None and _shape_of(d_theta) not in ((self.p,), (1, self.p), (B, self.p)):
+            raise ValueError("sysid_rollout_jvp: d_theta must be [p] or [B, p] with p = %d, B = %d, got %s" % (self.p, B, _shape_of(d_theta)))
+        if d_x0 is not None and _shape_of(d_x0) != (B, self.n):
+            raise ValueError("sysid_rollout_jvp: d_x0 must be [B, n] = %s, got %s" % ((B, self.n), _shape_of(d_x0)))
+        if d_u is not None and _shape_of(d_u) != (B, T, self.m):
+            raise ValueError("sysid_rollout_jvp: d_u must be [B, T, m] = %s, got %s" % ((B, T, self.m), _shape_of(d_u)))
         torch = torch_cuda()
         x, u, th = dev(x), dev(u), dev(theta)
         dth, dx0, du = (None if a is None else dev(a) for a in (d_theta, d_x0, d_u))
@@ -1236,10 +1244,7 @@ class ModelLib:
     def sysid_jvp_rows(self, B):
         """pool rows (time steps per Jacobian pass) of sysid_rollout_jvp's kernel for a batch of B on this device, as the library itself decides them
         (pdp_sysid_rollout_jvp_rows): sysid_vjp_rows' rule on the same row, with or without d_u - the chunk edges the tests aim at"""
-        rows = int(self.lib.pdp_sysid_rollout_jvp_rows(int(B)))
-        if rows <= 0:
-            raise RuntimeError("pdp_sysid_rollout_jvp_rows failed: %s" % PDP_E.get(rows, rows))
-        return rows
+        return self._sweep_rows("pdp_sysid_rollout_jvp_rows", B)
 
     def _sysid_workspace(self, B, T):
         """(workspace tensor or None, its bytes) of the fused SysID.step entry points"""

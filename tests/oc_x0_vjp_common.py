@@ -12,7 +12,7 @@ import numpy as np
 import oc_vjp_common as c
 
 ZOO = ("pendulum", "cartpole", "robotarm", "quadrotor", "rocket")
-# oc_x0_vjp_rows by the rule of csrc/pdp_oc_x0_vjp_kernels.h, worked out by hand: stride = (SOLF_NVAR + n m + n + m) | 1 with SOLF_NVAR = 3, 6, 10, 36, 42 variable
+# oc_x0_vjp_rows by the rule of csrc/pdp_sweep_pool.h, worked out by hand: stride = (SOLF_NVAR + n m + n + m) | 1 with SOLF_NVAR = 3, 6, 10, 36, 42 variable
 # entries of (F, G) -> 9, 15, 25, 105, 97; rows = min(64, max(4, 2400 // stride))
 ROWS = {"pendulum": 64, "cartpole": 64, "robotarm": 64, "quadrotor": 22, "rocket": 24}
 T_MAIN, B_MAIN = 20, 3

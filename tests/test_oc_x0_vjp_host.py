@@ -119,9 +119,12 @@ def test_rows_rule_of_the_five_zoo_models():
         mdl = runtime.ModelLib.__new__(runtime.ModelLib)
         mdl.name, mdl.n, mdl.m = info["name"], info["n"], info["m"]
         assert mdl.oc_x0_vjp_rows() == cx.ROWS[system], system
-    # the kernel header states the same rule
-    src = open(os.path.join(codegen.CSRC, "pdp_oc_x0_vjp_kernels.h")).read()
-    assert "(Mdl::SOLF_NVAR + Mdl::NX * Mdl::NU + Mdl::NX + Mdl::NU) | 1" in src and "2400 / stride < 4 ? 4 : (2400 / stride > 64 ? 64 : 2400 / stride)" in src
+    # the header of the sweep kernels' pool states the same rule
+    src = open(os.path.join(codegen.CSRC, "pdp_sweep_pool.h")).read()
+    assert "struct OcX0VjpPool : SweepPool<Mdl::SOLF_NVAR, Mdl::SOLF_NCONST, Mdl::NX * Mdl::NU + Mdl::NX + Mdl::NU> {" in src
+    assert "static constexpr int STRIDE = (NVAR + TAIL) | 1;" in src and "constexpr int SWEEP_POOL_DOUBLES = 2400;" in src
+    assert "SWEEP_POOL_DOUBLES / stride < 4 ? 4 : (SWEEP_POOL_DOUBLES / stride > 64 ? 64 : SWEEP_POOL_DOUBLES / stride)" in src
+    assert runtime.SWEEP_POOL_DOUBLES == 2400
 
 
 @pytest.mark.parametrize("case", __import__("oc_x0_vjp_common").reference_cases(), ids=lambda cs: "%s_B%d_T%d_%s" % (cs[0], cs[1], cs[2], "per_sample" if cs[3] else "shared"))

@@ -52,10 +52,18 @@ def test_argument_errors_are_returned_before_any_launch():
 def test_the_size_limit_is_a_compile_time_condition_of_the_host_routine():
     """PDP_E_SIZE for n > 64 or p > 512: a model of that size takes far longer to build than a test may, so the condition is read where it is decided"""
     src = open(os.path.join(ROOT, "pontryagin-differentiable-programming_amd", "csrc", "pdp_model.hip")).read()
-    body = src[src.index("int sysid_rollout_vjp("):]
-    body = body[:body.index("\n}\n")]
-    assert "if constexpr (Mdl::NX > 64 || Mdl::NP > 512) return PDP_E_SIZE;" in body
-    assert body.index("return PDP_E_ARG") < body.index("return PDP_E_MODE") < body.index("return PDP_E_SIZE") < body.index("launch(")
+    def body_of(head):
+        body = src[src.index(head):]
+        return body[:body.index("\n}\n")]
+    # the routine: its argument check, then the plan of the sweep launches with the limit as a compile-time argument, then the launch
+    body = body_of("int sysid_rollout_vjp(")
+    assert "sweep_plan<Mdl, SysidVjpPool, sweep_fits_p<Mdl>>(B)" in body
+    assert "template <class Mdl> constexpr bool sweep_fits_p = Mdl::NX <= 64 && Mdl::NP <= 512;" in src
+    assert body.index("return PDP_E_ARG") < body.index("sweep_plan<") < body.index("if constexpr (!pl.ok) return pl.rows;") < body.index("launch(")
+    # the plan: the model kind, then the limit, both compile-time conditions, then the bound on the block
+    plan = body_of("auto sweep_plan(int B)")
+    assert "else if constexpr (!FITS) return SweepPlan<false>{PDP_E_SIZE, 0};" in plan
+    assert plan.index("PDP_E_MODE") < plan.index("if constexpr (!FITS)") < plan.index("150 * 1024") and "PDP_E_ARG" not in plan
     assert "n > 64 or p > 512" in open(os.path.join(ROOT, "include", "pdp_hip_sysid_vjp.h")).read()
 
 
