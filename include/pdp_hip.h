@@ -391,6 +391,25 @@ typedef struct pdp_policy {
     const double* table;     /* TABLE: device memory, [T][n_basis] row-major */
 } pdp_policy;
 
+/* The rollout as a vector-Jacobian product, for any scalar loss L(x_0 .. x_T, u_0 .. u_{T-1}) of a rollout under the policy: pdp_cp_step_batched with
+ * PDP_POLICY_COTANGENT set in pol->kind reads pol as a pdp_policy_cot* and runs the adjoint sweep
+ *     mu_T = gx_T ;  t = T-1 .. 0:  v_t = gu_t + G_t' mu_{t+1} ;  dL/dtheta += (d pi/d theta)(t, x_t)' v_t ;  mu_t = gx_t + F_t' mu_{t+1} + (d pi/dx)(t, x_t)' v_t ;
+ *     dL/dx_0 = mu_0
+ * on the given rollout x (u_t = pi(t, x_t, theta) is re-derived) and no rollout: grad [B][p] = dL/dtheta per trajectory or NULL, grad_x0 [B][n] = dL/dx_0 or NULL, at
+ * least one of them; theta, theta_bstride, p as ever; x0 and the workspace are ignored; loss, x, u of the call must be NULL and x, grad_x, grad_u of the struct
+ * non-NULL - PDP_E_ARG otherwise, before anything is launched.  Limits: n <= 16, m <= 4, PDP_POLICY_POLY (<= 16 pivots) or PDP_POLICY_MLP (<= 8 layers of <= 32
+ * units), p <= 512; PDP_POLICY_TABLE and everything wider is PDP_E_SIZE (the caller contracts forward sensitivities instead: pdp_cp_auxsys_batched,
+ * pdp_cp_aux_integrate_batched, pdp_cp_grad_contract_batched).  Nothing is masked: a non-finite input gives a non-finite row, and that row only.
+ * pdp_cp_integrate_batched, pdp_cp_auxsys_batched and pdp_cp_step_workspace_bytes refuse the bit (PDP_E_ARG; 0 bytes). */
+#define PDP_POLICY_COTANGENT 256      /* bit of pdp_policy.kind: this pdp_policy is the first member of a pdp_policy_cot */
+typedef struct pdp_policy_cot {
+    pdp_policy pol;                   /* kind = PDP_POLICY_POLY or PDP_POLICY_MLP, | PDP_POLICY_COTANGENT */
+    const double* x;                  /* [B][T+1][n]  the rollout, as pdp_cp_integrate_batched left it */
+    const double* grad_x;             /* [B][T+1][n]  dL/dx_t */
+    const double* grad_u;             /* [B][T][m]    dL/du_t */
+    double* grad_x0;                  /* [B][n] or NULL */
+} pdp_policy_cot;
+
 /* ControlPlanning.integrateSys (PDP.py:763-786): x0 [B][n], theta -> x [B][T+1][n], u [B][T][m], cost [B]. */
 int pdp_cp_integrate_batched(int B, int T, const pdp_policy* pol, int p, const double* x0, const double* theta,
                              int theta_bstride, double* x, double* u, double* cost, void* stream);

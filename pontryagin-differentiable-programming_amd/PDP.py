@@ -526,6 +526,14 @@ class ControlPlanning(_CasadiFrontEnd):
         assert hasattr(self, "_policy"), "please set the control policy by running the init_step method first!"
         return self.model().cp_step(self._policy, self.n_auxvar, ini_state, auxvar_value, int(horizon))
 
+    def rollout_vjp_batch(self, state_traj, auxvar_value, grad_state, grad_control, want_theta=True, want_ini=True):
+        """The rollout of integrateSys_batch as a vector-Jacobian product, for any scalar loss L of it: state_traj [B, T+1, n] the rollout for auxvar_value ([p] or
+        [B, p]), grad_state [B, T+1, n] = dL/dx, grad_control [B, T, m] = dL/du -> dict(grad_theta [B, p], grad_x0 [B, n]) (runtime.ModelLib.cp_rollout_vjp: one adjoint
+        sweep; no size is refused).  The policy is the one of setPolyControl / setNeuralPolicy; the table policies of recmat_* / warp_* are served by
+        ModelLib.cp_rollout_vjp with their policy object, not from here."""
+        assert hasattr(self, "_policy"), "please set the control policy by running the init_step method first!"
+        return self.model().cp_rollout_vjp(self._policy, self.n_auxvar, state_traj, auxvar_value, grad_state, grad_control, want_theta=want_theta, want_ini=want_ini)
+
     # ---- reference signatures ---------------------------------------------------------------------------------
     def integrateSys(self, ini_state, horizon, auxvar_value):                   # PDP.py:763-786
         assert hasattr(self, "dyn_fn"), "Set the dynamics first!"

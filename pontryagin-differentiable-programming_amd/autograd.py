@@ -194,3 +194,56 @@ def sysid_trajectory(sid, ini_state, inputs, theta, input_grad=False):
     from . import runtime
     x0, u = (ini_state if torch.is_tensor(ini_state) else runtime.dev(ini_state)), (inputs if input_grad else runtime.dev(inputs))
     return _SysIDTrajectory.apply(theta, x0, u, sid, bool(input_grad))
+
+
+class _CPTrajectory(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, theta, ini_state, cp, horizon):
+        with torch.no_grad():
+            x, u, _ = cp.integrateSys_batch(ini_state.detach(), horizon, theta.detach())
+        need = ctx.needs_input_grad
+        ctx.cp, ctx.shared, ctx.want_theta, ctx.want_ini = cp, theta.dim() == 1, bool(need[0]), bool(need[1])
+        ctx.save_for_backward(x, theta.detach())
+        ctx.set_materialize_grads(False)
+        return x.clone(), u              # (the saved rollout stays as the kernel wrote it whatever the caller does to the output)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_state, grad_control):
+        x, theta = ctx.saved_tensors
+        B, T = x.shape[0], x.shape[1] - 1
+        gx = (torch.zeros_like(x) if grad_state is None else grad_state).to(torch.float64).contiguous()
+        gu = (x.new_zeros((B, T, ctx.cp.n_control)) if grad_control is None else grad_control).to(torch.float64).contiguous()
+        out = ctx.cp.rollout_vjp_batch(x, theta, gx, gu, want_theta=ctx.want_theta, want_ini=ctx.want_ini)
+        gt = out.get("grad_theta")
+        if gt is not None and ctx.shared:
+            gt = gt.sum(dim=0)
+        return gt, out.get("grad_x0"), None, None
+
+
+def cp_trajectory(cp, ini_state, horizon, theta):
+    """Rollouts of the PDP.ControlPlanning `cp` from ini_state [B, n] over `horizon` steps under its policy u_t = pi(t, x_t, theta) (setPolyControl / setNeuralPolicy),
+    differentiable in theta and ini_state: returns (state [B, T+1, n], control [B, T, m]).  Any scalar loss written in torch on them - a waypoint, an obstacle term, a
+    learned critic, a terminal constraint - trains the policy with loss.backward(); ControlPlanning.step knows the model's own cost only.  theta: CUDA fp64 tensor, [p]
+    (one policy shared by the batch: theta.grad is the sum over the batch) or [B, p] (one per sample).  ini_state: an array or a tensor; a CUDA fp64 tensor that
+    requires a gradient gets one (dL/dx_0, state[:, 0]'s own cotangent included).  Forward: ControlPlanning.integrateSys_batch.  Backward: one launch of the adjoint
+    sweep mu_t = dL/dx_t + F_t' mu_{t+1} + (d pi/dx)' v_t, v_t = dL/du_t + G_t' mu_{t+1}, dL/dtheta += (d pi/d theta)' v_t (ControlPlanning.rollout_vjp_batch,
+    pdp_policy_cot in include/pdp_hip.h), which computes exactly the gradients that are needed; a missing cotangent is zeros.  First order
+    only, no forward mode."""
+    if not (torch.is_tensor(theta) and theta.is_cuda and theta.dtype == torch.float64):
+        raise TypeError("cp_trajectory: theta must be a CUDA fp64 tensor ([p] shared, or [B, p] per sample)")
+    if not hasattr(cp, "_policy"):
+        raise ValueError("cp_trajectory: set the control policy first (setPolyControl / setNeuralPolicy / init_step)")
+    if theta.dim() not in (1, 2) or theta.shape[-1] != cp.n_auxvar:
+        raise ValueError("cp_trajectory: theta must be [p] or [B, p] with p = %d, got %s" % (cp.n_auxvar, tuple(theta.shape)))
+    if torch.is_tensor(ini_state) and ini_state.requires_grad and not (ini_state.is_cuda and ini_state.dtype == torch.float64):
+        raise TypeError("cp_trajectory: an ini_state that requires a gradient must be a CUDA fp64 tensor")
+    if int(horizon) < 1:
+        raise ValueError("cp_trajectory: horizon must be at least 1, got %s" % (horizon,))
+    from . import runtime
+    x0 = ini_state if torch.is_tensor(ini_state) else runtime.dev(ini_state)
+    if x0.dim() != 2 or x0.shape[-1] != cp.n_state:
+        raise ValueError("cp_trajectory: ini_state must be [B, n] with n = %d, got %s" % (cp.n_state, tuple(x0.shape)))
+    if theta.dim() == 2 and theta.shape[0] != x0.shape[0]:
+        raise ValueError("cp_trajectory: a per-sample theta must be [B, p] with B = %d, got %s" % (x0.shape[0], tuple(theta.shape)))
+    return _CPTrajectory.apply(theta, x0, cp, int(horizon))

@@ -32,6 +32,7 @@ namespace pdp { extern __device__ long long g_rb_stamp[16]; }
 #include "pdp_sysid_vjp_kernels.h"
 #include "pdp_sysid_jvp_kernels.h"
 #include "pdp_oc_x0_vjp_kernels.h"
+#include "pdp_cp_vjp_kernels.h"
 #include "pdp_launch.h"
 
 using namespace pdp;
@@ -592,6 +593,35 @@ int cp_step(int B, int T, const pdp_policy* pol, int p, const double* x0, const 
     } else { return PDP_E_MODE; }
 }
 
+// pdp_cp_step_batched with PDP_POLICY_COTANGENT (include/pdp_hip.h): the adjoint sweep of pdp_cp_vjp_kernels.h on the rollout the struct names, and no rollout.  The
+// kernel receives the pdp_policy by value with the bit cleared.  Every refusal comes before the launch.  Limits: those of cp_step_adjoint_kernel.
+template <class Mdl>
+int cp_vjp(int B, int T, const pdp_policy_cot* pc, int p, const double* th, int tb, const double* loss, double* grad, const double* x, const double* u, void* st) {
+    if constexpr (Mdl::KIND == PDP_KIND_CP) {
+        if (B <= 0 || T <= 0 || !th || loss || x || u || (!grad && !pc->grad_x0) || !pc->x || !pc->grad_x || !pc->grad_u) return PDP_E_ARG;
+        pdp_policy pol = pc->pol;
+        pol.kind &= ~PDP_POLICY_COTANGENT;
+        if (pol.kind != PDP_POLICY_POLY && pol.kind != PDP_POLICY_MLP && pol.kind != PDP_POLICY_TABLE) return PDP_E_ARG;
+        if constexpr (Mdl::NX <= 16 && Mdl::NU <= 4) {
+            if (pol.kind == PDP_POLICY_TABLE) return PDP_E_SIZE;
+            if (pol.kind == PDP_POLICY_MLP) {
+                const MlpShape net = mlp_shape<Mdl>(pol);
+                if (net.layers < 1 || !net.positive) return PDP_E_ARG;
+                if (net.beyond) return PDP_E_SIZE;
+                if (net.params != p || net.out != Mdl::NU) return PDP_E_ARG;
+            } else if (pol.n_pivots < 1 || pol.n_pivots > 16 || p != pol.n_pivots * Mdl::NU) return PDP_E_ARG;
+            if (p > 512) return PDP_E_SIZE;
+            constexpr int rows = oc_x0_vjp_rows_of(CpVjpPool<Mdl>::STRIDE);
+            const size_t lds = sizeof(double) * (size_t)cp_vjp_layout<Mdl>(p, rows).total;
+            if (lds > 150 * 1024) return PDP_E_SIZE;
+            return launch(cp_vjp_kernel<Mdl>, dim3(B), dim3(64), lds, S(st), B, T, pol, p, pc->x, th, tb, pc->grad_x, pc->grad_u, grad, pc->grad_x0, rows);
+        } else { return PDP_E_SIZE; }
+    } else { return PDP_E_MODE; }
+}
+// the entry points that do not serve a pdp_policy_cot
+inline bool cp_cot(const pdp_policy* pol) { return pol && (pol->kind & PDP_POLICY_COTANGENT) != 0; }
+constexpr int cp_cot_refusal() { return PdpModel::KIND == PDP_KIND_CP ? PDP_E_ARG : PDP_E_MODE; }
+
 template <class Mdl>
 int sysid_integrate(int B, int T, const double* x0, const double* u, const double* th, int tb, double* x, void* st) {
     if constexpr (Mdl::KIND == PDP_KIND_SYSID) {
@@ -813,15 +843,18 @@ int pdp_oc_predict_batched(int B, int T, const double* dtheta, int dtheta_bstrid
 }
 int pdp_cp_integrate_batched(int B, int T, const pdp_policy* pol, int p, const double* x0, const double* theta, int tb, double* x, double* u,
                              double* cost, void* stream) {
+    if (cp_cot(pol)) return cp_cot_refusal();
     return cp_integrate<PdpModel>(B, T, pol, p, x0, theta, tb, x, u, cost, stream);
 }
 int pdp_cp_auxsys_batched(int B, int T, const pdp_policy* pol, int p, const double* x, const double* u, const double* theta, int tb, double* dynF,
                           double* dynG, double* dUx, double* dUe, double* dcx, double* dcu, double* dhx, void* stream) {
+    if (cp_cot(pol)) return cp_cot_refusal();
     return cp_auxsys<PdpModel>(B, T, pol, p, x, u, theta, tb, dynF, dynG, dUx, dUe, dcx, dcu, dhx, stream);
 }
-int64_t pdp_cp_step_workspace_bytes(int B, int T, const pdp_policy* pol, int p) { return cp_step_ws_bytes<PdpModel>(B, T, pol, p); }
+int64_t pdp_cp_step_workspace_bytes(int B, int T, const pdp_policy* pol, int p) { return cp_cot(pol) ? 0 : cp_step_ws_bytes<PdpModel>(B, T, pol, p); }
 int pdp_cp_step_batched(int B, int T, const pdp_policy* pol, int p, const double* x0, const double* theta, int tb, double* loss, double* grad,
                         double* x, double* u, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (cp_cot(pol)) return cp_vjp<PdpModel>(B, T, (const pdp_policy_cot*)pol, p, theta, tb, loss, grad, x, u, stream);
     return cp_step<PdpModel>(B, T, pol, p, x0, theta, tb, loss, grad, x, u, workspace, workspace_bytes, stream);
 }
 int pdp_sysid_integrate_batched(int B, int T, const double* x0, const double* u, const double* theta, int tb, double* x, void* stream) {

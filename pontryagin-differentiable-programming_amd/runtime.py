@@ -12,8 +12,8 @@ import numpy as np
 
 from .abi import (LM_STATES, PDP_E, PDP_E_SIZE, PDP_GRAD_GAUSS_NEWTON, PDP_GRAD_SKIP_MISSING, PDP_MS_FROM_CONTROLS, PDP_MS_NO_RESTORATION,  # noqa: F401
                   PDP_MS_PREDICT, PDP_MS_PREDICT_GUARD, PDP_MS_PREDICT_PRIMAL, PDP_MS_WARM, PDP_MS_WITH_SOC, PDP_MS_WITH_WATCHDOG, PDP_OC_COTANGENT, PDP_OC_GIVEN_TRAJ,
-                  PDP_OC_PACKED, PDP_OC_RECORD_PRIMAL, PDP_POLICY_MLP, PDP_POLICY_POLY, PDP_POLICY_TABLE, PdpLmPrior, PdpLmSchedule, PdpLmState, PdpLqrProblem, PdpMat,
-                  PdpModelInfo, PdpOcAuxsys, PdpOcMsOpts, PdpOcSensOut, PdpOcSolveOpts, PdpPolicy, entry_points)
+                  PDP_OC_PACKED, PDP_OC_RECORD_PRIMAL, PDP_POLICY_COTANGENT, PDP_POLICY_MLP, PDP_POLICY_POLY, PDP_POLICY_TABLE, PdpLmPrior, PdpLmSchedule, PdpLmState, PdpLqrProblem, PdpMat,
+                  PdpModelInfo, PdpOcAuxsys, PdpOcMsOpts, PdpOcSensOut, PdpOcSolveOpts, PdpPolicy, PdpPolicyCot, entry_points)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
@@ -1133,6 +1133,82 @@ class ModelLib:
         check(lib.pdp_cp_grad_contract_batched(B, int(T), self.n, self.m, p, ptr(aux["dcx"]), ptr(aux["dcu"]), ptr(aux["dhx"]), ptr(X), ptr(U),
                                                ptr(grad), current_stream_ptr()), "pdp_cp_grad_contract_batched")
         return (loss, grad, x, u) if want_traj else (loss, grad)
+
+    def cp_vjp_rows(self):
+        """Pool rows (time steps per lane-parallel pass) of the ControlPlanning adjoint sweep, cp_vjp_kernel: csrc/pdp_sweep_pool.h's rule restated (no entry point
+        reports it) - what a pool of SWEEP_POOL_DOUBLES holds of rows of PATH_NVAR + n + m + max(n + m, 16) doubles, made odd, at least 4 and at most 64.  PATH_NVAR, the number of
+        variable entries of the `path` group, is read from the model's generated header.  The result bits do not depend on the rows: tests place their chunk edges by
+        them."""
+        import re
+        from . import codegen
+        src = open(os.path.join(codegen.GEN_DIR, self.name + ".h")).read()
+        nvar = int(re.search(r"\bPATH_NVAR\s*=\s*(\d+)", src).group(1))
+        stride = (nvar + self.n + self.m + max(self.n + self.m, 16)) | 1
+        return min(64, max(4, SWEEP_POOL_DOUBLES // stride))
+
+    def cp_rollout_vjp(self, pol, p, x, theta, grad_x, grad_u, want_theta=True, want_ini=True, force_materialised=False):
+        """The rollout under a policy as a vector-Jacobian product (pdp_cp_step_batched with a pdp_policy_cot, include/pdp_hip.h: the semantics): x [B, T+1, n] the
+        rollout of cp_integrate for theta ([p] or [B, p]), grad_x [B, T+1, n] = dL/dx, grad_u [B, T, m] = dL/du of any scalar loss L -> dict(grad_theta [B, p] = dL/dtheta
+        per trajectory, grad_x0 [B, n] = dL/dx_0), one launch of the adjoint sweep.  want_theta / want_ini = False: that output is not computed.  Beyond the sweep's limits
+        (PDP_E_SIZE: a table policy, n > 16, m > 4, p > 512, a network of more than 8 layers or 32 units) the forward sensitivities are materialised and contracted:
+        no size is refused.  force_materialised: that route whatever the size (probes, tests).  Shape errors are ValueErrors before any foreign call."""
+        sx, sg, su = _shape_of(x), _shape_of(grad_x), _shape_of(grad_u)
+        if len(sx) != 3 or sx[2] != self.n or sx[0] < 1 or sx[1] < 2:
+            raise ValueError("cp_rollout_vjp: state_traj must be [B, T+1, %d] with B, T >= 1, got %s" % (self.n, sx))
+        B, T = sx[0], sx[1] - 1
+        if sg != sx:
+            raise ValueError("cp_rollout_vjp: grad_state must be [B, T+1, n] = %s, got %s" % (sx, sg))
+        if su != (B, T, self.m):
+            raise ValueError("cp_rollout_vjp: grad_control must be [B, T, m] = %s, got %s" % ((B, T, self.m), su))
+        p = int(p)
+        if _shape_of(theta) not in ((p,), (1, p), (B, p)):
+            raise ValueError("cp_rollout_vjp: theta must be [p] or [B, p] with p = %d, B = %d, got %s" % (p, B, _shape_of(theta)))
+        if not (want_theta or want_ini):
+            raise ValueError("cp_rollout_vjp: want_theta and want_ini are both False - nothing to compute")
+        torch = torch_cuda()
+        x, gx, gu = dev(x), dev(grad_x), dev(grad_u)
+        th, tb = self._theta(theta, B, p)
+        out = {}
+        if want_theta:
+            out["grad_theta"] = torch.empty((B, p), dtype=torch.float64, device="cuda")
+        if want_ini:
+            out["grad_x0"] = torch.empty((B, self.n), dtype=torch.float64, device="cuda")
+        rc = PDP_E_SIZE
+        if not force_materialised:
+            cot = PdpPolicyCot()
+            C.memmove(C.byref(cot.pol), C.byref(pol), C.sizeof(PdpPolicy))
+            cot.pol.kind = pol.kind | PDP_POLICY_COTANGENT
+            cot.x, cot.grad_x, cot.grad_u = x.data_ptr(), gx.data_ptr(), gu.data_ptr()
+            cot.grad_x0 = out["grad_x0"].data_ptr() if want_ini else None
+            rc = self.lib.pdp_cp_step_batched(B, T, C.cast(C.byref(cot), C.POINTER(PdpPolicy)), p, None, ptr(th), tb, None, ptr(out.get("grad_theta")), None, None, None, 0,
+                                              current_stream_ptr())
+        if rc == PDP_E_SIZE:
+            self._cp_rollout_vjp_materialised(pol, p, x, th, gx, gu, out)
+            rc = 0
+        check(rc, "pdp_cp_step_batched (PDP_POLICY_COTANGENT)")
+        return out
+
+    def _cp_rollout_vjp_materialised(self, pol, p, x, th, gx, gu, out):
+        """cp_rollout_vjp through the materialised kernels: getAuxSys -> integrateAuxSys (forward sensitivities; for dL/dx_0 n further columns, zero in dUe, from
+        X_0 = [0 | I]) -> the chain rule with the cotangents in the places of c_x, c_u, h_x"""
+        torch = torch_cuda()
+        B, T, n = x.shape[0], x.shape[1] - 1, self.n
+        u = self.cp_integrate_T(pol, p, x[:, 0].contiguous(), th, T)[1]         # u_t = pi(t, x_t, theta) along the given rollout: x is that rollout
+        aux = self.cp_auxsys(pol, p, x, u, th, want_cost_grads=False)
+        dUe, X0, w = aux["dUe"], None, p
+        if "grad_x0" in out:
+            w = p + n
+            dUe = torch.cat([dUe, dUe.new_zeros((B, T, self.m, n))], dim=-1).contiguous()
+            X0 = torch.cat([x.new_zeros((n, p)), torch.eye(n, dtype=torch.float64, device="cuda")], dim=1).expand(B, n, w).contiguous()
+        X, U = cp_aux_integrate(aux["dynF"], aux["dynG"], aux["dUx"], dUe, X0)
+        g = torch.empty((B, w), dtype=torch.float64, device="cuda")
+        gx_path, gx_fin = gx[:, :T].contiguous(), gx[:, T].contiguous()          # (named: they must outlive the launch)
+        check(load_core().pdp_cp_grad_contract_batched(B, T, n, self.m, w, ptr(gx_path), ptr(gu), ptr(gx_fin), ptr(X), ptr(U), ptr(g), current_stream_ptr()),
+              "pdp_cp_grad_contract_batched")
+        if "grad_theta" in out:
+            out["grad_theta"].copy_(g[:, :p])
+        if "grad_x0" in out:
+            out["grad_x0"].copy_(g[:, p:])
 
     # -- SysID
     def sysid_integrate(self, x0, u, theta):
