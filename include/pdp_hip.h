@@ -410,6 +410,28 @@ typedef struct pdp_policy_cot {
     double* grad_x0;                  /* [B][n] or NULL */
 } pdp_policy_cot;
 
+/* The rollout as a Jacobian-vector product, the other half of the above: pdp_cp_step_batched with PDP_POLICY_TANGENT set in pol->kind reads pol as a pdp_policy_tan*
+ * and runs the tangent sweep along the direction (d_theta, d_x0)
+ *     dx_0 = d_x0 ;  t = 0 .. T-1:  du_t = (d pi/dx)(t, x_t) dx_t + (d pi/d theta)(t, x_t) d_theta ;  dx_{t+1} = F_t dx_t + G_t du_t
+ * on the given rollout x AND its controls u (both as pdp_cp_integrate_batched left them: nothing is re-derived) and no rollout: d_x [B][T+1][n] and, unless NULL,
+ * d_u [B][T][m] are written in full.  d_theta [p] per trajectory with the batch stride d_theta_bstride (0: one [p] shared by the batch) or NULL, d_x0 [B][n] or NULL -
+ * a NULL tangent reads as +0.0, at least one of them is given.  theta, theta_bstride, p as ever; x0 and the workspace are ignored; loss, grad, x, u of the call must be
+ * NULL and x, u, d_x of the struct non-NULL, and PDP_POLICY_COTANGENT not set beside it - PDP_E_ARG otherwise, before anything is launched.  Limits, PDP_E_SIZE and the
+ * refusals of the other entry points: those of pdp_policy_cot (the caller integrates one column of the forward sensitivities instead: pdp_cp_auxsys_batched,
+ * pdp_cp_aux_integrate_batched).  Nothing is masked: a non-finite input reaches its own trajectory only.  A Gauss-Newton product J' J v of any residual of the rollout
+ * is this call followed by the cotangent call: two sweeps on one saved rollout, whatever p is. */
+#define PDP_POLICY_TANGENT 512        /* bit of pdp_policy.kind: this pdp_policy is the first member of a pdp_policy_tan */
+typedef struct pdp_policy_tan {
+    pdp_policy pol;                   /* kind = PDP_POLICY_POLY or PDP_POLICY_MLP, | PDP_POLICY_TANGENT */
+    const double* x;                  /* [B][T+1][n]  the rollout, as pdp_cp_integrate_batched left it */
+    const double* u;                  /* [B][T][m]    its controls */
+    const double* d_theta;            /* [p] or [B][p], or NULL */
+    int d_theta_bstride;              /* 0 (shared) or p */
+    const double* d_x0;               /* [B][n] or NULL */
+    double* d_x;                      /* [B][T+1][n] */
+    double* d_u;                      /* [B][T][m] or NULL */
+} pdp_policy_tan;
+
 /* ControlPlanning.integrateSys (PDP.py:763-786): x0 [B][n], theta -> x [B][T+1][n], u [B][T][m], cost [B]. */
 int pdp_cp_integrate_batched(int B, int T, const pdp_policy* pol, int p, const double* x0, const double* theta,
                              int theta_bstride, double* x, double* u, double* cost, void* stream);

@@ -534,6 +534,16 @@ class ControlPlanning(_CasadiFrontEnd):
         assert hasattr(self, "_policy"), "please set the control policy by running the init_step method first!"
         return self.model().cp_rollout_vjp(self._policy, self.n_auxvar, state_traj, auxvar_value, grad_state, grad_control, want_theta=want_theta, want_ini=want_ini)
 
+    def rollout_jvp_batch(self, state_traj, control_traj, auxvar_value, d_auxvar=None, d_ini_state=None):
+        """The tangent of the rollouts (state_traj [B, T+1, n], control_traj [B, T, m]) = integrateSys_batch(ini_state, horizon, auxvar_value) along a direction:
+        d_auxvar ([p]: shared by the batch, or [B, p]) and d_ini_state [B, n], each None for zero (not both) -> dict(d_state [B, T+1, n], d_control [B, T, m]) = J v
+        by the tangent sweep d_u[t] = pi_x d_x[t] + pi_theta d_auxvar, d_x[t+1] = F_t d_x[t] + G_t d_u[t] in one launch (runtime.ModelLib.cp_rollout_jvp; no size is
+        refused) - the other half of rollout_vjp_batch: a Gauss-Newton product J' J v of any residual of the rollout is this call followed by that one.
+        pdp_amd.autograd.cp_trajectory uses it for torch.autograd.forward_ad, pdp_amd.irl.MatrixFreeLM.for_cp for Levenberg-Marquardt with a conjugate-gradient
+        inner solve.  The policy is the one of setPolyControl / setNeuralPolicy."""
+        assert hasattr(self, "_policy"), "please set the control policy by running the init_step method first!"
+        return self.model().cp_rollout_jvp(self._policy, self.n_auxvar, state_traj, control_traj, auxvar_value, d_theta=d_auxvar, d_x0=d_ini_state)
+
     # ---- reference signatures ---------------------------------------------------------------------------------
     def integrateSys(self, ini_state, horizon, auxvar_value):                   # PDP.py:763-786
         assert hasattr(self, "dyn_fn"), "Set the dynamics first!"

@@ -61,6 +61,11 @@ class PdpPolicyCot(C.Structure):                   # pdp_policy.kind | PDP_POLIC
     _fields_ = [("pol", PdpPolicy), ("x", C.c_void_p), ("grad_x", C.c_void_p), ("grad_u", C.c_void_p), ("grad_x0", C.c_void_p)]
 
 
+class PdpPolicyTan(C.Structure):                   # pdp_policy.kind | PDP_POLICY_TANGENT: pdp_cp_step_batched reads its policy argument as this
+    _fields_ = [("pol", PdpPolicy), ("x", C.c_void_p), ("u", C.c_void_p), ("d_theta", C.c_void_p), ("d_theta_bstride", C.c_int), ("d_x0", C.c_void_p),
+                ("d_x", C.c_void_p), ("d_u", C.c_void_p)]
+
+
 # ---- constants: every integer-valued #define PDP_* of include/*.h, under the header's name -------------------------------------------------------------------------
 PDP_E_ARG, PDP_E_SIZE, PDP_E_LAUNCH, PDP_E_MODE = -1, -2, -3, -4                                # return codes
 PDP_STATUS_NONFINITE, PDP_STATUS_PIVOT, PDP_STATUS_INDEFINITE = 1, 2, 256                       # status [B] of the LQR solve and the gradient units
@@ -76,6 +81,7 @@ PDP_OC_GIVEN_TRAJ, PDP_OC_PACKED, PDP_OC_RECORD_PRIMAL, PDP_OC_COTANGENT = 1, 2,
 PDP_GRAD_GAUSS_NEWTON, PDP_GRAD_SKIP_MISSING = 16, 32
 PDP_POLICY_POLY, PDP_POLICY_MLP, PDP_POLICY_TABLE = 0, 1, 2                                     # pdp_policy.kind
 PDP_POLICY_COTANGENT = 256                                                                      # bit of pdp_policy.kind: the struct is the head of a pdp_policy_cot
+PDP_POLICY_TANGENT = 512                                                                        # bit of pdp_policy.kind: the struct is the head of a pdp_policy_tan
 PDP_LM_START, PDP_LM_ACTIVE, PDP_LM_CONVERGED, PDP_LM_STALLED, PDP_LM_BUDGET, PDP_LM_FAILED = 0, 1, 2, 3, 4, 5      # pdp_lm_state.state (include/pdp_hip_lm.h)
 
 PDP_E = {PDP_E_ARG: "PDP_E_ARG (null pointer / bad size)", PDP_E_SIZE: "PDP_E_SIZE (dimension outside kernel limits)",

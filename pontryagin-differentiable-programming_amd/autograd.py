@@ -204,13 +204,15 @@ class _CPTrajectory(torch.autograd.Function):
         need = ctx.needs_input_grad
         ctx.cp, ctx.shared, ctx.want_theta, ctx.want_ini = cp, theta.dim() == 1, bool(need[0]), bool(need[1])
         ctx.save_for_backward(x, theta.detach())
-        ctx.set_materialize_grads(False)
-        return x.clone(), u              # (the saved rollout stays as the kernel wrote it whatever the caller does to the output)
+        ctx.save_for_forward(x, u, theta.detach())                          # (what jvp reads: forward-mode differentiation takes the controls as given)
+        ctx.set_materialize_grads(False)     # (and in jvp an input without a tangent arrives as None, not as a tensor of zeros)
+        return x.clone(), u.clone()              # (the saved rollout stays as the kernel wrote it whatever the caller does to the output)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_state, grad_control):
-        x, theta = ctx.saved_tensors
+        saved = ctx.saved_tensors
+        x, theta = saved[0], saved[-1]
         B, T = x.shape[0], x.shape[1] - 1
         gx = (torch.zeros_like(x) if grad_state is None else grad_state).to(torch.float64).contiguous()
         gu = (x.new_zeros((B, T, ctx.cp.n_control)) if grad_control is None else grad_control).to(torch.float64).contiguous()
@@ -220,6 +222,14 @@ class _CPTrajectory(torch.autograd.Function):
             gt = gt.sum(dim=0)
         return gt, out.get("grad_x0"), None, None
 
+    @staticmethod
+    def jvp(ctx, d_theta, d_ini_state, _cp, _horizon):
+        """forward mode (torch.autograd.forward_ad): the tangents of (state, control) along the tangents of theta ([p] or [B, p]) and ini_state, None where an input
+        carries none: one launch of the tangent sweep"""
+        x, u, theta = ctx.saved_tensors
+        out = ctx.cp.rollout_jvp_batch(x, u, theta, d_auxvar=d_theta, d_ini_state=d_ini_state)
+        return out["d_state"], out["d_control"]
+
 
 def cp_trajectory(cp, ini_state, horizon, theta):
     """Rollouts of the PDP.ControlPlanning `cp` from ini_state [B, n] over `horizon` steps under its policy u_t = pi(t, x_t, theta) (setPolyControl / setNeuralPolicy),
@@ -228,8 +238,10 @@ def cp_trajectory(cp, ini_state, horizon, theta):
     (one policy shared by the batch: theta.grad is the sum over the batch) or [B, p] (one per sample).  ini_state: an array or a tensor; a CUDA fp64 tensor that
     requires a gradient gets one (dL/dx_0, state[:, 0]'s own cotangent included).  Forward: ControlPlanning.integrateSys_batch.  Backward: one launch of the adjoint
     sweep mu_t = dL/dx_t + F_t' mu_{t+1} + (d pi/dx)' v_t, v_t = dL/du_t + G_t' mu_{t+1}, dL/dtheta += (d pi/d theta)' v_t (ControlPlanning.rollout_vjp_batch,
-    pdp_policy_cot in include/pdp_hip.h), which computes exactly the gradients that are needed; a missing cotangent is zeros.  First order
-    only, no forward mode."""
+    pdp_policy_cot in include/pdp_hip.h), which computes exactly the gradients that are needed; a missing cotangent is zeros.  Forward
+    mode: with torch.autograd.forward_ad dual tensors for theta and / or ini_state the tangents of (state, control) are one launch of the tangent sweep
+    du_t = pi_x dx_t + pi_theta d_theta, dx_{t+1} = F_t dx_t + G_t du_t on the saved rollout (ControlPlanning.rollout_jvp_batch, pdp_policy_tan in include/pdp_hip.h,
+    DESIGN.md section 4.1p).  First order only; torch.func transforms are out of scope."""
     if not (torch.is_tensor(theta) and theta.is_cuda and theta.dtype == torch.float64):
         raise TypeError("cp_trajectory: theta must be a CUDA fp64 tensor ([p] shared, or [B, p] per sample)")
     if not hasattr(cp, "_policy"):

@@ -33,6 +33,7 @@ namespace pdp { extern __device__ long long g_rb_stamp[16]; }
 #include "pdp_sysid_jvp_kernels.h"
 #include "pdp_oc_x0_vjp_kernels.h"
 #include "pdp_cp_vjp_kernels.h"
+#include "pdp_cp_jvp_kernels.h"
 #include "pdp_launch.h"
 
 using namespace pdp;
@@ -618,8 +619,35 @@ int cp_vjp(int B, int T, const pdp_policy_cot* pc, int p, const double* th, int 
         } else { return PDP_E_SIZE; }
     } else { return PDP_E_MODE; }
 }
-// the entry points that do not serve a pdp_policy_cot
-inline bool cp_cot(const pdp_policy* pol) { return pol && (pol->kind & PDP_POLICY_COTANGENT) != 0; }
+// pdp_cp_step_batched with PDP_POLICY_TANGENT (include/pdp_hip.h): the tangent sweep of pdp_cp_jvp_kernels.h on the rollout and the controls the struct names, and no
+// rollout.  As above: the pdp_policy by value with the bit cleared, every refusal before the launch, the limits of cp_step_adjoint_kernel.
+template <class Mdl>
+int cp_jvp(int B, int T, const pdp_policy_tan* pt, int p, const double* th, int tb, const double* loss, const double* grad, const double* x, const double* u, void* st) {
+    if constexpr (Mdl::KIND == PDP_KIND_CP) {
+        if (B <= 0 || T <= 0 || !th || loss || grad || x || u || (!pt->d_theta && !pt->d_x0) || !pt->x || !pt->u || !pt->d_x) return PDP_E_ARG;
+        if (pt->d_theta && pt->d_theta_bstride != 0 && pt->d_theta_bstride != p) return PDP_E_ARG;
+        pdp_policy pol = pt->pol;
+        pol.kind &= ~PDP_POLICY_TANGENT;                                   // (with PDP_POLICY_COTANGENT beside it what is left is no policy kind)
+        if (pol.kind != PDP_POLICY_POLY && pol.kind != PDP_POLICY_MLP && pol.kind != PDP_POLICY_TABLE) return PDP_E_ARG;
+        if constexpr (Mdl::NX <= 16 && Mdl::NU <= 4) {
+            if (pol.kind == PDP_POLICY_TABLE) return PDP_E_SIZE;
+            if (pol.kind == PDP_POLICY_MLP) {
+                const MlpShape net = mlp_shape<Mdl>(pol);
+                if (net.layers < 1 || !net.positive) return PDP_E_ARG;
+                if (net.beyond) return PDP_E_SIZE;
+                if (net.params != p || net.out != Mdl::NU) return PDP_E_ARG;
+            } else if (pol.n_pivots < 1 || pol.n_pivots > 16 || p != pol.n_pivots * Mdl::NU) return PDP_E_ARG;
+            if (p > 512) return PDP_E_SIZE;
+            constexpr int rows = oc_x0_vjp_rows_of(CpJvpPool<Mdl>::STRIDE);
+            const size_t lds = sizeof(double) * (size_t)cp_jvp_layout<Mdl>(p, rows).total;
+            if (lds > 150 * 1024) return PDP_E_SIZE;
+            return launch(cp_jvp_kernel<Mdl>, dim3(B), dim3(64), lds, S(st), B, T, pol, p, pt->x, pt->u, th, tb, pt->d_theta, pt->d_theta_bstride, pt->d_x0, pt->d_x,
+                          pt->d_u, rows);
+        } else { return PDP_E_SIZE; }
+    } else { return PDP_E_MODE; }
+}
+// the entry points that serve neither a pdp_policy_cot nor a pdp_policy_tan
+inline bool cp_cot(const pdp_policy* pol) { return pol && (pol->kind & (PDP_POLICY_COTANGENT | PDP_POLICY_TANGENT)) != 0; }
 constexpr int cp_cot_refusal() { return PdpModel::KIND == PDP_KIND_CP ? PDP_E_ARG : PDP_E_MODE; }
 
 template <class Mdl>
@@ -854,6 +882,7 @@ int pdp_cp_auxsys_batched(int B, int T, const pdp_policy* pol, int p, const doub
 int64_t pdp_cp_step_workspace_bytes(int B, int T, const pdp_policy* pol, int p) { return cp_cot(pol) ? 0 : cp_step_ws_bytes<PdpModel>(B, T, pol, p); }
 int pdp_cp_step_batched(int B, int T, const pdp_policy* pol, int p, const double* x0, const double* theta, int tb, double* loss, double* grad,
                         double* x, double* u, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (pol && (pol->kind & PDP_POLICY_TANGENT)) return cp_jvp<PdpModel>(B, T, (const pdp_policy_tan*)pol, p, theta, tb, loss, grad, x, u, stream);
     if (cp_cot(pol)) return cp_vjp<PdpModel>(B, T, (const pdp_policy_cot*)pol, p, theta, tb, loss, grad, x, u, stream);
     return cp_step<PdpModel>(B, T, pol, p, x0, theta, tb, loss, grad, x, u, workspace, workspace_bytes, stream);
 }

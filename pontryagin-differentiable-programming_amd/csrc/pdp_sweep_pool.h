@@ -1,5 +1,5 @@
 // pdp_sweep_pool.h - what the rollout sweep kernels share: sysid_vjp_kernel, sysid_vjp_u_kernel (pdp_sysid_vjp_kernels.h), sysid_jvp_kernel (pdp_sysid_jvp_kernels.h),
-// oc_x0_vjp_kernel (pdp_oc_x0_vjp_kernels.h), cp_vjp_kernel (pdp_cp_vjp_kernels.h) and, for pool_enc alone, cp_step_adjoint_kernel (pdp_model_kernels.h).  One wavefront per trajectory on a given rollout;
+// oc_x0_vjp_kernel (pdp_oc_x0_vjp_kernels.h), cp_vjp_kernel (pdp_cp_vjp_kernels.h), cp_jvp_kernel (pdp_cp_jvp_kernels.h) and, for pool_enc alone, cp_step_adjoint_kernel (pdp_model_kernels.h).  One wavefront per trajectory on a given rollout;
 // the horizon is cut into chunks of equal length <= rows; per chunk a lane-per-step pass packs the step's Jacobian entries into a pool row, then a serial sweep reads
 // the rows through per-lane (offset, multiplier) pairs and broadcasts the carried vector with readlane_f64 (pdp_tile.h).  Shared here: the layout of the LDS block, the
 // rule for its rows and the offset code.  Written out in every kernel, because a shared spelling did not keep their instructions: the chunk
@@ -41,10 +41,16 @@ template <class Mdl>
 struct CpVjpPool : SweepPool<Mdl::PATH_NVAR, Mdl::PATH_NCONST, Mdl::NX + Mdl::NU + (Mdl::NX + Mdl::NU > 16 ? Mdl::NX + Mdl::NU : 16)> {
     static constexpr int GXO = Mdl::PATH_NVAR, GUO = GXO + Mdl::NX, XO = GUO + Mdl::NU, UO = XO + Mdl::NX, BO = XO;
 };
+// cp_jvp_kernel: the entries of the `path` group (as above) | XO: x_t [NX], the input of an MLP policy's pass at step t | DUO: du_t [NU] of a Lagrange policy, which
+// does not depend on the recursion and is summed by the lane that evaluates the step (an MLP policy's du_t never reaches the row).  Rows: oc_x0_vjp_rows_of.
+template <class Mdl>
+struct CpJvpPool : SweepPool<Mdl::PATH_NVAR, Mdl::PATH_NCONST, Mdl::NX + Mdl::NU> {
+    static constexpr int XO = Mdl::PATH_NVAR, DUO = XO + Mdl::NX;
+};
 
 // Pool rows (time steps per lane-parallel Jacobian pass).  A pool of at most SWEEP_POOL_DOUBLES (18.75 KB: with the constants and the allocation granularity an
 // eighth of the CU's 160 KB) leaves two workgroups per SIMD resident, which fill each other's waits.  Both rules read the row stride alone, so Python restates them
-// (runtime.ModelLib.sysid_vjp_rows, .oc_x0_vjp_rows, .cp_vjp_rows).  The result bits do not depend on the rows: a sweep visits the steps in the same order whatever the pass they
+// (runtime.ModelLib.sysid_vjp_rows, .oc_x0_vjp_rows, .cp_vjp_rows, .cp_jvp_rows).  The result bits do not depend on the rows: a sweep visits the steps in the same order whatever the pass they
 // were evaluated in.
 constexpr int SWEEP_POOL_DOUBLES = 2400;
 // the SysID sweeps: the generated CHUNK while a CU holds at most one trajectory per SIMD; a larger batch what the pool holds, if that is at least 4 rows (the rule of
@@ -54,7 +60,7 @@ inline int sysid_vjp_rows_of(int B, int cus, int stride, int chunk) {
     const int fit = SWEEP_POOL_DOUBLES / stride;
     return fit >= 4 ? (fit < chunk ? fit : chunk) : chunk;
 }
-// oc_x0_vjp_kernel and cp_vjp_kernel, whatever the batch: what the pool holds, at least 4 and at most 64 (a lane per step)
+// oc_x0_vjp_kernel, cp_vjp_kernel and cp_jvp_kernel, whatever the batch: what the pool holds, at least 4 and at most 64 (a lane per step)
 constexpr int oc_x0_vjp_rows_of(int stride) { return SWEEP_POOL_DOUBLES / stride < 4 ? 4 : (SWEEP_POOL_DOUBLES / stride > 64 ? 64 : SWEEP_POOL_DOUBLES / stride); }
 
 // the (offset, multiplier) pair of a group's code (Mdl::path_code and its like): >= 0 a variable slot, -1 a structural zero, -2 - i constant i

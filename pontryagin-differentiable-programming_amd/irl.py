@@ -870,7 +870,8 @@ class MatrixFreeLM:
     (G + lam I) s = J' r / B by conjugate gradients, written in torch on the device, from s = 0 to a relative residual of cg_tol or cg_max iterations (None: 2 p).
     Plain lam I damping: matrix-free there is no diag G, so Marquardt's scaling (lm_step's lam diag G) is not available - scale the parameters where their
     magnitudes differ by orders.  The accept / reject / lam schedule and the keys of run() are LMLoop's, and `cg_iterations` (all inner iterations so far).
-    Out of scope: per-recording initial states, priors, covariance, process groups, Huber."""
+    Out of scope: per-recording initial states, priors, covariance, process groups, Huber.  MatrixFreeLM.for_cp builds the same loop for the policy of a
+    PDP.ControlPlanning, with residual(state, control): the loop reaches its model through a small adapter (rollout, J v, J' w) whose default is the SysID one."""
 
     def __init__(self, sid, ini_state, inputs, theta0, residual, lam0=1e-3, up=10.0, down=10.0, lam_min=1e-12, lam_max=1e8, cg_tol=1e-8, cg_max=None):
         shape = lambda a: tuple(int(k) for k in (a.shape if hasattr(a, "shape") else np.shape(a)))
@@ -885,12 +886,17 @@ class MatrixFreeLM:
             raise ValueError("MatrixFreeLM: p = %d is beyond the rollout's jvp / vjp kernels (p <= 512)" % p)
         if not callable(residual):
             raise ValueError("MatrixFreeLM: residual must be a function of the rollouts [B, T+1, n]")
-        self.sid, self.residual, self.B, self.p = sid, residual, su[0], p
-        self.x0, self.u = rt.dev(ini_state), rt.dev(inputs)
+        self.sid, self.x0, self.u = sid, rt.dev(ini_state), rt.dev(inputs)
+        self._setup(_SysIDSweeps(sid, self.x0, self.u), su[0], p, theta0, residual, lam0, up, down, lam_min, lam_max, cg_tol, cg_max)
+
+    def _setup(self, sweeps, B, p, theta0, residual, lam0, up, down, lam_min, lam_max, cg_tol, cg_max):
+        """the loop's state; `sweeps` is what it reaches the model through: rollout(theta) -> the tuple of tensors the residual takes, jv(traj, theta, v) -> their
+        tangents along v [p], jt(traj, theta, cotangents) -> J' of them, summed over the batch"""
+        self.sweeps, self.residual, self.B, self.p = sweeps, residual, B, p
         self.theta = rt.dev(theta0).reshape(p).clone()
         self.lam, self.up, self.down, self.lam_min, self.lam_max = float(lam0), float(up), float(down), float(lam_min), float(lam_max)
         self.cg_tol, self.cg_max = float(cg_tol), int(2 * p if cg_max is None else cg_max)
-        self.current = None                     # (loss, g = J'r / B, the rollout, residual's vjp at it) at self.theta
+        self.current = None                     # (loss, g = J'r / B, the rollout (a tuple), residual's vjp at it) at self.theta
         self.evaluations = self.rejected = self.cg_iterations = 0
         self.stalled = False
         self.loss_trace, self.parameter_trace, self.lambda_trace = [], [], []
@@ -900,27 +906,26 @@ class MatrixFreeLM:
         import torch
         self.evaluations += 1
         with torch.no_grad():
-            x = self.sid.integrateDyn_batch(self.x0, self.u, theta)
-        r, back = torch.func.vjp(self.residual, x)
+            traj = self.sweeps.rollout(theta)
+        r, back = torch.func.vjp(self.residual, *traj)
         loss = float((r.detach() ** 2).sum()) / self.B
         if not np.isfinite(loss):
             return None
-        g = self._jt(x, theta, back(r.detach())[0])
-        return loss, g, x, back
+        g = self._jt(traj, theta, back(r.detach()))
+        return loss, g, traj, back
 
-    def _jt(self, x, theta, w):
-        """J' of the rollout on a cotangent of the states, summed over the batch, / B"""
-        return self.sid.rollout_vjp_batch(x, self.u, theta, w.detach().contiguous(), want_ini=False)["grad_theta"].sum(dim=0) / self.B
+    def _jt(self, traj, theta, w):
+        """J' of the rollout on the cotangents of what the residual takes, summed over the batch, / B"""
+        return self.sweeps.jt(traj, theta, w) / self.B
 
     def gauss_newton_product(self, v):
         """G v = J' J v / B at the accepted point, v [p] on the device: rollout_jvp -> J_h -> J_h' -> rollout_vjp"""
         import torch
         if self.current is None:
             self.start()
-        _, _, x, back = self.current
-        dx = self.sid.rollout_jvp_batch(x, self.u, self.theta, d_auxvar=v)
-        jv = torch.func.jvp(self.residual, (x,), (dx,))[1]
-        return self._jt(x, self.theta, back(jv.detach())[0])
+        _, _, traj, back = self.current
+        jv = torch.func.jvp(self.residual, traj, self.sweeps.jv(traj, self.theta, v))[1]
+        return self._jt(traj, self.theta, back(jv.detach()))
 
     def _cg(self, g):
         """(G + lam I) s = g by conjugate gradients from s = 0"""
@@ -1015,3 +1020,62 @@ class MatrixFreeLM:
         x0 = (xobs[:, 0] if ini_state is None else rt.dev(ini_state)).contiguous().clone()
         target = torch.where(missing, torch.zeros_like(xobs), xobs)
         return cls(sid, x0, inputs, theta0, lambda state: (state - target) * scale, **kw)
+
+    @classmethod
+    def for_cp(cls, cp, ini_state, horizon, theta0, residual, lam0=1e-3, up=10.0, down=10.0, lam_min=1e-12, lam_max=1e8, cg_tol=1e-8, cg_max=None):
+        """The same loop for the policy of a PDP.ControlPlanning `cp` (setPolyControl / setNeuralPolicy): ONE theta [p] shared by the rollouts from ini_state [B, n]
+        over `horizon` steps, residual(state [B, T+1, n], control [B, T, m]) -> r written in torch - planning to waypoints, to a reference trajectory, to a terminal
+        state.  One evaluation is one rollout (ControlPlanning.integrateSys_batch); a Gauss-Newton product is rollout_jvp_batch -> J_h -> J_h' -> rollout_vjp_batch,
+        two sweeps on the saved rollout whatever p is (no size is refused: beyond the sweeps' limits both take their materialised routes).  Schedule, inner solve and
+        the keys of run(): those of the class."""
+        shape = lambda a: tuple(int(k) for k in (a.shape if hasattr(a, "shape") else np.shape(a)))
+        if not hasattr(cp, "_policy"):
+            raise ValueError("MatrixFreeLM.for_cp: set the control policy first (setPolyControl / setNeuralPolicy / init_step)")
+        p, sx = int(cp.n_auxvar), shape(ini_state)
+        if len(sx) != 2 or sx[1] != cp.n_state or sx[0] < 1:
+            raise ValueError("MatrixFreeLM.for_cp: ini_state must be [B, n] with n = %d and B >= 1, got %s" % (cp.n_state, sx))
+        if int(horizon) < 1:
+            raise ValueError("MatrixFreeLM.for_cp: horizon must be at least 1, got %s" % (horizon,))
+        if int(np.prod(shape(theta0))) != p:
+            raise ValueError("MatrixFreeLM.for_cp: theta0 must be [p] with p = %d (one policy shared by the batch), got %s" % (p, shape(theta0)))
+        if not callable(residual):
+            raise ValueError("MatrixFreeLM.for_cp: residual must be a function of the rollouts (state [B, T+1, n], control [B, T, m])")
+        loop = cls.__new__(cls)
+        loop.cp, loop.x0, loop.horizon = cp, rt.dev(ini_state), int(horizon)
+        loop._setup(_CPSweeps(cp, loop.x0, loop.horizon), sx[0], p, theta0, residual, lam0, up, down, lam_min, lam_max, cg_tol, cg_max)
+        return loop
+
+
+class _SysIDSweeps:
+    """MatrixFreeLM's way to a PDP.SysID: the rollout under the recorded inputs, its tangent and its adjoint sweep (the residual takes the states)"""
+
+    def __init__(self, sid, x0, u):
+        self.sid, self.x0, self.u = sid, x0, u
+
+    def rollout(self, theta):
+        return (self.sid.integrateDyn_batch(self.x0, self.u, theta),)
+
+    def jv(self, traj, theta, v):
+        return (self.sid.rollout_jvp_batch(traj[0], self.u, theta, d_auxvar=v),)
+
+    def jt(self, traj, theta, w):
+        return self.sid.rollout_vjp_batch(traj[0], self.u, theta, w[0].detach().contiguous(), want_ini=False)["grad_theta"].sum(dim=0)
+
+
+class _CPSweeps:
+    """... and to a PDP.ControlPlanning: the rollout under its policy (the residual takes the states and the controls)"""
+
+    def __init__(self, cp, x0, horizon):
+        self.cp, self.x0, self.horizon = cp, x0, horizon
+
+    def rollout(self, theta):
+        x, u, _ = self.cp.integrateSys_batch(self.x0, self.horizon, theta)
+        return x, u
+
+    def jv(self, traj, theta, v):
+        out = self.cp.rollout_jvp_batch(traj[0], traj[1], theta, d_auxvar=v)
+        return out["d_state"], out["d_control"]
+
+    def jt(self, traj, theta, w):
+        gx, gu = (a.new_zeros(a.shape) if g is None else g.detach().contiguous() for a, g in zip(traj, w))
+        return self.cp.rollout_vjp_batch(traj[0], theta, gx, gu, want_ini=False)["grad_theta"].sum(dim=0)

@@ -12,8 +12,8 @@ import numpy as np
 
 from .abi import (LM_STATES, PDP_E, PDP_E_SIZE, PDP_GRAD_GAUSS_NEWTON, PDP_GRAD_SKIP_MISSING, PDP_MS_FROM_CONTROLS, PDP_MS_NO_RESTORATION,  # noqa: F401
                   PDP_MS_PREDICT, PDP_MS_PREDICT_GUARD, PDP_MS_PREDICT_PRIMAL, PDP_MS_WARM, PDP_MS_WITH_SOC, PDP_MS_WITH_WATCHDOG, PDP_OC_COTANGENT, PDP_OC_GIVEN_TRAJ,
-                  PDP_OC_PACKED, PDP_OC_RECORD_PRIMAL, PDP_POLICY_COTANGENT, PDP_POLICY_MLP, PDP_POLICY_POLY, PDP_POLICY_TABLE, PdpLmPrior, PdpLmSchedule, PdpLmState, PdpLqrProblem, PdpMat,
-                  PdpModelInfo, PdpOcAuxsys, PdpOcMsOpts, PdpOcSensOut, PdpOcSolveOpts, PdpPolicy, PdpPolicyCot, entry_points)
+                  PDP_OC_PACKED, PDP_OC_RECORD_PRIMAL, PDP_POLICY_COTANGENT, PDP_POLICY_MLP, PDP_POLICY_POLY, PDP_POLICY_TABLE, PDP_POLICY_TANGENT, PdpLmPrior, PdpLmSchedule, PdpLmState, PdpLqrProblem, PdpMat,
+                  PdpModelInfo, PdpOcAuxsys, PdpOcMsOpts, PdpOcSensOut, PdpOcSolveOpts, PdpPolicy, PdpPolicyCot, PdpPolicyTan, entry_points)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
@@ -1209,6 +1209,81 @@ class ModelLib:
             out["grad_theta"].copy_(g[:, :p])
         if "grad_x0" in out:
             out["grad_x0"].copy_(g[:, p:])
+
+    def cp_jvp_rows(self):
+        """Pool rows (time steps per lane-parallel pass) of the ControlPlanning tangent sweep, cp_jvp_kernel: csrc/pdp_sweep_pool.h's rule restated as cp_vjp_rows does,
+        on the shorter row of CpJvpPool - PATH_NVAR + n + m doubles, made odd; what a pool of SWEEP_POOL_DOUBLES holds of them, at least 4 and at most 64.  The result
+        bits do not depend on the rows: tests place their chunk edges by them."""
+        import re
+        from . import codegen
+        src = open(os.path.join(codegen.GEN_DIR, self.name + ".h")).read()
+        nvar = int(re.search(r"\bPATH_NVAR\s*=\s*(\d+)", src).group(1))
+        stride = (nvar + self.n + self.m) | 1
+        return min(64, max(4, SWEEP_POOL_DOUBLES // stride))
+
+    def cp_rollout_jvp(self, pol, p, x, u, theta, d_theta=None, d_x0=None, want_control=True, force_materialised=False):
+        """The rollout under a policy as a Jacobian-vector product (pdp_cp_step_batched with a pdp_policy_tan, include/pdp_hip.h: the semantics): x [B, T+1, n] and
+        u [B, T, m] the rollout of cp_integrate for theta ([p] or [B, p]); the direction d_theta ([p]: shared by the batch, or [B, p]) and d_x0 [B, n], each None for
+        zero, not both -> dict(d_state [B, T+1, n], d_control [B, T, m]), the tangent of the rollout along it, one launch of the tangent sweep
+        d_u[t] = pi_x d_x[t] + pi_theta d_theta, d_x[t+1] = F_t d_x[t] + G_t d_u[t].  want_control=False: d_control is not stored.  Beyond the sweep's limits
+        (PDP_E_SIZE: those of cp_rollout_vjp) ONE column of the forward sensitivities is integrated through the materialised kernels: no size is refused.
+        force_materialised: that route whatever the size (probes, tests).  Shape errors are ValueErrors before any foreign call."""
+        sx, su = _shape_of(x), _shape_of(u)
+        if len(sx) != 3 or sx[2] != self.n or sx[0] < 1 or sx[1] < 2:
+            raise ValueError("cp_rollout_jvp: state_traj must be [B, T+1, %d] with B, T >= 1, got %s" % (self.n, sx))
+        B, T = sx[0], sx[1] - 1
+        if su != (B, T, self.m):
+            raise ValueError("cp_rollout_jvp: control_traj must be [B, T, m] = %s, got %s" % ((B, T, self.m), su))
+        p = int(p)
+        if _shape_of(theta) not in ((p,), (1, p), (B, p)):
+            raise ValueError("cp_rollout_jvp: theta must be [p] or [B, p] with p = %d, B = %d, got %s" % (p, B, _shape_of(theta)))
+        if d_theta is None and d_x0 is None:
+            raise ValueError("cp_rollout_jvp: d_theta and d_x0 are both None - nothing to compute")
+        if d_theta is not None and _shape_of(d_theta) not in ((p,), (1, p), (B, p)):
+            raise ValueError("cp_rollout_jvp: d_theta must be [p] or [B, p] with p = %d, B = %d, got %s" % (p, B, _shape_of(d_theta)))
+        if d_x0 is not None and _shape_of(d_x0) != (B, self.n):
+            raise ValueError("cp_rollout_jvp: d_x0 must be [B, n] = %s, got %s" % ((B, self.n), _shape_of(d_x0)))
+        torch = torch_cuda()
+        x, u = dev(x), dev(u)
+        th, tb = self._theta(theta, B, p)
+        dth, dtb = self._theta(d_theta, B, p) if d_theta is not None else (None, 0)
+        dx0 = dev(d_x0) if d_x0 is not None else None
+        out = {"d_state": torch.empty((B, T + 1, self.n), dtype=torch.float64, device="cuda")}      # (every entry is written exactly once: no need to clear them)
+        if want_control:
+            out["d_control"] = torch.empty((B, T, self.m), dtype=torch.float64, device="cuda")
+        rc = PDP_E_SIZE
+        if not force_materialised:
+            tan = PdpPolicyTan()
+            C.memmove(C.byref(tan.pol), C.byref(pol), C.sizeof(PdpPolicy))
+            tan.pol.kind = pol.kind | PDP_POLICY_TANGENT
+            tan.x, tan.u, tan.d_x = x.data_ptr(), u.data_ptr(), out["d_state"].data_ptr()
+            tan.d_theta, tan.d_theta_bstride = (dth.data_ptr() if dth is not None else None), dtb
+            tan.d_x0 = dx0.data_ptr() if dx0 is not None else None
+            tan.d_u = out["d_control"].data_ptr() if want_control else None
+            rc = self.lib.pdp_cp_step_batched(B, T, C.cast(C.byref(tan), C.POINTER(PdpPolicy)), p, None, ptr(th), tb, None, None, None, None, None, 0,
+                                              current_stream_ptr())
+        if rc == PDP_E_SIZE:
+            self._cp_rollout_jvp_materialised(pol, p, x, u, th, dth, dx0, out)
+            rc = 0
+        check(rc, "pdp_cp_step_batched (PDP_POLICY_TANGENT)")
+        return out
+
+    def _cp_rollout_jvp_materialised(self, pol, p, x, u, th, dth, dx0, out):
+        """cp_rollout_jvp through the materialised kernels, on ONE column: getAuxSys, then dUe @ d_theta as a [B, T, m, 1] block, then integrateAuxSys from
+        X_0 = d_x0[:, :, None]"""
+        torch = torch_cuda()
+        B, T = x.shape[0], x.shape[1] - 1
+        aux = self.cp_auxsys(pol, p, x, u, th, want_cost_grads=False)
+        if dth is None:
+            col = x.new_zeros((B, T, self.m, 1))
+        else:
+            v = dth.reshape(-1, p)
+            col = (aux["dUe"] @ (v[:, None, :, None] if v.shape[0] == B else v[0][:, None])).contiguous()
+        X0 = (x.new_zeros((B, self.n, 1)) if dx0 is None else dx0[:, :, None]).contiguous()
+        X, U = cp_aux_integrate(aux["dynF"], aux["dynG"], aux["dUx"], col, X0)
+        out["d_state"].copy_(X[..., 0])
+        if "d_control" in out:
+            out["d_control"].copy_(U[..., 0])
 
     # -- SysID
     def sysid_integrate(self, x0, u, theta):
