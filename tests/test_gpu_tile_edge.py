@@ -272,20 +272,8 @@ def test_trajectories_per_workgroup_layouts_agree_to_the_bit(run, name):
 
 
 def _judge_solve(margins, tag, got, b, ref, log, worst=None):
-    """tests/test_gpu_ocsolver.py::_follows on row b of a solver result (dict of [B, ...] arrays)"""
-    assert bool(got["converged"][b]) and int(got["status"][b]) == 0, (tag, b, got["status"][b])
-    assert int(got["iterations"][b]) == ref["iterations"] == len(log), (tag, b, int(got["iterations"][b]), ref["iterations"])
-    for r, l in zip(got["log"][b], log):
-        assert r[5] == l["alpha"], (tag, b, l["it"], r[5], l["alpha"])
-        assert abs(r[4] - l["dw"]) <= 1e-12 * max(1.0, l["dw"]), (tag, b, l["it"], r[4], l["dw"])
-        assert abs(r[1] - l["f"]) <= 1e-9 * max(1.0, abs(l["f"])), (tag, b, l["it"], r[1], l["f"])
-        assert abs(r[7] - l["theta"]) <= 1e-9 * max(1.0, l["theta"]) and abs(r[2] - l["inf_pr"]) <= 1e-9 * max(1.0, l["inf_pr"]), (tag, b, l["it"], r[7], l["theta"], r[2], l["inf_pr"])
-    for k, kr in (("state", "state_traj_opt"), ("control", "control_traj_opt"), ("costate", "costate_traj_opt")):
-        err = c.rel(got[k][b], ref[kr])
-        if worst is None:
-            margins.check("tile edge solver %s row %d: %s vs ipopt_ms.solve (relative to the largest entry)" % (tag, b, k), err, 1e-9)
-        else:
-            worst.add("%s vs ipopt_ms.solve (relative to the largest entry)" % k, err, "row %d" % b)
+    """tile_edge_common.judge_solve (shared with tests/test_gpu_frontend_ops.py): tests/test_gpu_ocsolver.py::_follows on row b of a solver result"""
+    c.judge_solve(margins, tag, got, b, ref, log, worst)
 
 
 def _solver_result(res, prefix):

@@ -264,3 +264,21 @@ def solver_oracle(name, regime, row):
     log = []
     ref = ipopt_ms.solve(model_oracle(name), solver_draws(name, regime)[row], REGIMES[regime]["T"], solver_theta(name, regime), tol=1e-10, log=log, max_iter=100)
     return ref, log
+
+
+def judge_solve(margins, tag, got, b, ref, log, worst=None, prefix="tile edge solver"):
+    """tests/test_gpu_ocsolver.py::_follows on row b of a solver result (dict of [B, ...] arrays): the oracle's iteration count and step lengths, dw to 1e-12, f / inf_pr /
+    theta to 1e-9, state / control / costate to 1e-9 of the largest entry - recorded through `margins` under `prefix`, or collected in `worst` (its .add)"""
+    assert bool(got["converged"][b]) and int(got["status"][b]) == 0, (tag, b, got["status"][b])
+    assert int(got["iterations"][b]) == ref["iterations"] == len(log), (tag, b, int(got["iterations"][b]), ref["iterations"])
+    for r, l in zip(got["log"][b], log):
+        assert r[5] == l["alpha"], (tag, b, l["it"], r[5], l["alpha"])
+        assert abs(r[4] - l["dw"]) <= 1e-12 * max(1.0, l["dw"]), (tag, b, l["it"], r[4], l["dw"])
+        assert abs(r[1] - l["f"]) <= 1e-9 * max(1.0, abs(l["f"])), (tag, b, l["it"], r[1], l["f"])
+        assert abs(r[7] - l["theta"]) <= 1e-9 * max(1.0, l["theta"]) and abs(r[2] - l["inf_pr"]) <= 1e-9 * max(1.0, l["inf_pr"]), (tag, b, l["it"], r[7], l["theta"], r[2], l["inf_pr"])
+    for k, kr in (("state", "state_traj_opt"), ("control", "control_traj_opt"), ("costate", "costate_traj_opt")):
+        err = rel(got[k][b], ref[kr])
+        if worst is None:
+            margins.check("%s %s row %d: %s vs ipopt_ms.solve (relative to the largest entry)" % (prefix, tag, b, k), err, 1e-9)
+        else:
+            worst.add("%s vs ipopt_ms.solve (relative to the largest entry)" % k, err, "row %d" % b)
