@@ -11,6 +11,8 @@ The kernel-selecting variables are read once per process, so the kernels run in 
 Fused unit: every model x horizon (1, 7, ROWS + 6, ROWS + 7: the last two span two backward chunks) x {shared, per-sample theta} x {rollout, given trajectory}, B = 5,
 every sample against oracle.pdp_oc_unit on the same inputs.  Solver: every model x regime, B = 3, row by row against oracle.ipopt_ms.solve.
 tests/test_tile_edge_inputs.py holds the conditions that make these comparisons mean something (the oracle's own rounding error is below 1e-15 here).
+tests/test_gpu_tile_edge_modes.py runs the unit's masked, weighted / Huber and initial-state modes on the same models, and these calls again, at horizons on both sides of
+every forward chunk (none of the four horizons here spans two forward chunks).
 
 Tolerance: 1e-10 relative to the largest entry of the compared array, per sample, through the `margins` fixture - one line per (variant, model,
 horizon, quantity) with the largest figure over theta modes, trajectory modes and samples; the loss to 1e-12 relative; the solver as
@@ -44,17 +46,18 @@ def npy(t):
     return t.detach().cpu().numpy()
 
 
-def _cases(info):
-    return [(T, per_sample, given) for T in c.unit_horizons(info) for per_sample in (False, True) for given in (False, True)]
+def _cases(info, horizons=None):
+    return [(T, per_sample, given) for T in (c.unit_horizons(info) if horizons is None else horizons) for per_sample in (False, True) for given in (False, True)]
 
 
 # ---- child process ------------------------------------------------------------------------------------------------------------------------------------------
-def _unit(out, name, oc):
-    """every case of one model: the default unit (plain, and with the sensitivities and the Riccati record), the cotangent unit, the Gauss-Newton unit"""
+def _unit(out, name, oc, horizons=None):
+    """every case of one model: the default unit (plain, and with the sensitivities and the Riccati record), the cotangent unit, the Gauss-Newton unit
+    (horizons: tests/test_gpu_tile_edge_modes.py runs the same calls at its own)"""
     import torch
     from pdp_amd import runtime as rt
     n, m, p = c.MODELS[name]
-    for T, per_sample, given in _cases(oc._model_info):
+    for T, per_sample, given in _cases(oc._model_info, horizons):
         inp = c.unit_inputs(name, T)
         B = inp["B"]
         th = inp["theta_b"] if per_sample else inp["theta"]

@@ -118,29 +118,31 @@ RICCATI_SCRATCH = 272 + 272 + 64
 SLICE = 160 * 1024 // 8 // 4
 
 
-def fused3_layout(info):
+def fused3_layout(info, xw=0):
+    """xw: the extra words of a forward row (Fused3Layout<Mdl, XW>: n + m scales in the weighted mode, with them dlT is n words longer); 0 in every other mode"""
     n, m, p, nv, nc = info["n"], info["m"], info["p"], info["nvar"], info["nconst"]
     npc = max(1, info["npc"])
     NA, NB = nv["patha"], max(nv["pathb"], 16)
     BSTRIDE = (NA + NB + 1 + nc["patha"] + nc["pathb"]) | 1
-    FSTRIDE = (nv["fwd"] + n + m + 1 + nc["fwd"]) | 1
+    FSTRIDE = (nv["fwd"] + n + m + xw + 1 + nc["fwd"]) | 1
     PAR = RICCATI_SCRATCH + 1 + nc["fin"] + nv["fin"]
-    POOL = PAR + p + npc + n + 8
+    POOL = PAR + p + npc + n + (n if xw else 0) + 8
     BUF = (SLICE - POOL) // 2
     return dict(BSTRIDE=BSTRIDE, FSTRIDE=FSTRIDE, BUF=BUF, ROWS=min(64, BUF // BSTRIDE), ROWSF=min(64, BUF // FSTRIDE))
 
 
-def fused3_ok(info, T):
-    L = fused3_layout(info)
+def fused3_ok(info, T, xw=0):
+    L = fused3_layout(info, xw)
     return info["n"] > 4 and L["ROWS"] >= 4 and L["ROWSF"] >= 4 and (T + 1) * info["n"] + T * info["m"] <= 2 * L["BUF"]
 
 
-def fused_accepts(info, T):
-    """pdp_oc_pdp_grad_batched does not answer PDP_E_SIZE: one tile per matrix, one [control | parameter] tile, the one-wave kernel's LDS within a CU's 160 KB"""
+def fused_accepts(info, T, xw=0):
+    """pdp_oc_pdp_grad_batched does not answer PDP_E_SIZE: one tile per matrix, one [control | parameter] tile, the one-wave kernel's LDS within a CU's 160 KB
+    (fused_lds_bytes<Mdl, XW>: xw further words per forward row and, with them, n behind dlT)"""
     n, m, p, nv, nc = info["n"], info["m"], info["p"], info["nvar"], info["nconst"]
     NC = 1 + max(nc["patha"] + nc["pathb"], nc["fwd"], nc["fin"])
-    pool = max(info["chunk"] * max((nv["patha"] + nv["pathb"] + n) | 1, (nv["fwd"] + n + m) | 1), nv["fin"] + 1, (T + 1) * n + T * m)
-    return n <= 16 and m <= 4 and m + p <= 16 and 8 * (RICCATI_SCRATCH + NC + pool + n + p + max(1, info["npc"]) + 8) <= 160 * 1024
+    pool = max(info["chunk"] * max((nv["patha"] + nv["pathb"] + n) | 1, (nv["fwd"] + n + m + xw) | 1), nv["fin"] + 1, (T + 1) * n + T * m)
+    return n <= 16 and m <= 4 and m + p <= 16 and 8 * (RICCATI_SCRATCH + NC + pool + n + (n if xw else 0) + p + max(1, info["npc"]) + 8) <= 160 * 1024
 
 
 def ms2_layout(info):
